@@ -972,7 +972,7 @@ def test_bench_self_launches_its_ranks():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     p = subprocess.Popen([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline', '--conformers', '256'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                          '--no-cpu-baseline', '--conformers', '256', '--full'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          start_new_session=True, env=env, cwd=root)
     try:
         out, err = p.communicate(timeout=600)
@@ -1006,7 +1006,7 @@ def test_bench_eight_ranks_on_one_box():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'LOCAL_WORLD_SIZE'):
         env.pop(k, None)
     p = subprocess.Popen([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline', '--conformers', '64', '--no-train-roofline'], stdout=subprocess.PIPE,
+                          '--no-cpu-baseline', '--conformers', '64', '--no-train-roofline', '--full'], stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, start_new_session=True, env=env, cwd=root)
     try:
         out, err = p.communicate(timeout=420)
@@ -1036,3 +1036,36 @@ def test_bench_eight_ranks_on_one_box():
     for key in ('"strong"', '"forms"', '"deferred"', '"host_gap_ms"', '"timing_anomaly"'):
         assert key in tail, key
     assert line['deferred']['repeats_needed'] == 0 and line['library_config']['version'] >= 106
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps in one region, prints the headline fields only, and with
+    --dump-outputs writes the last timed step's results; two runs with the same arguments write the same arrays bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'LOCAL_WORLD_SIZE'):
+        env.pop(k, None)
+    dumps = []
+    for run in ('a', 'b'):
+        d = str(tmp_path / run)
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2',
+                            '--conformers', '64', '--dump-outputs', d], capture_output=True, text=True, env=env, cwd=root,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, r.stdout[-3000:]
+        line = json.loads(lines[0])
+        assert line['full'] is False and line['steps'] == 7 and len(line['region_ms_per_step']) == 1
+        assert line['unit'] == 'atom-steps/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+        assert line['ms_per_step'] > 0 and abs(line['value'] - 64 * 21 / (line['ms_per_step'] * 1e-3)) <= 1e-3 * line['value']
+        assert not {'kernel_classes', 'cpu_baseline', 'train', 'single_stream', 'roofline'} & set(line)
+        assert line['outputs']['energy'] == [64] and line['outputs']['gradient_force'] == [64 * 21, 3]
+        dumps.append({f: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    assert set(dumps[0]) == {f'{n}.npy' for n in ('energy', 'gradient_force', 'edge_index', 'atom_node', 'force_node')}
+    assert dumps[0]['edge_index.npy'].dtype == np.float64 and dumps[0]['energy.npy'].dtype == np.float32
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f

@@ -183,30 +183,73 @@ def test_model_surgery_like_ase_interface():
         get_output_by_string('hessian')
 
 
-def test_bench_self_launch_command(monkeypatch):
+def test_bench_self_launch_command():
     """bench.py --gpus N without a launcher starts `python -m torch.distributed.run --nproc-per-node N bench.py <same argv>` as a
-    CHILD process (rendezvous on 127.0.0.1) and returns its exit code -- it never execs, and it does so before any GPU call."""
+    CHILD process (rendezvous on 127.0.0.1) and returns its exit code -- it never execs, and it does so before any GPU call.
+    Checked in a fresh interpreter: in a whole-suite run on a GPU box, earlier tests have already initialised the GPU in this one."""
+    import json
     import subprocess
     import sys
-    import bench
-    seen = {}
-
-    def fake_call(cmd, env=None):
-        seen['cmd'], seen['env'] = cmd, env
-        return 7
-    monkeypatch.setattr(subprocess, 'call', fake_call)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '4', '--steps', '3', '--warmup', '1'])
+    code = (
+        'import json, subprocess, sys\n'
+        f'sys.path.insert(0, {ROOT!r})\n'
+        'seen = {}\n'
+        'def fake_call(cmd, env=None):\n'
+        '    seen["cmd"], seen["env"] = cmd, env\n'
+        '    return 7\n'
+        'subprocess.call = fake_call\n'
+        'sys.argv = ["bench.py", "--gpus", "4", "--steps", "3", "--warmup", "1"]\n'
+        'import torch, bench\n'
+        'try:\n'
+        '    bench.main()\n'
+        '    code = None\n'
+        'except SystemExit as exc:\n'
+        '    code = exc.code\n'
+        'print(json.dumps({"code": code, "cmd": seen.get("cmd"), "ipc": (seen.get("env") or {}).get("HSA_ENABLE_IPC_MODE_LEGACY"),\n'
+        '                  "cuda_initialized": torch.cuda.is_initialized()}))\n')
+    env = dict(os.environ)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        monkeypatch.delenv(k, raising=False)
-    with pytest.raises(SystemExit) as exc:
-        bench.main()
-    assert exc.value.code == 7
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    seen = json.loads(r.stdout.strip().splitlines()[-1])
+    assert seen['code'] == 7
     cmd = seen['cmd']
     assert cmd[:3] == [sys.executable, '-m', 'torch.distributed.run'] and '--nproc-per-node=4' in cmd
     assert cmd[cmd.index('--master-addr') + 1] == '127.0.0.1'
     assert cmd[-6:] == ['--gpus', '4', '--steps', '3', '--warmup', '1'] and cmd[-7].endswith('bench.py')
-    assert seen['env']['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
-    assert not torch.cuda.is_initialized()
+    assert seen['ipc'] == '0'
+    assert not seen['cuda_initialized']
+
+
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: every array of the step's result bag as <name>.npy in float32 / float64 (edge_index exactly, as
+    float64); what does not fit the byte budget is a seeded sample along the long axis with its slice numbers beside it, the same
+    slices on every call for the same shapes."""
+    import types
+    import bench
+    g = torch.Generator().manual_seed(0)
+    n, e = 300, 2000
+    out = types.SimpleNamespace(energy=torch.randn(10, generator=g), gradient_force=torch.randn(n, 3, generator=g),
+                                edge_index=torch.randint(0, n, (2, e), generator=g), atom_node=torch.randn(n, 128, generator=g),
+                                force_node=torch.randn(n, 3, 128, generator=g))
+    shapes = bench.dump_outputs(out, str(tmp_path / 'all'))
+    assert shapes == {'energy': [10], 'gradient_force': [n, 3], 'edge_index': [2, e], 'atom_node': [n, 128], 'force_node': [n, 3, 128]}
+    for name, _ in bench.DUMP_FIELDS:
+        a = np.load(tmp_path / 'all' / f'{name}.npy')
+        want = getattr(out, name).numpy()
+        assert a.dtype == (np.float64 if name == 'edge_index' else np.float32) and np.array_equal(a, want.astype(a.dtype))
+    limit = 300_000                                   # atom_node 153 600 bytes, force_node 460 800: both are sampled
+    for run in ('a', 'b'):
+        bench.dump_outputs(out, str(tmp_path / run), limit=limit)
+        files = os.listdir(tmp_path / run)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= limit
+        assert 'energy_sample_index.npy' not in files and 'edge_index_sample_index.npy' not in files
+    for name in ('atom_node', 'force_node'):
+        idx = np.load(tmp_path / 'a' / f'{name}_sample_index.npy')
+        assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+        assert np.array_equal(idx, np.load(tmp_path / 'b' / f'{name}_sample_index.npy'))
+        assert np.array_equal(np.load(tmp_path / 'a' / f'{name}.npy'), getattr(out, name).numpy()[idx.astype(np.int64)])
 
 
 def test_no_packed_fp32_instruction_in_any_kernel():

@@ -1,7 +1,7 @@
 # A/B of library builds on one box: tools/ab_np.sh lib1.so lib2.so ...   (python bench.py --steps 30 each, twice)
 for r in 1 2; do for v in "$@"; do
 echo -n "$v: "
-NNHIP_ALLOW_TOOLING_LIB=1 NNHIP_LIB_NAME=$v python bench.py --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
+NNHIP_ALLOW_TOOLING_LIB=1 NNHIP_LIB_NAME=$v python bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1])
 k=d.get('kernel_classes',{})

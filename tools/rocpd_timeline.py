@@ -2,7 +2,7 @@
 """Print the kernel sequence of the LAST step in a rocprofv3 rocpd (.db) kernel trace: start offset, duration and the idle
 gap before each dispatch.  A step is delimited by the first kernel name given (default mol_ptr_kernel / cells kernel).
 usage: python tools/rocpd_timeline.py results.db [first_kernel_substring] [steps_back]   (steps_back: 0 = the last complete
-step; bench.py's last steps are its event-instrumented pass, so pass e.g. 12 to look at a step of the timed region)"""
+step; the last steps of `bench.py --full` are its event-instrumented pass, so pass e.g. 12 there to look at a step of the timed region)"""
 import sqlite3
 import sys
 
