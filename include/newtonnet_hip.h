@@ -754,6 +754,38 @@ int nnhip_direct_force_bwd(const float* g_out, const float* force_node, const in
                            void* stream);
 
 /* --------------------------------------------------------------------------
+ * Analytic Hessians of the energy with respect to the positions (cell fixed): HessianOutput, newtonnet/models/output.py:134-152
+ * (H = d^2E/dpos^2 = -d gradient_force / dpos; MLAseCalculator 'hessian', utils/ase_interface.py:19,75-77).  Tangent over reverse:
+ * sweeps 3-4 of the training step run along a position direction v with sign +1 and the reverse seed 1 + eps 0, plus three stages
+ * the training step has no use for -- the tangents of g_u (force-message adjoint), of g_x (radial adjoint, second derivative of
+ * the Bessel x envelope basis in fp64) and of the geometric adjoint -- and the force gather (csrc/hessian.hip).  No weight-gradient,
+ * column-sum or per-element-sum launches; fp32-grade products (train_ws->bf16_wgrad must be 0); no float atomics.
+ * Both calls need a prior nnhip_train_values on the same train_ws (the values and value adjoints of the batch).
+ *   nnhip_hessian_vp    : hv[N][3] = H v for v[N][3] (device pointers; H is block-diagonal over the molecules).
+ *   nnhip_hessian_blocks: ceil(n_dirs / n_rep) passes of the above with one-hot directions built on the device.  The batch of
+ *                         train_ws is n_rep replicas of an original batch of n_mol0 molecules (molecule b = replica b / n_mol0 of
+ *                         molecule b % n_mol0; n_rep = 1: the batch itself).  Pass k gives replica r the direction dir = k n_rep + r:
+ *                         coordinate dir % 3 of local atom dir / 3 of every molecule (none where dir >= 3 n_b), and writes the
+ *                         column H e_dir of each molecule into its packed block: blocks + blk_ptr[b] is [n_b][3][n_b][3],
+ *                         blk_ptr[b] = sum_{b' < b} 9 n_b'^2 (int64, device).  n_dirs = 3 max n_b fills every block.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+  float* dg_x;            /* [L][E]     tangent of g_x (owner edges; 0 on the other direction) */
+  float* dg_u;            /* [L][E][4]  tangent of g_u */
+  float* dg_d;            /* [E][4]     tangent of the geometric adjoint g_d */
+  float* v;               /* [N][3]     direction scratch of nnhip_hessian_blocks */
+  float* hv;              /* [N][3]     column scratch of nnhip_hessian_blocks */
+  const float* zeros_b;   /* [n_mol]    zeros: the tangent of the reverse seed */
+  const int64_t* blk_ptr; /* [n_mol0]   block offsets (nnhip_hessian_blocks only) */
+  int32_t n_rep, n_mol0;  /* replicas in the batch, molecules of the original batch (nnhip_hessian_blocks only) */
+} nnhip_hvp_ws;
+size_t nnhip_hvp_ws_bytes(void); /* sizeof(nnhip_hvp_ws) of this build */
+int nnhip_hessian_vp(const nnhip_model* model, const nnhip_train_ws* train_ws, const nnhip_hvp_ws* hvp_ws, const float* v, float* hv,
+                     void* stream);
+int nnhip_hessian_blocks(const nnhip_model* model, const nnhip_train_ws* train_ws, const nnhip_hvp_ws* hvp_ws, int32_t n_dirs,
+                         float* blocks, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

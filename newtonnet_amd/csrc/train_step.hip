@@ -367,21 +367,22 @@ extern "C" int nnhip_train_grads(const nnhip_model* model, const nnhip_train_ws*
 // states directly (the direct_force head, csrc/heads.hip).  They enter the epsilon-part of the reverse sweep at its top: that
 // sweep is the tangent of the value adjoint and is linear in its seeds, so every weight-gradient product below picks up the
 // plain back-propagation of these terms next to the tangent-over-reverse terms of the energy / gradient-force loss.
-extern "C" int nnhip_train_grads_seeded(const nnhip_model* model, const nnhip_train_ws* w, const float* g_energy,
-                                        const float* g_forces, const float* seed_a, const float* seed_f, void* s) {
-  TS_TRY(check(model, w, "nnhip_train_grads"));
-  if (!g_energy || !g_forces) {
-    nnhip_set_error("nnhip_train_grads: bad arguments");
-    return NNHIP_E_INVALID;
-  }
+// Sweeps 3 and 4: the tangent forward sweep along the position direction sign * v and the tangent reverse sweep with the reverse
+// seed 1 + eps g_energy.  `layer_hook` (may be NULL) runs inside the layer loop of sweep 4 once layer l's tangents are complete
+// (after nnhip_message_tan_bwd, while w->dgf still holds the tangent of gf[l]): the Hessian-vector product adds its stages there.
+struct LayerHook {
+  int (*fn)(const nnhip_model* model, const nnhip_train_ws* w, const void* ctx, int l, void* s);
+  const void* ctx;
+};
+static int tangent_sweeps(const nnhip_model* model, const nnhip_train_ws* w, const float* v, float sign, const float* g_energy,
+                          const float* seed_a, const float* seed_f, const LayerHook* layer_hook, void* s) {
   const int N = w->n_atoms, E = w->n_edges, L = w->n_layers, P = E / 2, act = model->activation;
-  if (N == 0) return NNHIP_OK;
   const bool img_on = train_images(model, w);
   const bool ln = has_ln(model);
   const bool node_img = img_on && !ln;
   const bool bf = train_bf16(model, w);
-  // ---- sweep 3: tangent forward along v = -dL/dF
-  TS_TRY(nnhip_edge_tangent_geom(g_forces, -1.0f, w->edge_index, w->geo, E, model->cutoff, w->tgeo, s));
+  // ---- sweep 3: tangent forward along sign * v (training: v = dL/dF, sign = -1)
+  TS_TRY(nnhip_edge_tangent_geom(v, sign, w->edge_index, w->geo, E, model->cutoff, w->tgeo, s));
   for (int l = 0; l < L; ++l) {
     const nnhip_layer_params& lp = model->layer[l];
     const bool first = l == 0;
@@ -523,6 +524,7 @@ extern "C" int nnhip_train_grads_seeded(const nnhip_model* model, const nnhip_tr
     }
     TS_TRY(nnhip_message_tan_bwd(w->g_msg[l], w->dg_msg, w->GA[l], w->dGA, w->m[l], first ? nullptr : w->dm[l], w->xg, w->tgeo,
                                  w->ftab[l], w->row_ptr, w->col, w->pid, w->dg_m[l], w->g_eps[l], w->dg_eps[l], N, s));
+    if (layer_hook) TS_TRY(layer_hook->fn(model, w, layer_hook->ctx, l, s));
     if (node_img) {
       TS_TRY(tan_bwd_fused(w->dg_m[l], w->hn[l], first ? nullptr : w->t_n[l], first ? nullptr : w->dhn[l], w->dg_hn[l], 1,
                            w->wimg[l][IMG_NODE2_T], w->wimg[l][IMG_NODE0_T], l - 1, first ? nullptr : nxt));
@@ -538,10 +540,94 @@ extern "C" int nnhip_train_grads_seeded(const nnhip_model* model, const nnhip_tr
     dGf = nxt;
     pp ^= 1;
   }
+  return NNHIP_OK;
+}
+
+extern "C" int nnhip_train_grads_seeded(const nnhip_model* model, const nnhip_train_ws* w, const float* g_energy,
+                                        const float* g_forces, const float* seed_a, const float* seed_f, void* s) {
+  TS_TRY(check(model, w, "nnhip_train_grads"));
+  if (!g_energy || !g_forces) {
+    nnhip_set_error("nnhip_train_grads: bad arguments");
+    return NNHIP_E_INVALID;
+  }
+  const int N = w->n_atoms, E = w->n_edges, P = E / 2;
+  if (N == 0) return NNHIP_OK;
+  TS_TRY(tangent_sweeps(model, w, g_forces, -1.0f, g_energy, seed_a, seed_f, nullptr, s));
   // ---- weight gradients: one batched split-K launch + its reduction, column sums, per-element sums
   TS_TRY(nnhip_pair_rbf(w->rbf, w->drbf, w->tgeo, w->edge_index, w->pid, E, w->n_basis, w->rb, s));
   TS_TRY(nnhip_wgrad_batch(w->probs, w->n_probs, w->chunks, w->slabs, w->bf16_wgrad, P, s));
   TS_TRY(nnhip_colsum_batch(w->sums, w->n_sums, w->cs_scratch, s));
   TS_TRY(nnhip_species_sum(w->dGA, NF, NF, w->z, N, w->sp_scratch, w->g_embedding, 0, NF, NF, nullptr, 0, 0, 0, nullptr, 0, s));
   return nnhip_species_sum(w->scal, 4, 4, w->z, N, w->sp_scratch, w->g_scale, 0, 1, 1, w->g_shift, 1, 1, 1, w->g_head4_b, 2, s);
+}
+
+// ---- Hessian-vector products (include/newtonnet_hip.h, nnhip_hessian_*; the stages: csrc/hessian.hip)
+int launch_hvp_dgu(const float* gf, const float* dgf, const float* phi1, const float* dphi1, const int* row_ptr, const int* pid,
+                   const int* xg, int n_atoms, float* dg_u, hipStream_t s);
+int launch_hvp_dgx(const int64_t* edge_index, const int* pid, const float* geo, const float* tgeo, const int* xg, const float* g_eps,
+                   const float* dg_eps, const float* edge_w, const float* freq, int nb, int env, float cutoff, int n_edges,
+                   float* dg_x, hipStream_t s);
+int launch_hvp_out(const float* g_x, const float* g_u, const float* dg_x, const float* dg_u, const float* geo, const float* tgeo,
+                   const int* row_ptr, const int* rev, int n_atoms, int n_edges, int n_layers, float cutoff, float* dg_d, float* hv,
+                   hipStream_t s);
+int launch_hess_dirs(const int64_t* batch, const int* mol_ptr, int n_atoms, int k, int n_rep, int n_mol0, float* v, hipStream_t s);
+int launch_hess_scatter(const float* hv, const int64_t* batch, const int* mol_ptr, const int64_t* blk_ptr, int n_atoms, int k,
+                        int n_rep, int n_mol0, float* blocks, hipStream_t s);
+
+extern "C" size_t nnhip_hvp_ws_bytes(void) { return sizeof(nnhip_hvp_ws); }
+
+// layer l of sweep 4 is complete: dgf = tangent of gf[l], g_eps / dg_eps of layer l written -> dg_u[l], dg_x[l]
+static int hvp_layer_stages(const nnhip_model* model, const nnhip_train_ws* w, const void* ctx, int l, void* s) {
+  const nnhip_hvp_ws* h = (const nnhip_hvp_ws*)ctx;
+  const int N = w->n_atoms, E = w->n_edges;
+  TS_TRY(launch_hvp_dgu(w->gf[l], w->dgf, w->phi1[l], w->dphi1[l], w->row_ptr, w->pid, w->xg, N, h->dg_u + (size_t)4 * l * E,
+                        (hipStream_t)s));
+  return launch_hvp_dgx(w->edge_index, w->pid, w->geo, w->tgeo, w->xg, w->g_eps[l], w->dg_eps[l], model->layer[l].edge_w,
+                        model->frequencies, model->n_basis, model->envelope, model->cutoff, E, h->dg_x + (size_t)l * E,
+                        (hipStream_t)s);
+}
+
+static int hvp_check(const nnhip_model* model, const nnhip_train_ws* w, const nnhip_hvp_ws* h, const char* who) {
+  TS_TRY(check(model, w, who));
+  if (!h || !h->dg_x || !h->dg_u || !h->dg_d || !h->zeros_b || !model->frequencies || w->bf16_wgrad != 0) {
+    nnhip_set_error("%s: bad arguments (nnhip_hvp_ws incomplete, or train_ws->bf16_wgrad != 0)", who);
+    return NNHIP_E_INVALID;
+  }
+  return NNHIP_OK;
+}
+
+static int hvp_run(const nnhip_model* model, const nnhip_train_ws* w, const nnhip_hvp_ws* h, const float* v, float* hv, void* s) {
+  const LayerHook hook = {hvp_layer_stages, h};
+  TS_TRY(tangent_sweeps(model, w, v, 1.0f, h->zeros_b, nullptr, nullptr, &hook, s));
+  return launch_hvp_out(w->g_x, w->g_u, h->dg_x, h->dg_u, w->geo, w->tgeo, w->row_ptr, w->rev, w->n_atoms, w->n_edges, w->n_layers,
+                        model->cutoff, h->dg_d, hv, (hipStream_t)s);
+}
+
+extern "C" int nnhip_hessian_vp(const nnhip_model* model, const nnhip_train_ws* w, const nnhip_hvp_ws* h, const float* v, float* hv,
+                                void* s) {
+  TS_TRY(hvp_check(model, w, h, "nnhip_hessian_vp"));
+  if (!v || !hv) {
+    nnhip_set_error("nnhip_hessian_vp: bad arguments");
+    return NNHIP_E_INVALID;
+  }
+  if (w->n_atoms == 0) return NNHIP_OK;
+  return hvp_run(model, w, h, v, hv, s);
+}
+
+extern "C" int nnhip_hessian_blocks(const nnhip_model* model, const nnhip_train_ws* w, const nnhip_hvp_ws* h, int32_t n_dirs,
+                                    float* blocks, void* s) {
+  TS_TRY(hvp_check(model, w, h, "nnhip_hessian_blocks"));
+  if (!blocks || !h->v || !h->hv || !h->blk_ptr || n_dirs < 0 || h->n_rep < 1 || h->n_mol0 < 1 ||
+      (long)h->n_rep * h->n_mol0 != w->n_mol || !w->batch || !w->mol_ptr) {
+    nnhip_set_error("nnhip_hessian_blocks: bad arguments");
+    return NNHIP_E_INVALID;
+  }
+  if (w->n_atoms == 0) return NNHIP_OK;
+  const int passes = (n_dirs + h->n_rep - 1) / h->n_rep;
+  for (int k = 0; k < passes; ++k) {
+    TS_TRY(launch_hess_dirs(w->batch, w->mol_ptr, w->n_atoms, k, h->n_rep, h->n_mol0, h->v, (hipStream_t)s));
+    TS_TRY(hvp_run(model, w, h, h->v, h->hv, s));
+    TS_TRY(launch_hess_scatter(h->hv, w->batch, w->mol_ptr, h->blk_ptr, w->n_atoms, k, h->n_rep, h->n_mol0, blocks, (hipStream_t)s));
+  }
+  return NNHIP_OK;
 }

@@ -1,0 +1,142 @@
+"""Analytic Hessians and Hessian-vector products of the energy on the HIP path.
+
+The reference's HessianOutput (newtonnet/models/output.py:134-152) returns H = d^2E/dpos^2 (cell fixed) as a dense [N,3,N,3]
+tensor from a torch.vmap of 3N double-backward calls, in train mode only.  Here H v is one tangent-over-reverse pass of the
+training kernels along v (include/newtonnet_hip.h: nnhip_hessian_vp; the three stages the training step lacks are in
+csrc/hessian.hip), and the Hessian is built from one-hot directions on the device (nnhip_hessian_blocks): molecules never
+share edges, so pass k fills column k of EVERY molecule's block at once and 3 max(n_b) passes give every block.
+
+Replica scheme: a small batch would spend its passes waiting on launch latency, so while R x N atoms stay under
+REPLICA_ATOM_BUDGET the batch is replicated R times into one graph and one value sweep, and every pass covers R directions,
+one per replica.  Large batches take R = 1 (the direction loop).
+
+Eval-only (training on Hessian labels is out of scope), fp32-grade products (no bf16 mode), current parameters on every call.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from newtonnet_amd import hip
+from newtonnet_amd import train_fused
+
+REPLICA_ATOM_BUDGET = 16384
+
+
+def _chk(rc, what):
+    if rc != 0:
+        raise hip.HipLibraryError(f'{what} failed ({rc}): {hip.lib().nnhip_last_error().decode()}')
+
+
+def _validate(model, pos):
+    if model.training:
+        raise NotImplementedError('Hessians run in eval mode only (training on Hessian labels is not supported): call model.eval()')
+    if 'energy' not in list(model.output_properties):
+        raise NotImplementedError("the Hessian is the energy's: the model needs the 'energy' head (output_properties)")
+    if not pos.is_cuda:
+        raise RuntimeError('newtonnet_amd Hessians run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
+
+
+class _Pass:
+    """Values of one (possibly replicated) batch on a workspace without weight-gradient tables, plus the HVP buffers."""
+
+    def __init__(self, model, z, pos, cell, batch, n_rep: int, blk_ptr: Optional[torch.Tensor]):
+        emb = model.embedding_layers.edge_embedding
+        n0, b0 = pos.shape[0], cell.shape[0]
+        zc = z.long().reshape(-1)
+        pd = hip._f32c(pos.detach(), 'pos')
+        cd = hip._f32c(cell.detach(), 'cell')
+        bc = batch.long().reshape(-1)
+        if n_rep > 1:
+            zc = zc.repeat(n_rep)
+            pd = pd.repeat(n_rep, 1)
+            cd = cd.repeat(n_rep, 1, 1)
+            bc = torch.cat([bc + r * b0 for r in range(n_rep)])
+        zc, pd, cd, bc = zc.contiguous(), pd.contiguous(), cd.contiguous(), bc.contiguous()
+        with torch.no_grad():
+            g = hip.build_graph(pd, cd, bc, emb.cutoff, emb.embedding.frequencies, want_rbf=True, z=zc, envelope=emb.envelope_id)
+        ws = train_fused.TrainWorkspace(model, g.n_atoms, max(g.n_edges, 2), g.n_mol, pos.device, wgrad=False)
+        runner = train_fused.Runner(model, zc, pd, cd, bc, g, ws)
+        self.model_c, self.ws_c = runner._bind()
+        ws.c.bf16_wgrad = 0                     # fp32-grade products whatever autocast says
+        self.st = hip._stream(pos.device)
+        _chk(hip.lib().nnhip_train_values(self.model_c, self.ws_c, self.st), 'nnhip_train_values')
+        if C.sizeof(hip.HvpWs) != hip.lib().nnhip_hvp_ws_bytes():
+            raise RuntimeError('nnhip_hvp_ws: the ctypes mirror and the library disagree (stale libnewtonnet_hip.so?)')
+        L, E, N = ws.L, max(g.n_edges, 1), g.n_atoms
+
+        def buf(*shape):
+            return torch.empty(*shape, dtype=torch.float32, device=pos.device)
+        self.dg_x, self.dg_u, self.dg_d = buf(L * E), buf(L * E * 4), buf(E, 4)
+        self.v, self.hv = buf(max(N, 1), 3), buf(max(N, 1), 3)
+        self.zeros_b = torch.zeros(max(g.n_mol, 1), dtype=torch.float32, device=pos.device)
+        self.blk_ptr = blk_ptr
+        h = self.h = hip.HvpWs()
+        for name in ('dg_x', 'dg_u', 'dg_d', 'v', 'hv', 'zeros_b', 'blk_ptr'):
+            t = getattr(self, name)
+            setattr(h, name, t.data_ptr() if t is not None else None)
+        h.n_rep, h.n_mol0 = n_rep, b0
+        self.keep = (g, ws, runner, zc, pd, cd, bc)    # every buffer the C views point at stays alive with this object
+
+
+def hessian_vector_product(model, z, pos, cell, batch, v) -> torch.Tensor:
+    """H v [N,3] (fp32) for a direction v [N,3]: d^2E/dpos^2 applied to v, cell held fixed (block-diagonal over molecules)."""
+    _validate(model, pos)
+    n = pos.shape[0]
+    vv = hip._f32c(v.detach().reshape(n, 3), 'v')
+    out = torch.empty(n, 3, dtype=torch.float32, device=pos.device)
+    if n == 0:
+        return out
+    p = _Pass(model, z, pos, cell, batch, 1, None)
+    _chk(hip.lib().nnhip_hessian_vp(p.model_c, p.ws_c, C.byref(p.h), vv.data_ptr(), out.data_ptr(), p.st), 'nnhip_hessian_vp')
+    return out
+
+
+def replicas_for(n_atoms: int, n_dirs: int) -> int:
+    """R of the replica scheme: as many copies of the batch as the atom budget allows, at most one per direction."""
+    if n_atoms <= 0 or n_dirs <= 1:
+        return 1
+    return max(1, min(n_dirs, REPLICA_ATOM_BUDGET // n_atoms))
+
+
+def hessian_blocks(model, z, pos, cell, batch, replicas: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Packed per-molecule Hessians: (blocks fp32 [sum_b 9 n_b^2], blk_ptr int64 [B]); block b = blocks[blk_ptr[b]:][:9 n_b^2]
+    viewed as [n_b, 3, n_b, 3].  `replicas`: R of the replica scheme (None: replicas_for)."""
+    _validate(model, pos)
+    n_mol = cell.shape[0]
+    counts = torch.bincount(batch.long().reshape(-1), minlength=n_mol).cpu() if pos.shape[0] else torch.zeros(n_mol, dtype=torch.long)
+    sizes = 9 * counts * counts
+    blk_ptr = torch.cumsum(sizes, 0) - sizes
+    total = int(sizes.sum())
+    blocks = torch.empty(total, dtype=torch.float32, device=pos.device)
+    blk_dev = blk_ptr.to(pos.device)
+    n_dirs = 3 * int(counts.max()) if n_mol else 0
+    if total == 0:
+        return blocks, blk_dev
+    r = replicas_for(pos.shape[0], n_dirs) if replicas is None else max(1, min(int(replicas), n_dirs))
+    p = _Pass(model, z, pos, cell, batch, r, blk_dev)
+    _chk(hip.lib().nnhip_hessian_blocks(p.model_c, p.ws_c, C.byref(p.h), n_dirs, blocks.data_ptr(), p.st), 'nnhip_hessian_blocks')
+    return blocks, blk_dev
+
+
+def blocks_to_dense(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor, n_atoms: int) -> torch.Tensor:
+    """The reference's layout: dense [N,3,N,3], zero between molecules."""
+    H = torch.zeros(n_atoms, 3, n_atoms, 3, dtype=blocks.dtype, device=blocks.device)
+    counts = torch.bincount(batch.long().reshape(-1), minlength=blk_ptr.numel()).tolist()
+    ptr = blk_ptr.tolist()
+    s = 0
+    for b, n in enumerate(counts):
+        if n:
+            H[s:s + n, :, s:s + n, :] = blocks[ptr[b]:ptr[b] + 9 * n * n].view(n, 3, n, 3)
+        s += n
+    return H
+
+
+def hessian(model, z, pos, cell, batch, blocks: bool = False, replicas: Optional[int] = None):
+    """blocks=False: dense [N,3,N,3] fp32 (the reference's HessianOutput layout); blocks=True: (blocks, blk_ptr)."""
+    blk, ptr = hessian_blocks(model, z, pos, cell, batch, replicas)
+    if blocks:
+        return blk, ptr
+    return blocks_to_dense(blk, ptr, batch, pos.shape[0])

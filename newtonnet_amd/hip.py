@@ -101,6 +101,12 @@ class TrainWs(C.Structure):
     _fields_ = _train_ws_fields()
 
 
+class HvpWs(C.Structure):
+    """nnhip_hvp_ws: the extra buffers of the Hessian-vector products (newtonnet_amd/hessian.py fills it)."""
+    _fields_ = [(n, C.c_void_p) for n in ('dg_x', 'dg_u', 'dg_d', 'v', 'hv', 'zeros_b', 'blk_ptr')] + \
+               [('n_rep', C.c_int32), ('n_mol0', C.c_int32)]
+
+
 MODE_FWD, MODE_BWD, MODE_TAN, MODE_TAN2 = 0, 1, 2, 3
 LOSS_MODES = {'mse': 0, 'mae': 1, 'huber': 2}          # newtonnet/train/loss.py:53-103
 WG_PLAIN, WG_ACT, WG_TDACT = 0, 1, 2
@@ -227,6 +233,9 @@ def lib():
     L.nnhip_direct_force_bwd_work_floats.restype = sz
     L.nnhip_direct_force_bwd.argtypes = [vp] * 7 + [i32, i32] + [vp] * 8
     L.nnhip_train_ws_bytes.restype = sz
+    L.nnhip_hvp_ws_bytes.restype = sz
+    L.nnhip_hessian_vp.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), C.POINTER(HvpWs), vp, vp, vp]
+    L.nnhip_hessian_blocks.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), C.POINTER(HvpWs), i32, vp, vp]
     L.nnhip_weight_image_bytes.restype = sz
     L.nnhip_weight_images.argtypes = [vp, vp, i32, vp]
     L.nnhip_mse_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -237,7 +246,7 @@ def lib():
     for fn in STAGE_SYMBOLS:
         if fn not in ('nnhip_filter_table_bytes', 'nnhip_wgrad_slab_bytes', 'nnhip_species_scratch_bytes',
                       'nnhip_colsum_scratch_bytes', 'nnhip_clip_adam_scratch_bytes', 'nnhip_train_ws_bytes',
-                      'nnhip_weight_image_bytes', 'nnhip_direct_force_bwd_work_floats'):
+                      'nnhip_weight_image_bytes', 'nnhip_direct_force_bwd_work_floats', 'nnhip_hvp_ws_bytes'):
             getattr(L, fn).restype = C.c_int
     for fn in ('nnhip_graph_count', 'nnhip_graph_fill', 'nnhip_edge_embed', 'nnhip_workspace_layout',
                'nnhip_energy_forces', 'nnhip_timers_enable', 'nnhip_timers_read', 'nnhip_linear128', 'nnhip_segment_sum', 'nnhip_gather_rows', 'nnhip_graph_count_cells',
@@ -258,7 +267,8 @@ STAGE_SYMBOLS = ('nnhip_embed', 'nnhip_filter_table_bytes', 'nnhip_filter_tables
                  'nnhip_wgrad_batch', 'nnhip_colsum_batch', 'nnhip_colsum_scratch_bytes', 'nnhip_mse_loss_grad', 'nnhip_loss_grad',
                  'nnhip_clip_adam', 'nnhip_clip_adam_dev', 'nnhip_clip_adam_scratch_bytes', 'nnhip_train_values', 'nnhip_train_grads',
                  'nnhip_train_ws_bytes', 'nnhip_weight_image_bytes', 'nnhip_weight_images', 'nnhip_train_grads_seeded',
-                 'nnhip_direct_force_bwd', 'nnhip_direct_force_bwd_work_floats')
+                 'nnhip_direct_force_bwd', 'nnhip_direct_force_bwd_work_floats', 'nnhip_hvp_ws_bytes', 'nnhip_hessian_vp',
+                 'nnhip_hessian_blocks')
 
 EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_graph_count', 'nnhip_graph_fill', 'nnhip_edge_embed',
                     'nnhip_workspace_bytes', 'nnhip_workspace_layout', 'nnhip_energy_forces', 'nnhip_timers_enable',

@@ -719,6 +719,22 @@ class NewtonNet(nn.Module):
         return lock
 
     # ------------------------------------------------------------------------------------------
+    def hessian(self, z, pos, cell, batch, blocks: bool = False):
+        """Analytic Hessian of the energy with respect to the positions, cell held fixed -- what the reference's HessianOutput
+        returns (output.py:134-152), here a method rather than an output head (get_output_by_string('hessian') keeps raising).
+        blocks=False: dense [N,3,N,3] fp32, zero between molecules (the reference's layout); blocks=True: (blocks, blk_ptr), the
+        packed per-molecule blocks [n_b,3,n_b,3] at blocks[blk_ptr[b]:] -- the form for large batches.  Eval mode only; needs the
+        'energy' head; uses the current parameters (newtonnet_amd/hessian.py, csrc/hessian.hip)."""
+        from newtonnet_amd import hessian as _h
+        with torch.no_grad():
+            return _h.hessian(self, z, pos, cell, batch, blocks=blocks)
+
+    def hessian_vector_product(self, z, pos, cell, batch, v):
+        """H v [N,3] fp32 for a position direction v [N,3] (one tangent-over-reverse pass; see hessian())."""
+        from newtonnet_amd import hessian as _h
+        with torch.no_grad():
+            return _h.hessian_vector_product(self, z, pos, cell, batch, v)
+
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated
         (trainer.py:301-313): newtonnet_amd/train_fused.py, no torch autograd graph inside the step."""

@@ -57,8 +57,11 @@ class TrainWorkspace:
     The edge count of real batches changes every step: the workspace is sized for a capacity and the kernels get the step's
     own counts (the pair-level problems of the weight-gradient table carry M = -1 = "this launch's pair count")."""
 
-    def __init__(self, model, N: int, E: int, B: int, device):
+    def __init__(self, model, N: int, E: int, B: int, device, wgrad: bool = True):
+        """wgrad=False: the buffers of sweeps 1-4 only -- no gradient outputs, no weight-gradient / column-sum tables
+        (n_probs = n_sums = 0), no direct_force head state: what the Hessian-vector products (newtonnet_amd/hessian.py) run on."""
         L = len(model.interaction_layers)
+        self.wgrad = wgrad
         P = E // 2
         self.N, self.E, self.B, self.L, self.P = N, E, B, L, P      # E, P: capacities
         self.busy = False
@@ -124,6 +127,19 @@ class TrainWorkspace:
         # ONE flat buffer, the per-parameter gradients are views into it: the backward hands autograd views of a single copy,
         # and a data-parallel all-reduce moves the flat tensor as it is
         self.params = trainable_parameters(model)
+        if not wgrad:
+            self.sp_scratch = None
+            self.has_ln = model.interaction_layers[0].layer_norm is not None
+            if self.has_ln:
+                self.ln_xhat, self.ln_dxhat, self.ln_gy = per_layer(N, F), per_layer(N, F), per_layer(N, F)
+                self.ln_row_w, self.ln_row_b = per_layer(N, F), per_layer(N, F)
+                self.ln_rstd, self.ln_drstd = per_layer(max(N, 1)), per_layer(max(N, 1))
+            self.dfh_idx = None
+            self.n_probs = self.n_sums = 0
+            self.chunks = 1
+            self.prob_dev = self.sum_dev = self.cs_scratch = self.slabs = self.g_head4_b = None
+            self._c_view(model, None)
+            return
         self.flat_grad = torch.zeros(sum(p.numel() for p in self.params), dtype=torch.float32, device=device)
         self.grads, off = [], 0
         for p in self.params:
@@ -283,11 +299,12 @@ class TrainWorkspace:
                 setattr(c, name, ptr(v))
         c.probs, c.sums = ptr(self.prob_dev), ptr(self.sum_dev)
         c.n_probs, c.chunks, c.n_sums = self.n_probs, self.chunks, self.n_sums
-        sc = model.scalers[list(model.output_properties).index('energy')]
-        c.g_embedding = ptr(G(model.embedding_layers.node_embedding.weight))
-        c.g_scale = ptr(G(sc.scale.weight)) if sc.scale is not None else None
-        c.g_shift = ptr(G(sc.shift.weight)) if sc.shift is not None else None
-        c.g_head4_b = ptr(self.g_head4_b)
+        if G is not None:
+            sc = model.scalers[list(model.output_properties).index('energy')]
+            c.g_embedding = ptr(G(model.embedding_layers.node_embedding.weight))
+            c.g_scale = ptr(G(sc.scale.weight)) if sc.scale is not None else None
+            c.g_shift = ptr(G(sc.shift.weight)) if sc.shift is not None else None
+            c.g_head4_b = ptr(self.g_head4_b)
         self.model_c, self.model_key = None, None
 
 
