@@ -786,6 +786,37 @@ int nnhip_hessian_blocks(const nnhip_model* model, const nnhip_train_ws* train_w
                          float* blocks, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Batched normal-mode analysis on the packed Hessian blocks (csrc/eig.hip): what a user of HessianOutput does next with
+ * numpy / LAPACK on the host, one molecule at a time.  One workgroup per molecule, ONE launch per batch, everything in LDS:
+ *   A = (H + H^T)/2 mass-weighted, A[ia][jb] = H[ia][jb] / sqrt(m_i m_j)   (masses [N] fp32 in amu; null: unit masses)
+ *   flags & NNHIP_EIG_PROJECT: A <- P A P, P = I - sum_k d_k d_k^T over the orthonormalised translations and rotations of the
+ *     molecule about its centre of mass (fp64 Gram-Schmidt; a vector whose remainder is not above 1e-5 of its norm is dropped);
+ *     a molecule with a non-zero cell row projects the translations only.  n_proj[b] = vectors projected (6, 5, 3 or 0).
+ *   cyclic Jacobi, round-robin ordering, A and the eigenvectors in LDS in fp32, until off(A) <= 2^-24 ||A||_F or 30 sweeps:
+ *     sweeps[b] = sweeps used, status[b] bit 0 (NNHIP_EIG_STATUS_SWEEPS) = the cap was hit.
+ *   status[b] bit 1 (NNHIP_EIG_STATUS_SIZE): mol_ptr gives the molecule more atoms than mol_ptr_host did (see below); bit 2
+ *     (NNHIP_EIG_STATUS_MASS): one of its masses is not positive and finite.  Such a molecule is not computed: its evals / modes keep
+ *     what the caller put there.
+ *   evals [3 N]: ascending per molecule, packed at 3 mol_ptr[b].  modes (may be null: eigenvalues only, bitwise the same ones):
+ *     packed like the blocks at blk_ptr[b], ROW k = mode k ([3 n_b][n_b][3]), mass-weighted coordinates, unit norm, the component
+ *     of largest magnitude (lowest index on a tie) positive.
+ * blocks / blk_ptr: as nnhip_hessian_blocks writes them.  mol_ptr: int32 [n_mol + 1] atom offsets on the device; mol_ptr_host: the
+ * same numbers on the host, which MUST be identical (a molecule that is larger by mol_ptr than by mol_ptr_host is skipped with
+ * status bit 1, never computed in too little LDS) -- the dimension bound is checked from them BEFORE any launch (NNHIP_E_UNSUPPORTED, the message names
+ * the bound and the molecule) and the launch's LDS is sized by the largest molecule.  pos [N][3] / cell [n_mol][3][3] are read with
+ * NNHIP_EIG_PROJECT only.  A molecule of 0 atoms writes nothing; no float atomics, fixed summation order (bitwise repeatable).
+ *   nnhip_eig_max_dim: the largest 3 n_b served (126: 42 atoms).
+ * ------------------------------------------------------------------------ */
+#define NNHIP_EIG_PROJECT 1
+#define NNHIP_EIG_STATUS_SWEEPS 1
+#define NNHIP_EIG_STATUS_SIZE 2
+#define NNHIP_EIG_STATUS_MASS 4
+int nnhip_eig_max_dim(void);
+int nnhip_eig_blocks(const float* blocks, const int64_t* blk_ptr, const int32_t* mol_ptr, const int32_t* mol_ptr_host, int32_t n_mol,
+                     const float* pos, const float* cell, const float* masses, int32_t flags, float* evals, float* modes,
+                     int32_t* n_proj, int32_t* sweeps, int32_t* status, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

@@ -101,9 +101,12 @@ def replicas_for(n_atoms: int, n_dirs: int) -> int:
     return max(1, min(n_dirs, REPLICA_ATOM_BUDGET // n_atoms))
 
 
-def hessian_blocks(model, z, pos, cell, batch, replicas: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Packed per-molecule Hessians: (blocks fp32 [sum_b 9 n_b^2], blk_ptr int64 [B]); block b = blocks[blk_ptr[b]:][:9 n_b^2]
-    viewed as [n_b, 3, n_b, 3].  `replicas`: R of the replica scheme (None: replicas_for)."""
+def hessian_blocks_counts(model, z, pos, cell, batch,
+                          replicas: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Packed per-molecule Hessians plus the atom counts: (blocks fp32 [sum_b 9 n_b^2], blk_ptr int64 [B] on the device, counts
+    int64 [B] on the CPU); block b = blocks[blk_ptr[b]:][:9 n_b^2] viewed as [n_b, 3, n_b, 3].  `replicas`: R of the replica
+    scheme (None: replicas_for).  The counts are what this function brings to the host for blk_ptr anyway; a consumer of the
+    blocks (newtonnet_amd/vibrations.py) takes them from here for its own offsets and size checks instead of copying again."""
     _validate(model, pos)
     n_mol = cell.shape[0]
     counts = torch.bincount(batch.long().reshape(-1), minlength=n_mol).cpu() if pos.shape[0] else torch.zeros(n_mol, dtype=torch.long)
@@ -114,11 +117,17 @@ def hessian_blocks(model, z, pos, cell, batch, replicas: Optional[int] = None) -
     blk_dev = blk_ptr.to(pos.device)
     n_dirs = 3 * int(counts.max()) if n_mol else 0
     if total == 0:
-        return blocks, blk_dev
+        return blocks, blk_dev, counts
     r = replicas_for(pos.shape[0], n_dirs) if replicas is None else max(1, min(int(replicas), n_dirs))
     p = _Pass(model, z, pos, cell, batch, r, blk_dev)
     _chk(hip.lib().nnhip_hessian_blocks(p.model_c, p.ws_c, C.byref(p.h), n_dirs, blocks.data_ptr(), p.st), 'nnhip_hessian_blocks')
-    return blocks, blk_dev
+    return blocks, blk_dev, counts
+
+
+def hessian_blocks(model, z, pos, cell, batch, replicas: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Packed per-molecule Hessians: (blocks fp32 [sum_b 9 n_b^2], blk_ptr int64 [B]); block b = blocks[blk_ptr[b]:][:9 n_b^2]
+    viewed as [n_b, 3, n_b, 3].  `replicas`: R of the replica scheme (None: replicas_for)."""
+    return hessian_blocks_counts(model, z, pos, cell, batch, replicas)[:2]
 
 
 def blocks_to_dense(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor, n_atoms: int) -> torch.Tensor:

@@ -236,6 +236,9 @@ def lib():
     L.nnhip_hvp_ws_bytes.restype = sz
     L.nnhip_hessian_vp.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), C.POINTER(HvpWs), vp, vp, vp]
     L.nnhip_hessian_blocks.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), C.POINTER(HvpWs), i32, vp, vp]
+    L.nnhip_eig_max_dim.restype = C.c_int
+    L.nnhip_eig_blocks.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.nnhip_eig_blocks.restype = C.c_int
     L.nnhip_weight_image_bytes.restype = sz
     L.nnhip_weight_images.argtypes = [vp, vp, i32, vp]
     L.nnhip_mse_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -281,7 +284,8 @@ EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_
                     'nnhip_step_layout_of', 'nnhip_forward_dev', 'nnhip_graph_small_dev', 'nnhip_graph_small_max_atoms',
                     'nnhip_energy_forces_pp', 'nnhip_graph_count_pairs_z', 'nnhip_prepare_check_counter', 'nnhip_graph_mol_dev',
                     'nnhip_edge_index_from_csr', 'nnhip_config', 'nnhip_weight_images_bf16', 'nnhip_bf16_mlp_launches',
-                    'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute')
+                    'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute', 'nnhip_eig_blocks',
+                    'nnhip_eig_max_dim')
 
 
 def _check(rc: int, what: str):
