@@ -793,7 +793,8 @@ int nnhip_hessian_blocks(const nnhip_model* model, const nnhip_train_ws* train_w
  *     molecule about its centre of mass (fp64 Gram-Schmidt; a vector whose remainder is not above 1e-5 of its norm is dropped);
  *     a molecule with a non-zero cell row projects the translations only.  n_proj[b] = vectors projected (6, 5, 3 or 0).
  *   cyclic Jacobi, round-robin ordering, A and the eigenvectors in LDS in fp32, until off(A) <= 2^-24 ||A||_F or 30 sweeps:
- *     sweeps[b] = sweeps used, status[b] bit 0 (NNHIP_EIG_STATUS_SWEEPS) = the cap was hit.
+ *     sweeps[b] = sweeps used, status[b] bit 0 (NNHIP_EIG_STATUS_SWEEPS) = the cap was hit (a block with a
+ *     NaN or an Inf never counts as converged: it runs to the cap and says so).
  *   status[b] bit 1 (NNHIP_EIG_STATUS_SIZE): mol_ptr gives the molecule more atoms than mol_ptr_host did (see below); bit 2
  *     (NNHIP_EIG_STATUS_MASS): one of its masses is not positive and finite.  Such a molecule is not computed: its evals / modes keep
  *     what the caller put there.

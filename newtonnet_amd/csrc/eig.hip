@@ -279,7 +279,8 @@ eig_kernel(EigArgs g) {
     }
     off = block_sum(off, red);
     diag = block_sum(diag, red);
-    converged = off <= eps2 * (off + diag);
+    // (an Inf entry makes both sides +inf: without the second test it would pass as converged; a NaN fails the first)
+    converged = off <= eps2 * (off + diag) && off + diag <= 1.7976931348623157e308;
     if (converged || n_sweeps == EIG_MAX_SWEEPS) break;
     for (int s = 0; s < Mp - 1; ++s) {
       if (t < P) {

@@ -78,7 +78,8 @@ class NormalModes:
     modes              fp32 [sum 9 n_b^2] or None: ROW k = mode k in mass-weighted coordinates, unit norm, largest component positive
     ptr, blk_ptr       int64 [B+1], [B]
     n_projected        int32 [B]  translation / rotation vectors projected out (6, 5, 3 or 0)
-    sweeps, status     int32 [B]  Jacobi sweeps used; status bit 0 = the sweep cap was hit, bit 2 = a mass of the molecule is not
+    sweeps, status     int32 [B]  Jacobi sweeps used; status bit 0 = the sweep cap was hit (always for a block
+                                  that holds a NaN or an Inf), bit 2 = a mass of the molecule is not
                                   positive and finite (the molecule is not computed: its outputs are zero)
     n_imaginary        int64 [B]  eigenvalues below -tol_zero max_k |lambda_k|
     zero_point_energy  fp32 [B]   eV: sum of hbar omega / 2 over the modes with lambda > tol_zero max_k |lambda_k|

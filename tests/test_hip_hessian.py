@@ -48,6 +48,18 @@ def check_blocks(H, H_ref, batch):
     assert n == H.shape[0]
 
 
+def block_errors(H, H_ref, batch):
+    """{m: (max |dH|, mean |dH|, max |H_ref|)} per molecule, for printing next to check_blocks"""
+    H, H_ref = H.detach().cpu().double(), H_ref.double()
+    b = batch.cpu()
+    out = {}
+    for m in torch.unique(b).tolist():
+        idx = (b == m).nonzero().reshape(-1)
+        d = (H[idx][:, :, idx] - H_ref[idx][:, :, idx]).abs()
+        out[m] = (d.max().item(), d.mean().item(), H_ref[idx][:, :, idx].abs().max().item())
+    return out
+
+
 def mol_subset(z, pos, cell, batch, mols):
     keep = torch.isin(batch, torch.tensor(mols))
     remap = {m: k for k, m in enumerate(mols)}

@@ -53,7 +53,8 @@ def molecules(batch):
     b = batch.cpu()
     for m in range(int(b.max()) + 1):
         idx = (b == m).nonzero().reshape(-1)
-        yield m, idx
+        if idx.numel():                                       # (an empty molecule slot owns nothing to check)
+            yield m, idx
 
 
 def check_solver(nm, blocks_host, ptr_host, z, pos, cell, batch, masses, project, label):

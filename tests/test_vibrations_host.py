@@ -107,3 +107,77 @@ def test_yardstick_drop_rule_for_linear_single_and_periodic_molecules():
     rng = np.random.default_rng(0)
     assert len(vr.tr_rot_vectors(rng.standard_normal((5, 3)), None, periodic=True)) == 3
     assert len(vr.tr_rot_vectors(rng.standard_normal((5, 3)), None)) == 6
+
+
+@pytest.mark.parametrize('M', [63, 126])
+def test_synthetic_spectra_are_deterministic_and_the_yardstick_recovers_them(M):
+    """tests/test_hip_eig_spectra.py: the generators give the same arrays on every call, their fp32 form is the fp64 one rounded
+    once, and the yardstick returns the planted eigenvalues to 1e-12 s from the fp64 matrix"""
+    a, b = vr.hard_spectra(M), vr.hard_spectra(M)
+    assert list(a) == list(b) and len(a) == 9
+    pos = np.zeros((M // 3, 3))
+    for name, (lam, A64, A32) in a.items():
+        assert np.array_equal(A64, b[name][1]) and np.array_equal(A32, A64.astype(np.float32)) and np.array_equal(A64, A64.T)
+        assert A32.shape == (M, M) and A32.dtype == np.float32 and np.all(np.isfinite(A32))
+        if lam is None:
+            continue
+        got = vr.analyse(A64, pos, None, project=False)
+        assert np.abs(got['evals'] - lam).max() <= 1e-12 * got['s'], name
+    assert np.count_nonzero(a['cluster'][0] == 1.0) == M - 3 and np.all(np.bincount(np.unique(a['triples'][0], return_inverse=True)[1]) == 3)
+    T = a['tiny_coupling'][2]
+    assert np.all(np.abs(T[0::2, 1::2].diagonal()) < 1e-29) and np.all(T[0::2, 1::2].diagonal() > 0)      # normal fp32 numbers, not 0
+    mixed = a['tiny_and_plain_coupling'][2][0::2, 1::2].diagonal()
+    assert np.all(mixed[0::2] < 1e-29) and np.all(mixed[1::2] >= 0.5)
+    rng1, rng2 = np.random.default_rng(42), np.random.default_rng(42)
+    assert np.array_equal(vr.random_symmetric(7, rng1), vr.random_symmetric(7, rng2))
+
+
+def test_drop_rule_molecules_give_the_stated_counts_in_the_yardstick():
+    """tests/test_hip_eig_spectra.py::test_projection_drop_rule: 5 for the collinear molecules (not along an axis) and for a bend of
+    1e-7 of the length, 6 for a bend of 1e-3 and for the planar molecule, 3 for all of them in a periodic cell; the remainder of
+    the dropped or kept sixth vector is a decade or more away from DROP_TOL"""
+    mols = vr.drop_rule_molecules()
+    assert [n for _, _, n in mols] == [5, 5, 6, 5, 5, 6, 6] and [p.shape[0] for _, p, _ in mols] == [3, 3, 3, 4, 4, 4, 4]
+    for name, pos, n_proj in mols:
+        assert pos.dtype == np.float32
+        m = np.array(([15.999, 1.008] * 2)[:pos.shape[0]])
+        for masses in (None, m):
+            assert len(vr.tr_rot_vectors(pos, masses)) == n_proj, name
+            assert len(vr.tr_rot_vectors(pos, masses, periodic=True)) == 3, name
+            # the same count with the rule a decade tighter and a decade looser: the cases are not on its edge
+            keep = vr.DROP_TOL
+            try:
+                for tol in (keep / 10, keep * 10):
+                    vr.DROP_TOL = tol
+                    assert len(vr.tr_rot_vectors(pos, masses)) == n_proj, (name, tol)
+            finally:
+                vr.DROP_TOL = keep
+        A = vr.gapped_symmetric(pos.shape[0], np.random.default_rng(1), m)
+        for periodic, want in ((False, n_proj), (True, 3)):
+            got = vr.analyse(A, pos, m, project=True, periodic=periodic)
+            small = np.sort(np.abs(got['evals']))
+            assert got['n_proj'] == want and np.count_nonzero(small <= 1e-12 * got['s']) == want
+            assert small[want] >= 0.1 * got['s']                     # the gap the projected-zero count of check_solver needs
+
+
+@pytest.mark.parametrize('mixed_masses', [False, True])
+def test_every_size_batch_keeps_its_spectra_away_from_zero(mixed_masses):
+    """tests/test_hip_eig_spectra.py::test_every_size_in_one_launch_and_in_any_order: deterministic, every size 1 .. 42, and after
+    the projection the smallest genuine |eigenvalue| of every molecule is at least 0.1 s -- the solver bound is 1e-4 s at most, so
+    the count of eigenvalues inside it is the count of projected vectors and nothing else"""
+    sizes, mats, poss, masses = vr.every_size_batch(mixed_masses)
+    again = vr.every_size_batch(mixed_masses)
+    assert sizes == list(range(1, 43))
+    for n, A, p, m, B in zip(sizes, mats, poss, masses, again[1]):
+        assert A.shape == (3 * n, 3 * n) and A.dtype == np.float32 and np.array_equal(A, B) and np.array_equal(A, A.T)
+        if mixed_masses:
+            assert m.dtype == np.float32 and set(np.unique(m)) <= {np.float32(1.008), np.float32(126.90)}
+        got = vr.analyse(A, p.astype(np.float32), m, project=True)
+        want = 3 if n == 1 else 5 if n == 2 else 6
+        assert got['n_proj'] == want
+        small = np.sort(np.abs(got['evals']))
+        if 3 * n > want:
+            assert vr.solver_bound(3 * n, got['s']) <= 1e-4 * got['s'] and small[want] >= 0.1 * got['s'], n
+            assert np.count_nonzero(small <= 1e-12 * got['s']) == want
+        free = vr.analyse(A, p, m, project=False)
+        assert np.abs(free['evals']).min() >= 0.1 * free['s']
