@@ -818,6 +818,26 @@ int nnhip_eig_blocks(const float* blocks, const int64_t* blk_ptr, const int32_t*
                      int32_t* n_proj, int32_t* sweeps, int32_t* status, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Normal-mode sampling on the packed spectra of nnhip_eig_blocks (csrc/sample.hip): n_samples displaced geometries per molecule
+ * drawn from its harmonic distribution at `temperature` (K), one workgroup per (molecule, tile of 32 samples), the mode matrix in LDS.
+ *   modes / evals / blk_ptr / mol_ptr / mol_ptr_host / masses: as nnhip_eig_blocks writes / takes them (masses null: unit masses).
+ *   thr [n_mol]: mode k of molecule b is LIVE iff evals > thr[b]; every other mode (projected, zero, imaginary) gets amplitude 0.
+ *     n_skipped [n_mol] (int32): modes with evals < -thr[b] (-1: mol_ptr gives the molecule more atoms than mol_ptr_host did; it is
+ *     not computed).
+ *   classical (quantum = 0): sigma_k^2 = k_B T / lambda_k;  quantum: sigma_k^2 = (eps / 2 lambda) coth(eps / 2 k_B T), eps = hbar omega
+ *     (T = 0: the ground state, eps / 2 lambda);  k_B = 8.617333262e-5 eV / K.
+ *   xi: standard-normal draws, fp32, S x [3 n_b] per molecule at 3 S mol_ptr[b] (sample-major).  q = sigma xi ->
+ *     amplitudes (same layout; may be null),  pos_out (same layout, as [n_b][3] per sample) = pos_i + sum_k q_k L[k][i] / sqrt(m_i),
+ *     energy [n_mol x S] = 1/2 sum_k lambda_k q_k^2 (eV).  The samples of molecule b are molecules b S .. b S + S - 1 of the new batch.
+ * The dimension bound is nnhip_eig_max_dim, checked from mol_ptr_host BEFORE any launch (NNHIP_E_UNSUPPORTED).  No float atomics, a
+ * fixed summation order over k: bitwise repeatable, and a sample does not depend on n_samples or on its tile.
+ * ------------------------------------------------------------------------ */
+int nnhip_mode_sample(const float* modes, const float* evals, const int64_t* blk_ptr, const int32_t* mol_ptr,
+                      const int32_t* mol_ptr_host, int32_t n_mol, const float* masses, const float* pos, const float* thr,
+                      double temperature, int32_t quantum, int32_t n_samples, const float* xi, float* pos_out, float* energy,
+                      float* amplitudes, int32_t* n_skipped, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

@@ -747,6 +747,16 @@ class NewtonNet(nn.Module):
         with torch.no_grad():
             return _v.normal_modes(self, z, pos, cell, batch, masses=masses, project=project, modes=modes, tol_zero=tol_zero)
 
+    def sample_displacements(self, z, pos, cell, batch, n_samples: int, temperature: float, quantum: bool = False, masses=None,
+                             generator=None):
+        """n_samples displaced geometries per molecule drawn from the harmonic distribution around `pos` at `temperature` (K):
+        normal_modes(...) and then NormalModes.sample (csrc/sample.hip), everything on the device.  quantum=False: classical
+        normal-mode sampling; quantum=True: Wigner sampling (T = 0: the ground state).  Projected, zero and imaginary modes are not
+        displaced.  Returns a vibrations.ModeSamples whose z, pos, cell, batch go straight back into the model (molecule
+        b n_samples + s is sample s of molecule b), with harmonic_energy, n_skipped_imaginary and amplitudes."""
+        return self.normal_modes(z, pos, cell, batch, masses=masses).sample(n_samples, temperature, quantum=quantum,
+                                                                           generator=generator)
+
     def frequencies(self, z, pos, cell, batch, masses=None, project: bool = True):
         """Harmonic frequencies fp32 [3N] in cm^-1, packed per molecule and ascending, imaginary ones negative:
         normal_modes(..., modes=False).frequencies."""

@@ -146,6 +146,23 @@ class MLAseCalculator(_Base):
         modes = nm.modes.cpu().numpy().reshape(n_frames, 3 * n_atoms, n_atoms, 3)
         return (freq[0], modes[0]) if n_frames == 1 else (freq, modes)
 
+    def sample(self, atoms, n_samples: int, temperature: float, quantum: bool = False, seed=None):
+        """n_samples geometries of one structure drawn from its harmonic distribution at `temperature` (K), as an
+        [n_samples, n_atoms, 3] array in Angstrom (NewtonNet.sample_displacements: classical normal-mode sampling, or Wigner
+        sampling with quantum=True).  Masses from atoms.get_masses() when the object has it, else standard atomic weights.
+        seed: of the device generator that draws the amplitudes (None: torch's global one)."""
+        z, pos, cell, batch = self.format_data([atoms])
+        masses = None
+        if hasattr(atoms, 'get_masses'):
+            masses = torch.tensor(np.asarray(atoms.get_masses(), dtype=np.float64), dtype=torch.float32, device=pos.device)
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=pos.device)
+            gen.manual_seed(int(seed))
+        out = self.model.sample_displacements(z, pos, cell, batch, n_samples, temperature, quantum=quantum, masses=masses,
+                                              generator=gen)
+        return out.pos.cpu().numpy().reshape(int(n_samples), len(atoms), 3)
+
     # ------------------------------------------------------------------ MD-loop latency path (SURVEY 8f rank 2)
     def _calculate_md(self, atoms):
         """One structure per call, called thousands of times by an MD driver (simulate.py:21-30): keep everything that does

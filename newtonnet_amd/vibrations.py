@@ -30,6 +30,10 @@ _PLANCK = 6.62607015e-34           # J s
 WAVENUMBER_PER_SQRT_EIGENVALUE = math.sqrt(_E_CHARGE / (1e-20 * _AMU)) / (2.0 * math.pi * _C_LIGHT)
 # 0.5 hbar omega = 0.5 h c nu~:  h c = 1.239841984e-4 eV cm
 EV_PER_WAVENUMBER = _PLANCK * _C_LIGHT / _E_CHARGE
+# Boltzmann constant in eV / K: 1.380649e-23 J/K / 1.602176634e-19 J/eV = 8.617333262e-5 (both exact in the SI of 2019)
+K_BOLTZMANN = 8.617333262e-5
+# hbar omega (eV) of a mode with eigenvalue 1 eV / (A^2 amu): eps = EV_PER_SQRT_EIGENVALUE sqrt(lambda) = 0.064654 eV
+EV_PER_SQRT_EIGENVALUE = EV_PER_WAVENUMBER * WAVENUMBER_PER_SQRT_EIGENVALUE
 
 EPS32 = 2.0 ** -24
 
@@ -69,6 +73,49 @@ def max_dim() -> int:
     return int(hip.lib().nnhip_eig_max_dim())
 
 
+_STORED = object()   # sample(): "the value stored on the NormalModes"
+
+
+def _temperature(temperature) -> float:
+    T = float(temperature)
+    if not (T >= 0.0 and math.isfinite(T)):
+        raise ValueError(f'temperature: a finite value >= 0 K expected (got {temperature!r})')
+    return T
+
+
+def zero_threshold(evals: torch.Tensor, ptr: torch.Tensor, counts_dev: torch.Tensor, tol_zero: Optional[float]) -> torch.Tensor:
+    """threshold [B] below which an eigenvalue counts as zero: tol_zero max_k |lambda_k| per molecule (default tol_zero: 8 x 3 n_b x
+    2^-24, the solver's error bound).  The one rule behind n_imaginary, zero_point_energy, sample and thermochemistry."""
+    last = evals.numel() - 1
+    lo, hi = ptr[:-1].clamp(max=last), (ptr[1:] - 1).clamp(min=0)
+    scale = torch.maximum(evals[lo].abs(), evals[hi].abs()) * (counts_dev > 0)   # sorted: the extremes are at the ends
+    tol = (8.0 * EPS32) * (3 * counts_dev).float() if tol_zero is None else torch.full_like(scale, float(tol_zero))
+    return tol * scale
+
+
+class ModeSamples:
+    """Displaced geometries of NormalModes.sample, ready for model(z, pos, cell, batch): molecule b S + s is sample s of molecule b.
+
+    z                    int64 [S N] or None (the NormalModes held no z)
+    pos                  fp32 [S N, 3]
+    cell                 fp32 [B S, 3, 3]
+    batch                int64 [S N]
+    harmonic_energy      fp32 [B S]    eV: 1/2 sum_k lambda_k q_k^2 over the live modes
+    n_skipped_imaginary  int64 [B]     imaginary modes (lambda < -threshold) left undisplaced
+    amplitudes           fp32 [3 S N]  q_k per sample in mass-weighted coordinates (A sqrt(amu)), packed like the draws xi
+    """
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class Thermochemistry:
+    """U, F (eV) and S, Cv (eV / K) of NormalModes.thermochemistry: fp32 [B] each, at `temperature` (K)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 class NormalModes:
     """Spectra of a batch, packed per molecule (molecule b owns eigenvalues[ptr[b]:ptr[b+1]] and the [3 n_b, n_b, 3] rows of
     modes at blk_ptr[b]).
@@ -84,6 +131,8 @@ class NormalModes:
     n_imaginary        int64 [B]  eigenvalues below -tol_zero max_k |lambda_k|
     zero_point_energy  fp32 [B]   eV: sum of hbar omega / 2 over the modes with lambda > tol_zero max_k |lambda_k|
     masses             fp32 [N] or None (unit masses)
+    threshold          fp32 [B]   tol_zero max_k |lambda_k|: a mode is LIVE iff lambda > threshold, imaginary iff lambda < -threshold
+    pos, cell, z       the geometry the spectra belong to (z: None when eig_blocks was not given one): what sample() displaces
     """
 
     def __init__(self, **kw):
@@ -109,17 +158,144 @@ class NormalModes:
         o, n = self._offsets[b], self._counts[b]
         return m / self.masses[o:o + n].sqrt()[None, :, None]
 
+    def _live(self):
+        """(live [3N] bool, imaginary [3N] bool): the one rule n_imaginary, zero_point_energy, sample and thermochemistry share"""
+        thr = self.threshold.repeat_interleave(self.ptr[1:] - self.ptr[:-1], output_size=self.eigenvalues.numel())
+        return self.eigenvalues > thr, self.eigenvalues < -thr
+
+    def sample(self, n_samples: int, temperature: float, quantum: bool = False, generator: Optional[torch.Generator] = None,
+               xi: Optional[torch.Tensor] = None, pos=_STORED, z=_STORED, cell=_STORED) -> 'ModeSamples':
+        """n_samples displaced geometries per molecule drawn from its harmonic distribution at `temperature` (K), in one launch
+        (nnhip_mode_sample, csrc/sample.hip).  quantum=False: classical normal-mode sampling, amplitude variance k_B T / lambda per
+        live mode; quantum=True: Wigner sampling, (eps / 2 lambda) coth(eps / 2 k_B T) with eps = hbar omega (T = 0: the ground
+        state).  Modes that are not live (projected, zero, imaginary: lambda <= threshold) are not displaced; the imaginary ones
+        skipped are counted in n_skipped_imaginary.
+        xi: the standard-normal draws, fp32 on the device, S x [3 n_b] values per molecule packed at 3 S x (atom offset),
+        sample-major; None draws them with torch.randn and `generator` (a generator of the device).  pos / z / cell: other values
+        than the stored ones (same shapes).  The result is ready for model(z, pos, cell, batch): the samples of molecule b are the
+        molecules b S .. b S + S - 1, each with that molecule's cell."""
+        S = int(n_samples)
+        if S < 1 or S != n_samples:
+            raise ValueError(f'n_samples: a positive integer expected (got {n_samples!r})')
+        T = _temperature(temperature)
+        if self.modes is None:
+            raise ValueError('this result holds no modes (modes=False)')
+        pos = self.pos if pos is _STORED else pos
+        z = self.z if z is _STORED else z
+        cell = self.cell if cell is _STORED else cell
+        n_atoms, n_mol = self.eigenvalues.numel() // 3, len(self._counts)
+        dev = self.eigenvalues.device
+        if pos is None or tuple(pos.shape) != (n_atoms, 3) or cell is None or tuple(cell.shape) != (n_mol, 3, 3):
+            raise ValueError(f'pos [{n_atoms},3] and cell [{n_mol},3,3] expected')
+        if z is not None and z.numel() != n_atoms:
+            raise ValueError(f'z: {z.numel()} values for {n_atoms} atoms')
+        if xi is not None:
+            if xi.numel() != 3 * n_atoms * S or xi.dim() != 1:
+                raise ValueError(f'xi: 1-d with n_samples x 3 N = {3 * n_atoms * S} values expected (got {tuple(xi.shape)})')
+            if xi.device != dev:
+                raise ValueError(f'xi is on {xi.device}, the modes on {dev}')
+            if xi.dtype != torch.float32:
+                raise ValueError(f'xi: float32 expected (got {xi.dtype})')
+        for name, t in (('pos', pos), ('cell', cell), ('z', z)):
+            if t is not None and t.device != dev:
+                raise ValueError(f'{name} is on {t.device}, the modes on {dev}')
+        if generator is not None and xi is None and torch.device(generator.device).type != dev.type:
+            raise ValueError(f'generator is on {generator.device}, the modes on {dev}')
+        if not self.eigenvalues.is_cuda:
+            raise RuntimeError('newtonnet_amd normal modes run on an MI355X (ROCm) device only: move the inputs to "cuda"')
+        if xi is None:
+            xi = torch.randn(3 * n_atoms * S, generator=generator, device=dev, dtype=torch.float32)
+        xi = xi.contiguous()
+        pos_c = hip._f32c(pos.detach(), 'pos')
+        mol_host = torch.tensor(self._offsets + [n_atoms], dtype=torch.int32)
+        mol_dev = (self.ptr // 3).to(torch.int32)
+        new_pos = torch.empty(n_atoms * S, 3, dtype=torch.float32, device=dev)
+        amp = torch.empty(3 * n_atoms * S, dtype=torch.float32, device=dev)
+        energy = torch.zeros(n_mol * S, dtype=torch.float32, device=dev)
+        skipped = torch.zeros(n_mol, dtype=torch.int32, device=dev)
+        if n_mol:
+            rc = hip.lib().nnhip_mode_sample(hip._ptr(self.modes), hip._ptr(self.eigenvalues), hip._ptr(self.blk_ptr), hip._ptr(mol_dev),
+                                             mol_host.data_ptr(), n_mol, hip._ptr(self.masses), hip._ptr(pos_c),
+                                             hip._ptr(self.threshold), T, 1 if quantum else 0, S, hip._ptr(xi), hip._ptr(new_pos),
+                                             hip._ptr(energy), hip._ptr(amp), hip._ptr(skipped), hip._stream(dev))
+            if rc == 2:
+                raise NotImplementedError(hip.lib().nnhip_last_error().decode())
+            hip._check(rc, 'nnhip_mode_sample')
+        # the sample batch: molecule b S + s is sample s of molecule b
+        counts = (mol_dev[1:] - mol_dev[:-1]).long()
+        mol_of = torch.arange(n_mol, device=dev).repeat_interleave(S)
+        batch = torch.arange(n_mol * S, device=dev).repeat_interleave(counts[mol_of], output_size=n_atoms * S)
+        new_z = None
+        if z is not None:
+            first_new = S * mol_dev[:-1].long()[mol_of] + (torch.arange(n_mol * S, device=dev) % S) * counts[mol_of]
+            src = mol_dev[:-1].long()[mol_of][batch] + torch.arange(n_atoms * S, device=dev) - first_new[batch]
+            new_z = z.reshape(-1)[src]
+        return ModeSamples(z=new_z, pos=new_pos, cell=cell.repeat_interleave(S, dim=0), batch=batch, harmonic_energy=energy,
+                           n_skipped_imaginary=skipped.long(), amplitudes=amp, n_samples=S, temperature=T, quantum=bool(quantum))
+
+    def thermochemistry(self, temperature: float) -> 'Thermochemistry':
+        """Harmonic vibrational thermochemistry per molecule at `temperature` (K) over the live modes, with x = eps / k_B T and
+        eps = hbar omega per mode:
+            U_vib = sum eps / 2 + eps / (e^x - 1)                       eV  (the first sum is zero_point_energy)
+            S_vib = k_B sum x / (e^x - 1) - ln(1 - e^-x)                eV / K
+            F_vib = U - T S = sum eps / 2 + k_B T ln(1 - e^-x)          eV  (summed in this per-mode form)
+            C_v   = k_B sum x^2 e^-x / (1 - e^-x)^2                     eV / K
+        fp32 [B] each.  The per-mode terms are elementwise torch ops in fp64 on the packed device arrays (e^-x is as
+        ill-conditioned as x is large), rounded to fp32 and summed per molecule by the deterministic hip.segment_sum; x is capped at
+        100, where every thermal term is below the smallest fp32 number relative to eps.  T = 0 returns U = F = the zero-point
+        energy and S = C_v = 0."""
+        T = _temperature(temperature)
+        n_mol = len(self._counts)
+        zpe = self.zero_point_energy
+        if T == 0.0 or self.eigenvalues.numel() == 0:
+            zero = torch.zeros_like(zpe)
+            return Thermochemistry(U=zpe.clone(), S=zero, F=zpe.clone(), Cv=zero.clone(), temperature=T)
+        kT = K_BOLTZMANN * T
+        live, _ = self._live()
+        eps = EV_PER_SQRT_EIGENVALUE * torch.where(live, self.eigenvalues, torch.ones_like(self.eigenvalues)).double().sqrt()
+        x = (eps / kT).clamp(max=100.0)
+        em = torch.exp(-x)
+        om = -torch.expm1(-x)                     # 1 - e^-x
+        occ = em / om                             # 1 / (e^x - 1)
+        ln = torch.log(om)
+        terms = torch.stack([eps * occ, K_BOLTZMANN * (x * occ - ln), kT * ln, K_BOLTZMANN * x * x * em / (om * om)], dim=1)
+        terms = torch.where(live[:, None], terms, torch.zeros_like(terms)).float().contiguous()
+        s = hip.segment_sum(terms, self.ptr.to(torch.int32), n_mol)
+        return Thermochemistry(U=zpe + s[:, 0], S=s[:, 1].contiguous(), F=zpe + s[:, 2], Cv=s[:, 3].contiguous(), temperature=T)
+
+
+def derived_quantities(evals: torch.Tensor, ptr: torch.Tensor, batch: torch.Tensor, n_mol: int, tol_zero: Optional[float] = None):
+    """(frequencies [3N], threshold [B], n_imaginary [B], zero_point_energy [B]) of packed eigenvalues that ascend per molecule:
+    elementwise on the packed arrays + one segmented sum."""
+    dev = evals.device
+    n_atoms = evals.numel() // 3
+    counts_dev = ((ptr[1:] - ptr[:-1]) // 3).long()
+    freq = torch.sign(evals) * evals.abs().sqrt() * WAVENUMBER_PER_SQRT_EIGENVALUE
+    if n_atoms:
+        thr_mol = zero_threshold(evals, ptr, counts_dev, tol_zero)
+        thr = thr_mol[batch.long().reshape(-1)].repeat_interleave(3)
+        imag, real = evals < -thr, evals > thr
+        x = torch.stack([imag.float(), (0.5 * EV_PER_WAVENUMBER) * freq * real], dim=1).contiguous()
+        s = hip.segment_sum(x, ptr.to(torch.int32), n_mol)
+        n_imag, zpe = s[:, 0].round().long(), s[:, 1].contiguous()
+    else:
+        thr_mol = torch.zeros(n_mol, dtype=torch.float32, device=dev)
+        n_imag = torch.zeros(n_mol, dtype=torch.long, device=dev)
+        zpe = torch.zeros(n_mol, dtype=torch.float32, device=dev)
+    return freq, thr_mol, n_imag, zpe
+
 
 def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor, pos: torch.Tensor, cell: torch.Tensor,
                masses: Optional[torch.Tensor] = None, project: bool = True, modes: bool = True,
-               tol_zero: Optional[float] = None, counts: Optional[torch.Tensor] = None) -> NormalModes:
+               tol_zero: Optional[float] = None, counts: Optional[torch.Tensor] = None,
+               z: Optional[torch.Tensor] = None) -> NormalModes:
     """The solver alone on packed blocks the caller already has (layout of hessian_blocks; atoms of a molecule contiguous and
     molecules ascending in `batch`: not checked, a check would cost a copy to the host).  masses: fp32 [N] in amu, None = unit
     masses (plain eigenvalues of the symmetrised block); a molecule with a mass that is not positive and finite is not computed
     and says so in `status` (bit 2), checked on the device.
     counts: atoms per molecule as a CPU tensor if the caller has them (else one bincount is copied to the host).
     modes=False skips the eigenvectors; the eigenvalues are bitwise the same either way (the rotations of the matrix do not depend
-    on the accumulated vectors)."""
+    on the accumulated vectors).  z: atomic numbers, kept on the result for sample() (not used by the solver)."""
     dev = blocks.device
     if not blocks.is_cuda:
         raise RuntimeError('newtonnet_amd normal modes run on an MI355X (ROCm) device only: move the inputs to "cuda"')
@@ -168,25 +344,11 @@ def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor,
         if rc == 2:
             raise NotImplementedError(hip.lib().nnhip_last_error().decode())
         hip._check(rc, 'nnhip_eig_blocks')
-    # ---- derived quantities: elementwise on the packed arrays + one segmented sum ----
-    counts_dev = (mol_dev[1:] - mol_dev[:-1]).long()
-    freq = torch.sign(evals) * evals.abs().sqrt() * WAVENUMBER_PER_SQRT_EIGENVALUE
-    if n_atoms:
-        last = 3 * n_atoms - 1
-        lo, hi = ptr[:-1].clamp(max=last), (ptr[1:] - 1).clamp(min=0)
-        scale = torch.maximum(evals[lo].abs(), evals[hi].abs()) * (counts_dev > 0)   # sorted: the extremes are at the ends
-        tol = (8.0 * EPS32) * (3 * counts_dev).float() if tol_zero is None else torch.full_like(scale, float(tol_zero))
-        thr = (tol * scale)[batch.long().reshape(-1)].repeat_interleave(3)
-        imag, real = evals < -thr, evals > thr
-        x = torch.stack([imag.float(), (0.5 * EV_PER_WAVENUMBER) * freq * real], dim=1).contiguous()
-        s = hip.segment_sum(x, ptr.to(torch.int32), n_mol)
-        n_imag, zpe = s[:, 0].round().long(), s[:, 1].contiguous()
-    else:
-        n_imag = torch.zeros(n_mol, dtype=torch.long, device=dev)
-        zpe = torch.zeros(n_mol, dtype=torch.float32, device=dev)
+    freq, thr_mol, n_imag, zpe = derived_quantities(evals, ptr, batch, n_mol, tol_zero)
     return NormalModes(eigenvalues=evals, frequencies=freq, modes=vecs, ptr=ptr, blk_ptr=blk_ptr, n_projected=n_proj, sweeps=sweeps,
                        status=status, n_imaginary=n_imag, zero_point_energy=zpe, masses=m_c, _counts=cl,
-                       _offsets=mol_host[:-1].tolist(), _blk_offsets=blk_off)
+                       _offsets=mol_host[:-1].tolist(), _blk_offsets=blk_off, threshold=thr_mol, pos=pos_c, cell=cell_c,
+                       z=None if z is None else z.detach())
 
 
 def normal_modes(model, z, pos, cell, batch, masses: Optional[torch.Tensor] = None, project: bool = True, modes: bool = True,
@@ -199,4 +361,4 @@ def normal_modes(model, z, pos, cell, batch, masses: Optional[torch.Tensor] = No
     _hessian._validate(model, pos)
     m = table_masses(z) if masses is None else masses
     blocks, blk_ptr, counts = _hessian.hessian_blocks_counts(model, z, pos, cell, batch)
-    return eig_blocks(blocks, blk_ptr, batch, pos, cell, m, project=project, modes=modes, tol_zero=tol_zero, counts=counts)
+    return eig_blocks(blocks, blk_ptr, batch, pos, cell, m, project=project, modes=modes, tol_zero=tol_zero, counts=counts, z=z)
