@@ -818,6 +818,35 @@ int nnhip_eig_blocks(const float* blocks, const int64_t* blk_ptr, const int32_t*
                      int32_t* n_proj, int32_t* sweeps, int32_t* status, void* stream);
 
 /* --------------------------------------------------------------------------
+ * The same analysis above nnhip_eig_max_dim (csrc/eig_large.hip), opt-in: a two-sided BLOCK Jacobi spread over many workgroups by
+ * ordinary launches, A and the eigenvectors in the caller's workspace in fp32.  Blocks of 32 coordinates on the round-robin ordering
+ * of nnhip_eig_blocks, the order padded to a multiple of 64; per block step two launches (one workgroup per block pair diagonalises
+ * its 64 x 64 sub-problem in LDS with the cyclic Jacobi of nnhip_eig_blocks; one workgroup per 64 x 64 tile forms Qt_k T Qt_l^T and
+ * writes the tile and its mirror image, the eigenvector rows take Qt_k in the same launch), per sweep one launch that sums off(A)^2
+ * and ||A||_F^2 per molecule in fp64 and ONE read-back of the per-molecule done flags by the host (the call synchronises `stream`
+ * once per sweep: this is not the steady-state inference step).  Symmetrisation, mass-weighting, projection (flags, n_proj), the
+ * stopping rule off(A) <= 2^-24 ||A||_F, the cap of 30 sweeps (sweeps[b] counts OUTER sweeps here), the status bits, the sorting and
+ * the sign rule are those of nnhip_eig_blocks, and so are all arguments up to `status`; the outputs go to the same packed places.
+ *   select_host [n_mol] (host; null: all): nonzero = this molecule is solved here.  The outputs of an unselected molecule are not
+ *     touched, so nnhip_eig_blocks on the small molecules and this call on the others fill one set of arrays.
+ *   ws / ws_bytes: device workspace, 256-byte aligned, at least nnhip_eig_large_ws_bytes(mol_ptr_host', n', modes != null) for the
+ *     offsets mol_ptr_host' of the SELECTED molecules in their order (the size depends on their atom counts only; the offsets of
+ *     all molecules give an upper bound): about 8 Mp^2 bytes per molecule with modes, 4 Mp^2 without (NNHIP_E_WORKSPACE).
+ * Checked from mol_ptr_host BEFORE any launch, for the selected molecules: NNHIP_E_UNSUPPORTED above nnhip_eig_large_max_dim (the
+ * message names the bound and the molecule).  A selected molecule to which mol_ptr gives more atoms than mol_ptr_host did is skipped
+ * with status bit 1.  No float atomics, fixed summation orders: bitwise repeatable, the eigenvalues bitwise the same with and without
+ * modes, and a molecule's result does not depend on the rest of the batch.
+ *   nnhip_eig_large_max_dim: the largest 3 n_b served (1536: 512 atoms) -- the range the accuracy bound has been verified in and
+ *     what the one-workgroup-per-molecule prepare / converge / finish kernels are sized for (the sort scratch of 3 x 1536 words is LDS).
+ * ------------------------------------------------------------------------ */
+int nnhip_eig_large_max_dim(void);
+size_t nnhip_eig_large_ws_bytes(const int32_t* mol_ptr_host, int32_t n_mol, int32_t want_modes);
+int nnhip_eig_blocks_large(const float* blocks, const int64_t* blk_ptr, const int32_t* mol_ptr, const int32_t* mol_ptr_host,
+                           int32_t n_mol, const float* pos, const float* cell, const float* masses, int32_t flags, float* evals,
+                           float* modes, int32_t* n_proj, int32_t* sweeps, int32_t* status, const uint8_t* select_host, void* ws,
+                           size_t ws_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
  * Normal-mode sampling on the packed spectra of nnhip_eig_blocks (csrc/sample.hip): n_samples displaced geometries per molecule
  * drawn from its harmonic distribution at `temperature` (K), one workgroup per (molecule, tile of 32 samples), the mode matrix in LDS.
  *   modes / evals / blk_ptr / mol_ptr / mol_ptr_host / masses: as nnhip_eig_blocks writes / takes them (masses null: unit masses).

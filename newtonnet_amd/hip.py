@@ -239,6 +239,11 @@ def lib():
     L.nnhip_eig_max_dim.restype = C.c_int
     L.nnhip_eig_blocks.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.nnhip_eig_blocks.restype = C.c_int
+    L.nnhip_eig_large_max_dim.restype = C.c_int
+    L.nnhip_eig_large_ws_bytes.argtypes = [vp, i32, i32]
+    L.nnhip_eig_large_ws_bytes.restype = sz
+    L.nnhip_eig_blocks_large.argtypes = L.nnhip_eig_blocks.argtypes[:-1] + [vp, vp, sz, vp]
+    L.nnhip_eig_blocks_large.restype = C.c_int
     L.nnhip_mode_sample.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
     L.nnhip_mode_sample.restype = C.c_int
     L.nnhip_weight_image_bytes.restype = sz
@@ -287,7 +292,8 @@ EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_
                     'nnhip_energy_forces_pp', 'nnhip_graph_count_pairs_z', 'nnhip_prepare_check_counter', 'nnhip_graph_mol_dev',
                     'nnhip_edge_index_from_csr', 'nnhip_config', 'nnhip_weight_images_bf16', 'nnhip_bf16_mlp_launches',
                     'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute', 'nnhip_eig_blocks',
-                    'nnhip_eig_max_dim', 'nnhip_mode_sample')
+                    'nnhip_eig_max_dim', 'nnhip_mode_sample', 'nnhip_eig_large_max_dim', 'nnhip_eig_large_ws_bytes',
+                    'nnhip_eig_blocks_large')
 
 
 def _check(rc: int, what: str):

@@ -735,17 +735,23 @@ class NewtonNet(nn.Module):
         with torch.no_grad():
             return _h.hessian_vector_product(self, z, pos, cell, batch, v)
 
-    def normal_modes(self, z, pos, cell, batch, masses=None, project: bool = True, modes: bool = True, tol_zero=None):
+    def normal_modes(self, z, pos, cell, batch, masses=None, project: bool = True, modes: bool = True, tol_zero=None,
+                     solver: str = 'lds'):
         """Harmonic normal-mode analysis of every molecule of the batch: the Hessian blocks of hessian() diagonalised on the
         device, one workgroup per molecule in one launch (newtonnet_amd/vibrations.py, csrc/eig.hip) -- the step the reference
         leaves to LAPACK on the host.  Returns a vibrations.NormalModes: packed eigenvalues (eV / (A^2 amu), ascending per
         molecule), frequencies in cm^-1 (negative = imaginary), modes (row k = mode k, mass-weighted, unit norm), n_projected,
         sweeps, n_imaginary, zero_point_energy (eV).  masses: fp32 [N] amu (None: standard atomic weights of z); project:
-        remove translations / rotations (translations only for periodic molecules); modes=False: eigenvalues only.  Molecules
-        of up to vibrations.max_dim() / 3 atoms.  Eval mode only; needs the 'energy' head; uses the current parameters."""
+        remove translations / rotations (translations only for periodic molecules); modes=False: eigenvalues only.
+        solver='lds' (default): molecules of up to vibrations.max_dim() / 3 = 42 atoms, larger ones are refused; solver='auto':
+        larger molecules, up to vibrations.max_dim_large() / 3 = 512 atoms, go through the blocked solver (csrc/eig_large.hip),
+        the others exactly as before; solver='blocked': all of them do.  NormalModes.sample still stops at 42 atoms.
+        Eval mode only; needs the 'energy' head; uses the current parameters."""
         from newtonnet_amd import vibrations as _v
+        _v._check_solver(solver)
         with torch.no_grad():
-            return _v.normal_modes(self, z, pos, cell, batch, masses=masses, project=project, modes=modes, tol_zero=tol_zero)
+            return _v.normal_modes(self, z, pos, cell, batch, masses=masses, project=project, modes=modes, tol_zero=tol_zero,
+                                   solver=solver)
 
     def sample_displacements(self, z, pos, cell, batch, n_samples: int, temperature: float, quantum: bool = False, masses=None,
                              generator=None):
@@ -757,10 +763,10 @@ class NewtonNet(nn.Module):
         return self.normal_modes(z, pos, cell, batch, masses=masses).sample(n_samples, temperature, quantum=quantum,
                                                                            generator=generator)
 
-    def frequencies(self, z, pos, cell, batch, masses=None, project: bool = True):
+    def frequencies(self, z, pos, cell, batch, masses=None, project: bool = True, solver: str = 'lds'):
         """Harmonic frequencies fp32 [3N] in cm^-1, packed per molecule and ascending, imaginary ones negative:
-        normal_modes(..., modes=False).frequencies."""
-        return self.normal_modes(z, pos, cell, batch, masses=masses, project=project, modes=False).frequencies
+        normal_modes(..., modes=False).frequencies.  solver: as in normal_modes ('auto' serves molecules above 42 atoms)."""
+        return self.normal_modes(z, pos, cell, batch, masses=masses, project=project, modes=False, solver=solver).frequencies
 
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated

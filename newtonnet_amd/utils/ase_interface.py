@@ -126,11 +126,12 @@ class MLAseCalculator(_Base):
             h = blocks.to(self.dtype).cpu().numpy()
             self.results['hessian'] = h.reshape(n_frames, n_atoms, 3, n_atoms, 3).squeeze()
 
-    def vibrations(self, atoms_or_list, project: bool = True):
+    def vibrations(self, atoms_or_list, project: bool = True, solver: str = 'lds'):
         """Harmonic analysis of one structure or a list of equally sized ones (NewtonNet.normal_modes): (frequencies
         [n_frames, 3 n_atoms] in cm^-1, imaginary ones negative; modes [n_frames, 3 n_atoms, n_atoms, 3], row k = mode k in
         mass-weighted coordinates), squeezed for one frame.  Masses from atoms.get_masses() when the object has it, else
-        standard atomic weights.  A method of its own: not a property of calculate()."""
+        standard atomic weights.  solver: 'lds' (structures of up to 42 atoms), 'auto' (larger ones, up to 512 atoms, through the
+        blocked solver) or 'blocked', as in NewtonNet.normal_modes.  A method of its own: not a property of calculate()."""
         atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
         n_frames, n_atoms = len(atoms), len(atoms[0])
         if any(len(a) != n_atoms for a in atoms):
@@ -141,7 +142,7 @@ class MLAseCalculator(_Base):
         if all(hasattr(a, 'get_masses') for a in atoms):
             masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
                                   dtype=torch.float32, device=pos.device)
-        nm = self.model.normal_modes(z, pos, cell, batch, masses=masses, project=project)
+        nm = self.model.normal_modes(z, pos, cell, batch, masses=masses, project=project, solver=solver)
         freq = nm.frequencies.cpu().numpy().reshape(n_frames, 3 * n_atoms)
         modes = nm.modes.cpu().numpy().reshape(n_frames, 3 * n_atoms, n_atoms, 3)
         return (freq[0], modes[0]) if n_frames == 1 else (freq, modes)

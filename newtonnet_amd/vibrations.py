@@ -4,7 +4,8 @@ energies of a whole batch from its analytic Hessian blocks, without a host round
 The reference stops at the Hessian (HessianOutput, newtonnet/models/output.py:134-152); its users then call LAPACK per molecule
 on the host.  Here the packed blocks of newtonnet_amd.hessian.hessian_blocks stay on the device and ONE launch of
 nnhip_eig_blocks (csrc/eig.hip: one workgroup per molecule; symmetrise, mass-weight, project translations / rotations, cyclic
-Jacobi in LDS, sort) returns every spectrum.  The derived quantities below are elementwise torch ops on the packed device arrays
+Jacobi in LDS, sort) returns every spectrum of up to 126 coordinates; solver='auto' sends larger molecules (up to 1536) through
+the blocked solver nnhip_eig_blocks_large (csrc/eig_large.hip), which keeps the matrix in a workspace in HBM.  The derived quantities below are elementwise torch ops on the packed device arrays
 plus one deterministic segmented sum (hip.segment_sum); nothing is copied to the host beyond the per-molecule atom counts that
 hessian_blocks already brings there.
 
@@ -69,8 +70,23 @@ def table_masses(z: torch.Tensor) -> torch.Tensor:
 
 
 def max_dim() -> int:
-    """Largest 3 n_b the solver serves (nnhip_eig_max_dim)."""
+    """Largest 3 n_b the one-workgroup solver serves (nnhip_eig_max_dim): the bound of solver='lds' and of NormalModes.sample."""
     return int(hip.lib().nnhip_eig_max_dim())
+
+
+def max_dim_large() -> int:
+    """Largest 3 n_b the blocked solver serves (nnhip_eig_large_max_dim; solver='auto' / 'blocked').  Bounded by the range its
+    accuracy has been verified in and by the one-workgroup-per-molecule kernels around its sweeps (csrc/eig_large.hip)."""
+    return int(hip.lib().nnhip_eig_large_max_dim())
+
+
+SOLVERS = ('lds', 'auto', 'blocked')
+
+
+def _check_solver(solver) -> str:
+    if solver not in SOLVERS:
+        raise ValueError(f"solver: one of 'lds', 'auto', 'blocked' expected (got {solver!r})")
+    return solver
 
 
 _STORED = object()   # sample(): "the value stored on the NormalModes"
@@ -125,9 +141,10 @@ class NormalModes:
     modes              fp32 [sum 9 n_b^2] or None: ROW k = mode k in mass-weighted coordinates, unit norm, largest component positive
     ptr, blk_ptr       int64 [B+1], [B]
     n_projected        int32 [B]  translation / rotation vectors projected out (6, 5, 3 or 0)
-    sweeps, status     int32 [B]  Jacobi sweeps used; status bit 0 = the sweep cap was hit (always for a block
-                                  that holds a NaN or an Inf), bit 2 = a mass of the molecule is not
-                                  positive and finite (the molecule is not computed: its outputs are zero)
+    sweeps, status     int32 [B]  Jacobi sweeps used (a molecule solved by the blocked solver -- solver='auto' above max_dim(),
+                                  solver='blocked' -- counts its OUTER sweeps over the block pairs); status bit 0 = the
+                                  sweep cap was hit (always for a block that holds a NaN or an Inf), bit 2 = a mass of
+                                  the molecule is not positive and finite (the molecule is not computed: its outputs are zero)
     n_imaginary        int64 [B]  eigenvalues below -tol_zero max_k |lambda_k|
     zero_point_energy  fp32 [B]   eV: sum of hbar omega / 2 over the modes with lambda > tol_zero max_k |lambda_k|
     masses             fp32 [N] or None (unit masses)
@@ -173,7 +190,9 @@ class NormalModes:
         xi: the standard-normal draws, fp32 on the device, S x [3 n_b] values per molecule packed at 3 S x (atom offset),
         sample-major; None draws them with torch.randn and `generator` (a generator of the device).  pos / z / cell: other values
         than the stored ones (same shapes).  The result is ready for model(z, pos, cell, batch): the samples of molecule b are the
-        molecules b S .. b S + S - 1, each with that molecule's cell."""
+        molecules b S .. b S + S - 1, each with that molecule's cell.
+        A result that holds a molecule above max_dim() (126 coordinates; solver='auto' / 'blocked' produce them) raises
+        NotImplementedError: the kernel stages a molecule's mode matrix in LDS, and a tiled sampling kernel does not exist yet."""
         S = int(n_samples)
         if S < 1 or S != n_samples:
             raise ValueError(f'n_samples: a positive integer expected (got {n_samples!r})')
@@ -288,14 +307,20 @@ def derived_quantities(evals: torch.Tensor, ptr: torch.Tensor, batch: torch.Tens
 def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor, pos: torch.Tensor, cell: torch.Tensor,
                masses: Optional[torch.Tensor] = None, project: bool = True, modes: bool = True,
                tol_zero: Optional[float] = None, counts: Optional[torch.Tensor] = None,
-               z: Optional[torch.Tensor] = None) -> NormalModes:
+               z: Optional[torch.Tensor] = None, solver: str = 'lds') -> NormalModes:
     """The solver alone on packed blocks the caller already has (layout of hessian_blocks; atoms of a molecule contiguous and
     molecules ascending in `batch`: not checked, a check would cost a copy to the host).  masses: fp32 [N] in amu, None = unit
     masses (plain eigenvalues of the symmetrised block); a molecule with a mass that is not positive and finite is not computed
     and says so in `status` (bit 2), checked on the device.
     counts: atoms per molecule as a CPU tensor if the caller has them (else one bincount is copied to the host).
     modes=False skips the eigenvectors; the eigenvalues are bitwise the same either way (the rotations of the matrix do not depend
-    on the accumulated vectors).  z: atomic numbers, kept on the result for sample() (not used by the solver)."""
+    on the accumulated vectors).  z: atomic numbers, kept on the result for sample() (not used by the solver).
+    solver: 'lds' (default) -- nnhip_eig_blocks, one workgroup per molecule, NotImplementedError above max_dim() = 126 coordinates;
+    'auto' -- the molecules within max_dim() go through nnhip_eig_blocks, bitwise as with 'lds', the others through the blocked
+    solver (nnhip_eig_blocks_large, csrc/eig_large.hip: block Jacobi over many workgroups, the matrix in a torch-owned workspace,
+    one small read-back per sweep), NotImplementedError above max_dim_large(); 'blocked' -- every molecule through the blocked
+    solver.  All land in one packed NormalModes."""
+    _check_solver(solver)
     dev = blocks.device
     if not blocks.is_cuda:
         raise RuntimeError('newtonnet_amd normal modes run on an MI355X (ROCm) device only: move the inputs to "cuda"')
@@ -323,10 +348,18 @@ def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor,
     if len(cl) != n_mol or sum(cl) != n_atoms or blocks.numel() != sum(9 * n * n for n in cl):
         raise ValueError('blocks / batch / cell disagree about the molecules')
     bound = max_dim()
-    for b, n in enumerate(cl):
-        if 3 * n > bound:
-            raise NotImplementedError(f'molecule {b} has 3 x {n} = {3 * n} coordinates, above the {bound} the batched eigensolver '
-                                      f'serves (nnhip_eig_max_dim)')
+    large = [False] * n_mol if solver == 'lds' else [n > 0 and (solver == 'blocked' or 3 * n > bound) for n in cl]
+    if solver == 'lds':
+        for b, n in enumerate(cl):
+            if 3 * n > bound:
+                raise NotImplementedError(f'molecule {b} has 3 x {n} = {3 * n} coordinates, above the {bound} the batched eigensolver '
+                                          f'serves (nnhip_eig_max_dim)')
+    elif any(large):
+        bound_large = max_dim_large()
+        for b, n in enumerate(cl):
+            if large[b] and 3 * n > bound_large:
+                raise NotImplementedError(f'molecule {b} has 3 x {n} = {3 * n} coordinates, above the {bound_large} the blocked '
+                                          f'eigensolver serves (nnhip_eig_large_max_dim)')
     mol_host = torch.zeros(n_mol + 1, dtype=torch.int32)
     mol_host[1:] = torch.cumsum(counts, 0).to(torch.int32)
     mol_dev = mol_host.to(dev)
@@ -337,13 +370,15 @@ def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor,
     evals = torch.zeros(3 * n_atoms, dtype=torch.float32, device=dev)
     vecs = torch.zeros(blocks.numel(), dtype=torch.float32, device=dev) if modes else None
     n_proj, sweeps, status = (torch.zeros(n_mol, dtype=torch.int32, device=dev) for _ in range(3))
-    if n_mol and n_atoms:
+    if n_mol and n_atoms and not any(large):
         rc = hip.lib().nnhip_eig_blocks(hip._ptr(blocks), hip._ptr(blk_ptr), hip._ptr(mol_dev), mol_host.data_ptr(), n_mol,
                                         hip._ptr(pos_c), hip._ptr(cell_c), hip._ptr(m_c), 1 if project else 0, hip._ptr(evals),
                                         hip._ptr(vecs), hip._ptr(n_proj), hip._ptr(sweeps), hip._ptr(status), hip._stream(dev))
         if rc == 2:
             raise NotImplementedError(hip.lib().nnhip_last_error().decode())
         hip._check(rc, 'nnhip_eig_blocks')
+    elif n_mol and n_atoms:
+        _solve_mixed(blocks, blk_ptr, mol_dev, mol_host, cl, large, pos_c, cell_c, m_c, project, evals, vecs, n_proj, sweeps, status)
     freq, thr_mol, n_imag, zpe = derived_quantities(evals, ptr, batch, n_mol, tol_zero)
     return NormalModes(eigenvalues=evals, frequencies=freq, modes=vecs, ptr=ptr, blk_ptr=blk_ptr, n_projected=n_proj, sweeps=sweeps,
                        status=status, n_imaginary=n_imag, zero_point_energy=zpe, masses=m_c, _counts=cl,
@@ -351,14 +386,50 @@ def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor,
                        z=None if z is None else z.detach())
 
 
+def _solve_mixed(blocks, blk_ptr, mol_dev, mol_host, cl, large, pos_c, cell_c, m_c, project, evals, vecs, n_proj, sweeps, status):
+    """solver='auto' / 'blocked': nnhip_eig_blocks on every run of consecutive molecules the one-workgroup solver serves (it takes a
+    batch as offsets into the packed arrays, so a run is the same call with the per-molecule pointers moved up), one
+    nnhip_eig_blocks_large call on the others; both write the same packed outputs."""
+    L, dev, n_mol, flags = hip.lib(), blocks.device, len(cl), 1 if project else 0
+    b = 0
+    while b < n_mol:
+        if large[b]:
+            b += 1
+            continue
+        e = b
+        while e < n_mol and not large[e]:
+            e += 1
+        if sum(cl[b:e]):
+            rc = L.nnhip_eig_blocks(hip._ptr(blocks), blk_ptr.data_ptr() + 8 * b, mol_dev.data_ptr() + 4 * b,
+                                    mol_host.data_ptr() + 4 * b, e - b, hip._ptr(pos_c), cell_c.data_ptr() + 36 * b, hip._ptr(m_c),
+                                    flags, hip._ptr(evals), hip._ptr(vecs), n_proj.data_ptr() + 4 * b, sweeps.data_ptr() + 4 * b,
+                                    status.data_ptr() + 4 * b, hip._stream(dev))
+            hip._check(rc, 'nnhip_eig_blocks')
+        b = e
+    select = torch.tensor(large, dtype=torch.uint8)
+    sel_host = torch.zeros(sum(large) + 1, dtype=torch.int32)          # the workspace is sized by the selected molecules alone
+    sel_host[1:] = torch.cumsum(torch.tensor([n for n, big in zip(cl, large) if big], dtype=torch.int32), 0)
+    ws_bytes = int(L.nnhip_eig_large_ws_bytes(sel_host.data_ptr(), sel_host.numel() - 1, 0 if vecs is None else 1))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    rc = L.nnhip_eig_blocks_large(hip._ptr(blocks), hip._ptr(blk_ptr), hip._ptr(mol_dev), mol_host.data_ptr(), n_mol, hip._ptr(pos_c),
+                                  hip._ptr(cell_c), hip._ptr(m_c), flags, hip._ptr(evals), hip._ptr(vecs), hip._ptr(n_proj),
+                                  hip._ptr(sweeps), hip._ptr(status), select.data_ptr(), hip._ptr(ws), ws_bytes, hip._stream(dev))
+    if rc == 2:
+        raise NotImplementedError(L.nnhip_last_error().decode())
+    hip._check(rc, 'nnhip_eig_blocks_large')
+
+
 def normal_modes(model, z, pos, cell, batch, masses: Optional[torch.Tensor] = None, project: bool = True, modes: bool = True,
-                 tol_zero: Optional[float] = None) -> NormalModes:
+                 tol_zero: Optional[float] = None, solver: str = 'lds') -> NormalModes:
     """Harmonic analysis of every molecule of the batch at the current parameters: Hessian blocks (hessian.hessian_blocks) and
     the batched solver, on the caller's current stream.  masses=None: standard atomic weights of z (ValueError for an element
     outside the built-in table).  project: remove translations and rotations (translations only for periodic molecules).
     tol_zero: relative threshold below which an eigenvalue counts as zero (default 8 x 3 n_b x 2^-24, the solver's error bound,
-    so projected modes are never counted as imaginary or real)."""
+    so projected modes are never counted as imaginary or real).  solver: 'lds' (molecules up to max_dim() = 126 coordinates),
+    'auto' (larger ones go through the blocked solver, up to max_dim_large()) or 'blocked': see eig_blocks."""
+    _check_solver(solver)
     _hessian._validate(model, pos)
     m = table_masses(z) if masses is None else masses
     blocks, blk_ptr, counts = _hessian.hessian_blocks_counts(model, z, pos, cell, batch)
-    return eig_blocks(blocks, blk_ptr, batch, pos, cell, m, project=project, modes=modes, tol_zero=tol_zero, counts=counts, z=z)
+    return eig_blocks(blocks, blk_ptr, batch, pos, cell, m, project=project, modes=modes, tol_zero=tol_zero, counts=counts, z=z,
+                      solver=solver)
