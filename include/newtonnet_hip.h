@@ -867,6 +867,29 @@ int nnhip_mode_sample(const float* modes, const float* evals, const int64_t* blk
                       float* amplitudes, int32_t* n_skipped, void* stream);
 
 /* --------------------------------------------------------------------------
+ * The same sampling above nnhip_eig_max_dim (csrc/sample_large.hip), opt-in: the mode matrix stays in HBM.  Two ordinary launches on
+ * `stream` -- one workgroup per (molecule, tile of 32 samples) forms the amplitudes and the harmonic energies, one per (molecule,
+ * tile of 32 samples, tile of 256 coordinates) the displacements -- no float atomics, no workspace.  The arguments up to n_skipped,
+ * the formulas and the order of every sum over k are those of nnhip_mode_sample: a molecule both entries serve gets the same bits
+ * from either, repeats are bitwise identical and a sample does not depend on n_samples, its tile or the rest of the batch.
+ * Differences from nnhip_mode_sample:
+ *   min_dim: the call serves the molecules with 3 n_b >= min_dim (decided from mol_ptr on the device; a molecule without atoms is
+ *     never served).  No output of any other molecule is touched, so nnhip_mode_sample on the small molecules and this call with
+ *     min_dim = nnhip_eig_max_dim() + 1 fill one set of arrays.  min_dim <= 1: every molecule.
+ *   amplitudes is REQUIRED (the displacement kernel reads it): null gives NNHIP_E_INVALID.
+ *   The bound is nnhip_mode_sample_large_max_dim (= nnhip_eig_large_max_dim: 1536, 512 atoms), checked from mol_ptr_host BEFORE any
+ *     launch for the molecules min_dim selects: NNHIP_E_UNSUPPORTED, the message names the bound and the molecule.  A served
+ *     molecule to which mol_ptr gives more coordinates than the largest served one of mol_ptr_host is not computed: n_skipped = -1.
+ * Every other check is that of nnhip_mode_sample (decreasing mol_ptr_host, negative counts, a temperature that is not finite and
+ * >= 0, more than 65535 x 32 samples).
+ * ------------------------------------------------------------------------ */
+int nnhip_mode_sample_large_max_dim(void);
+int nnhip_mode_sample_large(const float* modes, const float* evals, const int64_t* blk_ptr, const int32_t* mol_ptr,
+                            const int32_t* mol_ptr_host, int32_t n_mol, const float* masses, const float* pos, const float* thr,
+                            double temperature, int32_t quantum, int32_t n_samples, const float* xi, float* pos_out, float* energy,
+                            float* amplitudes, int32_t* n_skipped, int32_t min_dim, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

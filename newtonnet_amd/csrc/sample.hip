@@ -21,13 +21,8 @@
 //
 // Layout of the sample batch: the samples of molecule b are the molecules b S .. b S + S - 1, so xi, amplitudes and pos_out hold
 // S x [3 n_b] values per molecule at 3 S mol_ptr[b], sample-major.
-#include <cmath>
-
-#include "common.h"
-
-#define SMP_THREADS 256
-#define SMP_TILE 32            // samples per workgroup: q of the tile takes 32 x 126 x 4 = 16 128 bytes at the bound
-#define SMP_MAX_TILES 65535    // grid.y
+// The tile sizes, the constants and the per-mode rule of step 1 live in sample_common.h, shared with sample_large.hip.
+#include "sample_common.h"   // SMP_TILE = 32 samples per workgroup: q of the tile takes 32 x 126 x 4 = 16 128 bytes at the bound
 
 namespace {
 
@@ -82,22 +77,7 @@ sample_kernel(SampleArgs g) {
   }
   int imag = 0;
   if (t < M) {           // M <= 126 < SMP_THREADS: one mode per thread
-    const float l = g.evals[3 * (size_t)a0 + t];
-    const float thr = g.thr[b];
-    const bool live = l > thr;
-    imag = l < -thr ? 1 : 0;
-    float var = 0.f;
-    if (live) {
-      if (g.quantum) {
-        const float eps = g.hbar_unit * sqrtf(l);
-        const float coth = g.kT > 0.f ? 1.f + 2.f / expm1f(eps / g.kT) : 1.f;
-        var = eps / (2.f * l) * coth;
-      } else {
-        var = g.kT / l;
-      }
-    }
-    sig[t] = sqrtf(var);
-    lam[t] = live ? l : 0.f;
+    imag = smp_mode_rule(g.evals[3 * (size_t)a0 + t], g.thr[b], g.kT, g.hbar_unit, g.quantum, &sig[t], &lam[t]);
   }
   const int n_imag = __syncthreads_count(imag);   // (also the barrier behind the staging)
   if (t == 0 && blockIdx.y == 0) g.n_skipped[b] = n_imag;
@@ -179,11 +159,8 @@ extern "C" int nnhip_mode_sample(const float* modes, const float* evals, const i
   g.energy = energy;
   g.amplitudes = amplitudes;
   g.n_skipped = n_skipped;
-  g.kT = (float)(8.617333262e-5 * temperature);   // k_B in eV / K (CODATA 2018, exact in the SI of 2019)
-  // hbar sqrt(e / (1e-20 amu)) / e: eps in eV of a mode with lambda = 1 eV / (A^2 amu) -- EV_PER_WAVENUMBER x WAVENUMBER_PER_SQRT_EIGENVALUE
-  // of newtonnet_amd/vibrations.py (0.064654 eV)
-  g.hbar_unit = (float)(6.62607015e-34 / (2.0 * 3.14159265358979323846 * 1.602176634e-19) *
-                        std::sqrt(1.602176634e-19 / (1e-20 * 1.66053906660e-27)));
+  g.kT = smp_kT(temperature);
+  g.hbar_unit = smp_hbar_unit();
   g.quantum = quantum ? 1 : 0;
   g.n_samples = n_samples;
   g.m_max = m_max;

@@ -246,6 +246,9 @@ def lib():
     L.nnhip_eig_blocks_large.restype = C.c_int
     L.nnhip_mode_sample.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
     L.nnhip_mode_sample.restype = C.c_int
+    L.nnhip_mode_sample_large_max_dim.restype = C.c_int
+    L.nnhip_mode_sample_large.argtypes = L.nnhip_mode_sample.argtypes[:-1] + [i32, vp]
+    L.nnhip_mode_sample_large.restype = C.c_int
     L.nnhip_weight_image_bytes.restype = sz
     L.nnhip_weight_images.argtypes = [vp, vp, i32, vp]
     L.nnhip_mse_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -293,7 +296,7 @@ EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_
                     'nnhip_edge_index_from_csr', 'nnhip_config', 'nnhip_weight_images_bf16', 'nnhip_bf16_mlp_launches',
                     'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute', 'nnhip_eig_blocks',
                     'nnhip_eig_max_dim', 'nnhip_mode_sample', 'nnhip_eig_large_max_dim', 'nnhip_eig_large_ws_bytes',
-                    'nnhip_eig_blocks_large')
+                    'nnhip_eig_blocks_large', 'nnhip_mode_sample_large_max_dim', 'nnhip_mode_sample_large')
 
 
 def _check(rc: int, what: str):

@@ -745,7 +745,8 @@ class NewtonNet(nn.Module):
         remove translations / rotations (translations only for periodic molecules); modes=False: eigenvalues only.
         solver='lds' (default): molecules of up to vibrations.max_dim() / 3 = 42 atoms, larger ones are refused; solver='auto':
         larger molecules, up to vibrations.max_dim_large() / 3 = 512 atoms, go through the blocked solver (csrc/eig_large.hip),
-        the others exactly as before; solver='blocked': all of them do.  NormalModes.sample still stops at 42 atoms.
+        the others exactly as before; solver='blocked': all of them do.  NormalModes.sample serves such a result with kernel='auto' /
+        'tiled' (csrc/sample_large.hip); its default kernel='lds' stops at 42 atoms.
         Eval mode only; needs the 'energy' head; uses the current parameters."""
         from newtonnet_amd import vibrations as _v
         _v._check_solver(solver)
@@ -754,14 +755,19 @@ class NewtonNet(nn.Module):
                                    solver=solver)
 
     def sample_displacements(self, z, pos, cell, batch, n_samples: int, temperature: float, quantum: bool = False, masses=None,
-                             generator=None):
+                             generator=None, solver: str = 'lds'):
         """n_samples displaced geometries per molecule drawn from the harmonic distribution around `pos` at `temperature` (K):
         normal_modes(...) and then NormalModes.sample (csrc/sample.hip), everything on the device.  quantum=False: classical
         normal-mode sampling; quantum=True: Wigner sampling (T = 0: the ground state).  Projected, zero and imaginary modes are not
         displaced.  Returns a vibrations.ModeSamples whose z, pos, cell, batch go straight back into the model (molecule
-        b n_samples + s is sample s of molecule b), with harmonic_energy, n_skipped_imaginary and amplitudes."""
-        return self.normal_modes(z, pos, cell, batch, masses=masses).sample(n_samples, temperature, quantum=quantum,
-                                                                           generator=generator)
+        b n_samples + s is sample s of molecule b), with harmonic_energy, n_skipped_imaginary and amplitudes.
+        solver: as in normal_modes, and the sampling kernel follows it -- 'lds' (default): molecules of up to 42 atoms, larger ones
+        are refused; 'auto': larger ones, up to 512 atoms, go through the blocked solver and the tiled sampling kernel
+        (csrc/sample_large.hip), the others exactly as before; 'blocked': all of them do."""
+        from newtonnet_amd import vibrations as _v
+        _v._check_solver(solver)
+        nm = self.normal_modes(z, pos, cell, batch, masses=masses, solver=solver)
+        return nm.sample(n_samples, temperature, quantum=quantum, generator=generator, kernel=_v.KERNEL_OF_SOLVER[solver])
 
     def frequencies(self, z, pos, cell, batch, masses=None, project: bool = True, solver: str = 'lds'):
         """Harmonic frequencies fp32 [3N] in cm^-1, packed per molecule and ascending, imaginary ones negative:

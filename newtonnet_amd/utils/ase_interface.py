@@ -147,11 +147,15 @@ class MLAseCalculator(_Base):
         modes = nm.modes.cpu().numpy().reshape(n_frames, 3 * n_atoms, n_atoms, 3)
         return (freq[0], modes[0]) if n_frames == 1 else (freq, modes)
 
-    def sample(self, atoms, n_samples: int, temperature: float, quantum: bool = False, seed=None):
+    def sample(self, atoms, n_samples: int, temperature: float, quantum: bool = False, seed=None, solver: str = 'lds'):
         """n_samples geometries of one structure drawn from its harmonic distribution at `temperature` (K), as an
         [n_samples, n_atoms, 3] array in Angstrom (NewtonNet.sample_displacements: classical normal-mode sampling, or Wigner
         sampling with quantum=True).  Masses from atoms.get_masses() when the object has it, else standard atomic weights.
-        seed: of the device generator that draws the amplitudes (None: torch's global one)."""
+        seed: of the device generator that draws the amplitudes (None: torch's global one).  solver: 'lds' (structures of up to 42
+        atoms), 'auto' (larger ones, up to 512 atoms, through the blocked solver and the tiled sampling kernel) or 'blocked', as in
+        NewtonNet.sample_displacements."""
+        from newtonnet_amd import vibrations as _v
+        _v._check_solver(solver)
         z, pos, cell, batch = self.format_data([atoms])
         masses = None
         if hasattr(atoms, 'get_masses'):
@@ -161,7 +165,7 @@ class MLAseCalculator(_Base):
             gen = torch.Generator(device=pos.device)
             gen.manual_seed(int(seed))
         out = self.model.sample_displacements(z, pos, cell, batch, n_samples, temperature, quantum=quantum, masses=masses,
-                                              generator=gen)
+                                              generator=gen, solver=solver)
         return out.pos.cpu().numpy().reshape(int(n_samples), len(atoms), 3)
 
     # ------------------------------------------------------------------ MD-loop latency path

@@ -70,7 +70,8 @@ def table_masses(z: torch.Tensor) -> torch.Tensor:
 
 
 def max_dim() -> int:
-    """Largest 3 n_b the one-workgroup solver serves (nnhip_eig_max_dim): the bound of solver='lds' and of NormalModes.sample."""
+    """Largest 3 n_b the one-workgroup solver serves (nnhip_eig_max_dim): the bound of solver='lds' and of
+    NormalModes.sample(kernel='lds')."""
     return int(hip.lib().nnhip_eig_max_dim())
 
 
@@ -80,13 +81,27 @@ def max_dim_large() -> int:
     return int(hip.lib().nnhip_eig_large_max_dim())
 
 
+def max_dim_sample_large() -> int:
+    """Largest 3 n_b the tiled sampling kernel serves (nnhip_mode_sample_large_max_dim; NormalModes.sample with kernel='auto' /
+    'tiled'): the bound of the blocked solver, max_dim_large()."""
+    return int(hip.lib().nnhip_mode_sample_large_max_dim())
+
+
 SOLVERS = ('lds', 'auto', 'blocked')
+SAMPLE_KERNELS = ('lds', 'auto', 'tiled')
+KERNEL_OF_SOLVER = {'lds': 'lds', 'auto': 'auto', 'blocked': 'tiled'}   # the sampling kernel that serves what the solver produced
 
 
 def _check_solver(solver) -> str:
     if solver not in SOLVERS:
         raise ValueError(f"solver: one of 'lds', 'auto', 'blocked' expected (got {solver!r})")
     return solver
+
+
+def _check_kernel(kernel) -> str:
+    if kernel not in SAMPLE_KERNELS:
+        raise ValueError(f"kernel: one of 'lds', 'auto', 'tiled' expected (got {kernel!r})")
+    return kernel
 
 
 _STORED = object()   # sample(): "the value stored on the NormalModes"
@@ -181,7 +196,7 @@ class NormalModes:
         return self.eigenvalues > thr, self.eigenvalues < -thr
 
     def sample(self, n_samples: int, temperature: float, quantum: bool = False, generator: Optional[torch.Generator] = None,
-               xi: Optional[torch.Tensor] = None, pos=_STORED, z=_STORED, cell=_STORED) -> 'ModeSamples':
+               xi: Optional[torch.Tensor] = None, pos=_STORED, z=_STORED, cell=_STORED, kernel: str = 'lds') -> 'ModeSamples':
         """n_samples displaced geometries per molecule drawn from its harmonic distribution at `temperature` (K), in one launch
         (nnhip_mode_sample, csrc/sample.hip).  quantum=False: classical normal-mode sampling, amplitude variance k_B T / lambda per
         live mode; quantum=True: Wigner sampling, (eps / 2 lambda) coth(eps / 2 k_B T) with eps = hbar omega (T = 0: the ground
@@ -191,8 +206,13 @@ class NormalModes:
         sample-major; None draws them with torch.randn and `generator` (a generator of the device).  pos / z / cell: other values
         than the stored ones (same shapes).  The result is ready for model(z, pos, cell, batch): the samples of molecule b are the
         molecules b S .. b S + S - 1, each with that molecule's cell.
-        A result that holds a molecule above max_dim() (126 coordinates; solver='auto' / 'blocked' produce them) raises
-        NotImplementedError: the kernel stages a molecule's mode matrix in LDS, and a tiled sampling kernel does not exist yet."""
+        kernel: 'lds' (default) -- nnhip_mode_sample stages a molecule's mode matrix in LDS: a result that holds a molecule above
+        max_dim() (126 coordinates; solver='auto' / 'blocked' produce them) raises NotImplementedError; 'tiled' -- every molecule
+        goes through nnhip_mode_sample_large (csrc/sample_large.hip: two launches, the mode matrix streamed from HBM),
+        NotImplementedError above max_dim_sample_large() (1536 coordinates); 'auto' -- the molecules within max_dim() go through
+        nnhip_mode_sample, bitwise as with 'lds', the others through the tiled kernel.  The kernels sum in the same order, so
+        'tiled' and 'lds' agree bitwise where both serve."""
+        _check_kernel(kernel)
         S = int(n_samples)
         if S < 1 or S != n_samples:
             raise ValueError(f'n_samples: a positive integer expected (got {n_samples!r})')
@@ -232,14 +252,47 @@ class NormalModes:
         amp = torch.empty(3 * n_atoms * S, dtype=torch.float32, device=dev)
         energy = torch.zeros(n_mol * S, dtype=torch.float32, device=dev)
         skipped = torch.zeros(n_mol, dtype=torch.int32, device=dev)
-        if n_mol:
-            rc = hip.lib().nnhip_mode_sample(hip._ptr(self.modes), hip._ptr(self.eigenvalues), hip._ptr(self.blk_ptr), hip._ptr(mol_dev),
-                                             mol_host.data_ptr(), n_mol, hip._ptr(self.masses), hip._ptr(pos_c),
-                                             hip._ptr(self.threshold), T, 1 if quantum else 0, S, hip._ptr(xi), hip._ptr(new_pos),
-                                             hip._ptr(energy), hip._ptr(amp), hip._ptr(skipped), hip._stream(dev))
+        bound = max_dim()
+        large = [False] * n_mol if kernel == 'lds' else [n > 0 and (kernel == 'tiled' or 3 * n > bound) for n in self._counts]
+        if any(large):
+            bound_large = max_dim_sample_large()
+            for b, n in enumerate(self._counts):
+                if large[b] and 3 * n > bound_large:
+                    raise NotImplementedError(f'molecule {b} has 3 x {n} = {3 * n} coordinates, above the {bound_large} the tiled '
+                                              f'sampling kernel serves (nnhip_mode_sample_large_max_dim)')
+        L, stream = hip.lib(), hip._stream(dev)
+
+        def call(fn, first, count, *tail):
+            """fn on the molecules first .. first + count - 1: the per-molecule pointers moved up by `first` (`energy`, which the
+            kernels index by b S, by first x S); everything else is addressed through the absolute offsets they hold"""
+            return fn(hip._ptr(self.modes), hip._ptr(self.eigenvalues), self.blk_ptr.data_ptr() + 8 * first,
+                      mol_dev.data_ptr() + 4 * first, mol_host.data_ptr() + 4 * first, count, hip._ptr(self.masses), hip._ptr(pos_c),
+                      self.threshold.data_ptr() + 4 * first, T, 1 if quantum else 0, S, hip._ptr(xi), hip._ptr(new_pos),
+                      energy.data_ptr() + 4 * first * S, hip._ptr(amp), skipped.data_ptr() + 4 * first, *tail, stream)
+        if n_mol and not any(large):
+            rc = call(L.nnhip_mode_sample, 0, n_mol)
             if rc == 2:
-                raise NotImplementedError(hip.lib().nnhip_last_error().decode())
+                raise NotImplementedError(L.nnhip_last_error().decode())
             hip._check(rc, 'nnhip_mode_sample')
+        elif n_mol:
+            # nnhip_mode_sample on every run of consecutive molecules it serves, as _solve_mixed does for the eigensolver, and one
+            # nnhip_mode_sample_large call on the others: it picks them by their size on the device and touches nothing of the
+            # rest, so both write the same packed outputs
+            b = 0
+            while b < n_mol:
+                if large[b]:
+                    b += 1
+                    continue
+                e = b
+                while e < n_mol and not large[e]:
+                    e += 1
+                if sum(self._counts[b:e]):
+                    hip._check(call(L.nnhip_mode_sample, b, e - b), 'nnhip_mode_sample')
+                b = e
+            rc = call(L.nnhip_mode_sample_large, 0, n_mol, 0 if kernel == 'tiled' else bound + 1)
+            if rc == 2:
+                raise NotImplementedError(L.nnhip_last_error().decode())
+            hip._check(rc, 'nnhip_mode_sample_large')
         # the sample batch: molecule b S + s is sample s of molecule b
         counts = (mol_dev[1:] - mol_dev[:-1]).long()
         mol_of = torch.arange(n_mol, device=dev).repeat_interleave(S)
