@@ -390,9 +390,37 @@ struct NodeImages {
 int launch_weight_images(const float* const* src, char* const* dst, int n, hipStream_t s, int fmt = WIMG_FMT_SPLIT_F16);
 int launch_node_fwd_split(const NodeFwdArgs& a, const NodeImages& im, hipStream_t s);
 int launch_node_bwd_split(const NodeBwdArgs& a, const NodeImages& im, hipStream_t s);
+// The turn-around of the energy+force sweep in one launch (node128s.hip:node_turn_split_kernel; SiLU, every image of NodeImages):
+// the last layer's node_fwd, the head tail and the head adjoint + the last layer's update adjoint, with q, e1, e2 and g_e2 kept on chip
+struct NodeTurnArgs {
+  const float* f;      // [N][3][F] force_node of the last layer after its edge phase
+  const float* a_mid;  // [N][F]
+  float* a_out;        // [N][F] out: atom_node
+  const float *b0, *b2;            // biases of the head's first two linears
+  const float *w4, *b4;            // the head's last linear ([F], [1])
+  const float *scale, *shift;      // per-species tables (NULL = 1 / 0)
+  const int64_t* z;
+  float* atom_energy;  // [N] out
+  float* g_a;          // [N][F] out: dE/d atom_node
+  float* gf;           // [N][3][F] out
+  int N;
+};
+int launch_node_turn_split(const NodeTurnArgs& a, const NodeImages& im, hipStream_t s);
+bool node_turn_enabled();        // node128s.hip (NNHIP_NODE_TURN=0 keeps the three launches)
 int launch_mlp_wide_split(int mode, bool accum, const MlpArgs& a, hipStream_t s);      // needs a.W1_img / a.W2_img, SiLU
 int launch_mlp_wide_pair_split(int mode, const MlpPair& P, hipStream_t s);
 int launch_lin_wide_split(const float* X, int ldx, const char* img, float* Y, int ldy, int M, bool acc, hipStream_t s);
 bool split_products_enabled();   // mlp128.hip (NNHIP_MLP_SPLIT=0 turns every split-f16 kernel off)
+
+// msg_bwd_mol_kernel of layer 0 going on with the geometry adjoint + forces of its molecule (edge.hip): what force_direct_mol_kernel takes
+// besides g_x (layer 0's g_x, which the launch writes, is the head of the [L][E] array it reads)
+struct MsgBwdForceTail {
+  const float* g_u;    // [L][E][4]
+  const float* geo;
+  const int* rev;
+  int n_edges, n_layers;
+  float inv_rc;
+  float* forces;       // [N][3] out
+};
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -465,12 +465,20 @@ msg_bwd_kernel(const float* __restrict__ g_msg /*[P][F]*/, const float* __restri
 // msg_bwd for batches of small molecules: one workgroup per molecule, the molecule's m and g_a rows staged in LDS once (the
 // same idea as force_fwd_mol_kernel: the sender-row gathers m[j], g_a[j] are 1 KB of the 3.5 KB a directed edge pulls through the
 // vector memory path).  Per-row arithmetic of msg_bwd_kernel<NEED_GM, 1>.
-template <bool NEED_GM>
+// FORCE (layer 0, the last launch but one of the reverse sweep): the workgroup goes on with the geometry adjoint and the forces of its
+// molecule -- force_direct_mol_kernel's arithmetic in its order (same bits), on the g_x rows of layer 0 this workgroup has just
+// written; the staged g_d of the molecule's edges takes the place of the m rows in LDS.
+// (g_x of layer 0 is the head of the [L][E] array: the other layers' rows are read through the same pointer.)
+__device__ __forceinline__ float4 gd_of_edge(const float* __restrict__ g_x, const float* __restrict__ g_u,
+                                             const float* __restrict__ geo, int e, int n_edges, int n_layers, float inv_rc);
+static_assert((size_t)NNHIP_MOL_STAGE_MAX * (NNHIP_MOL_STAGE_MAX - 1) * sizeof(float4) <= (size_t)NNHIP_MOL_STAGE_MAX * NF * sizeof(float),
+              "g_d of a staged molecule's edges must fit in the LDS rows of m");
+template <bool NEED_GM, bool FORCE>
 __global__ void __launch_bounds__(64 * FM_WAVES)
 msg_bwd_mol_kernel(const float* __restrict__ g_msg /*[P][F]*/, const float* __restrict__ g_a, const float* __restrict__ m,
                    const int2* __restrict__ xg, const float* __restrict__ table, const int* __restrict__ mol_ptr,
                    const int* __restrict__ row_ptr, const int* __restrict__ col, const int* __restrict__ pid,
-                   float* __restrict__ g_m, float* __restrict__ g_x, int n_mol, const int* __restrict__ pair_ptr) {
+                   float* __restrict__ g_m, float* __restrict__ g_x, int n_mol, const int* __restrict__ pair_ptr, const MsgBwdForceTail ft) {
   __shared__ __attribute__((aligned(16))) float ml[NNHIP_MOL_STAGE_MAX * NF];
   __shared__ __attribute__((aligned(16))) float gl[NNHIP_MOL_STAGE_MAX * NF];
   __shared__ int s_next;
@@ -542,6 +550,43 @@ msg_bwd_mol_kernel(const float* __restrict__ g_msg /*[P][F]*/, const float* __re
     if (NEED_GM) {
       acc = add4(acc, upper_half(acc));
       if (!hi) st4(g_m + (size_t)i * NF + c4, acc);
+    }
+  }
+  if (FORCE) {
+    __syncthreads();     // (this molecule's g_x rows of layer 0 are written: same workgroup, lines nobody has read before; m rows free)
+    float4* sgd = reinterpret_cast<float4*>(ml);
+    const int E0 = row_ptr[a0];
+    if (staged) {
+      const int nE = row_ptr[a0 + n] - E0;
+      for (int u = threadIdx.x; u < nE; u += 64 * FM_WAVES)
+        sgd[u] = gd_of_edge(g_x, ft.g_u, ft.geo, E0 + u, ft.n_edges, ft.n_layers, ft.inv_rc);
+    }
+    __syncthreads();
+    const int sub = threadIdx.x & 15;
+    for (int k0 = 0; k0 < n; k0 += 4 * FM_WAVES) {
+      const int k = k0 + (threadIdx.x >> 4);
+      const int i = a0 + k;
+      float fx = 0.f, fy = 0.f, fz = 0.f;
+      if (k < n) {
+        for (int e = row_ptr[i] + sub; e < row_ptr[i + 1]; e += 16) {
+          const float4 a = staged ? sgd[e - E0] : gd_of_edge(g_x, ft.g_u, ft.geo, e, ft.n_edges, ft.n_layers, ft.inv_rc);
+          const float4 c = staged ? sgd[ft.rev[e] - E0] : gd_of_edge(g_x, ft.g_u, ft.geo, ft.rev[e], ft.n_edges, ft.n_layers, ft.inv_rc);
+          fx -= (a.x - c.x);
+          fy -= (a.y - c.y);
+          fz -= (a.z - c.z);
+        }
+      }
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) {
+        fx += __shfl_xor(fx, o, WAVE);
+        fy += __shfl_xor(fy, o, WAVE);
+        fz += __shfl_xor(fz, o, WAVE);
+      }
+      if (k < n && sub == 0) {
+        ft.forces[3 * (size_t)i] = fx;
+        ft.forces[3 * (size_t)i + 1] = fy;
+        ft.forces[3 * (size_t)i + 2] = fz;
+      }
     }
   }
 }
@@ -939,13 +984,14 @@ static bool mol_kernels_pay(int n_atoms, int n_mol) {
 }
 
 // what the launchers below decide with, for nnhip_config (pipeline.hip)
-void edge_config(int* small_atoms, int* mol_min, int* wpr /*[4]: msg_fwd, force_fwd, force_bwd, msg_bwd*/, int* mol_forms /*bits: force_fwd, msg_bwd, force_direct, head_out*/) {
+void edge_config(int* small_atoms, int* mol_min, int* wpr /*[4]: msg_fwd, force_fwd, force_bwd, msg_bwd*/, int* mol_forms /*bits: force_fwd, msg_bwd, force_direct, head_out, msg_bwd going on with the forces*/) {
   *small_atoms = getenv("NNHIP_EDGE_SMALL_ATOMS") ? atoi(getenv("NNHIP_EDGE_SMALL_ATOMS")) : EDGE_SMALL_ATOMS;
   *mol_min = getenv("NNHIP_MOL_KERNELS_MIN") ? atoi(getenv("NNHIP_MOL_KERNELS_MIN")) : 640;
   wpr[0] = EDGE_WPR_MSG_FWD, wpr[1] = EDGE_WPR_FORCE_FWD, wpr[2] = EDGE_WPR_FORCE_BWD, wpr[3] = EDGE_WPR_MSG_BWD;
   auto off = [](const char* name) { return getenv(name) && atoi(getenv(name)) == 0; };
   *mol_forms = (off("NNHIP_FORCE_FWD_MOL") ? 0 : 1) | (off("NNHIP_MSG_BWD_MOL") ? 0 : 2) | (off("NNHIP_FORCE_DIRECT_MOL") ? 0 : 4) |
-               (off("NNHIP_HEAD_OUT_MOL") ? 0 : 8);
+               (off("NNHIP_HEAD_OUT_MOL") ? 0 : 8) |
+               ((off("NNHIP_MSG_BWD_FORCE") || off("NNHIP_MSG_BWD_MOL") || off("NNHIP_FORCE_DIRECT_MOL")) ? 0 : 16);
 }
 
 int launch_msg_fwd(const float* m, const int* xg, const float* table, const int* row_ptr, const int* col,
@@ -997,18 +1043,29 @@ int launch_force_bwd(bool has_f, const float* gf, const float* phi1, const float
 
 int launch_msg_bwd(const float* g_msg, const float* g_a, const float* m, const int* xg, const float* table,
                    const int* row_ptr, const int* col, const int* pid, float* g_m, float* g_x, int n_atoms,
-                   bool need_gm, hipStream_t s, const int* pair_ptr, const int* mol_ptr, int n_mol) {
+                   bool need_gm, hipStream_t s, const int* pair_ptr, const int* mol_ptr, int n_mol, const MsgBwdForceTail* tail,
+                   bool* tail_done) {
   ScopedTimer t0(TC_EDGE, s);
   ScopedTimer t1(TC_EDGE_BWD_MSG, s);
+  if (tail_done) *tail_done = false;
   // batches of small molecules (see launch_force_fwd); NNHIP_MSG_BWD_MOL=0: never
   static const bool mol_off = getenv("NNHIP_MSG_BWD_MOL") && atoi(getenv("NNHIP_MSG_BWD_MOL")) == 0;
   if (mol_ptr && pair_ptr && mol_kernels_pay(n_atoms, n_mol) && !mol_off) {
+    const MsgBwdForceTail none = {};
+    // the geometry adjoint + forces in the same launch: layer 0 (nobody needs g_m), where force_direct_mol_kernel would run next
+    // (launch_geometry_bwd's test); NNHIP_MSG_BWD_FORCE=0: never
+    static const bool tail_off = (getenv("NNHIP_MSG_BWD_FORCE") && atoi(getenv("NNHIP_MSG_BWD_FORCE")) == 0) ||
+                                 (getenv("NNHIP_FORCE_DIRECT_MOL") && atoi(getenv("NNHIP_FORCE_DIRECT_MOL")) == 0);
     if (need_gm)
-      msg_bwd_mol_kernel<true><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr, row_ptr,
-                                                              col, pid, g_m, g_x, n_mol, pair_ptr);
-    else
-      msg_bwd_mol_kernel<false><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr, row_ptr,
-                                                               col, pid, g_m, g_x, n_mol, pair_ptr);
+      msg_bwd_mol_kernel<true, false><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr,
+                                                                     row_ptr, col, pid, g_m, g_x, n_mol, pair_ptr, none);
+    else if (tail && tail_done && !tail_off) {
+      msg_bwd_mol_kernel<false, true><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr,
+                                                                     row_ptr, col, pid, g_m, g_x, n_mol, pair_ptr, *tail);
+      *tail_done = true;
+    } else
+      msg_bwd_mol_kernel<false, false><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr,
+                                                                      row_ptr, col, pid, g_m, g_x, n_mol, pair_ptr, none);
     LAUNCH_CHECK();
     return 0;
   }
@@ -1121,6 +1178,18 @@ int launch_embed(const int64_t* z, const float* table, const float* m_table, int
   return 0;
 }
 
+static int mol_energy_sums(const float* atom_energy, const int* mol_ptr, int n_atoms, int n_mol, float* energy, hipStream_t s,
+                           bool small_molecules) {
+  // some molecule MAY be long (the host knows only the totals, unless the count pass said so: small_molecules); few molecules: cheap
+  const bool big = n_atoms > MOL_SPLIT && n_mol <= 4096 && !small_molecules;
+  mol_energy_kernel<<<cdiv(n_mol, ROWS_PER_BLOCK), 256, 0, s>>>(atom_energy, mol_ptr, n_mol, energy, big ? MOL_SPLIT : 0x7fffffff);
+  LAUNCH_CHECK();
+  if (big) {
+    mol_energy_big_kernel<<<n_mol, 1024, 0, s>>>(atom_energy, mol_ptr, n_mol, energy);
+    LAUNCH_CHECK();
+  }
+  return 0;
+}
 int launch_head_out(const float* e2, const float* w4, const float* b4, const float* scale, const float* shift,
                     const int64_t* z, const int* mol_ptr, int n_atoms, int n_mol, int act, float* atom_energy, float* g_e2,
                     float* energy, hipStream_t s, bool small_molecules) {
@@ -1133,15 +1202,14 @@ int launch_head_out(const float* e2, const float* w4, const float* b4, const flo
   }
   head_out_kernel<<<cdiv(n_atoms, ROWS_PER_BLOCK), 256, 0, s>>>(e2, w4, b4, scale, shift, z, n_atoms, act, atom_energy, g_e2);
   LAUNCH_CHECK();
-  // some molecule MAY be long (the host knows only the totals, unless the count pass said so: small_molecules); few molecules: cheap
-  const bool big = n_atoms > MOL_SPLIT && n_mol <= 4096 && !small_molecules;
-  mol_energy_kernel<<<cdiv(n_mol, ROWS_PER_BLOCK), 256, 0, s>>>(atom_energy, mol_ptr, n_mol, energy, big ? MOL_SPLIT : 0x7fffffff);
-  LAUNCH_CHECK();
-  if (big) {
-    mol_energy_big_kernel<<<n_mol, 1024, 0, s>>>(atom_energy, mol_ptr, n_mol, energy);
-    LAUNCH_CHECK();
-  }
-  return 0;
+  return mol_energy_sums(atom_energy, mol_ptr, n_atoms, n_mol, energy, s, small_molecules);
+}
+// the molecule sums alone (after node_turn_split_kernel, which writes the atom energies itself): bit for bit the sums of
+// head_out_mol_kernel too -- the same lane-strided fp64 partial sums and butterfly
+int launch_mol_energy(const float* atom_energy, const int* mol_ptr, int n_atoms, int n_mol, float* energy, hipStream_t s,
+                      bool small_molecules) {
+  ScopedTimer t0(TC_OTHER, s);
+  return mol_energy_sums(atom_energy, mol_ptr, n_atoms, n_mol, energy, s, small_molecules);
 }
 
 int launch_transposes(const float* const* src, float* const* dst, int count, hipStream_t s) {

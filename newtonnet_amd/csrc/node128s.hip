@@ -504,6 +504,138 @@ __global__ void __launch_bounds__(256, NS_WG_PER_CU_BWD) node_bwd_split_kernel(c
 #endif
 }
 
+// The turn-around of the energy+force sweep: node_fwd_split_kernel of the last layer, the head tail (edge.hip:head_out_kernel) and
+// node_bwd_split_kernel for the head adjoint + the last layer's update adjoint, on the same 32-row tile in one launch.  q_k, f_k, e1
+// stay in registers, e2 and g_e2 never leave the chip: per row 4 x [3][F] + 6 x [F] floats less traffic and one fill / drain of the
+// GEMM chain instead of three.  Every operation keeps the operand order of the kernels it replaces -- same bits:
+//   * stages 1, 2 = node_fwd_split_kernel (without the q / e1 / e2 stores);
+//   * stage 3: the e2 tile goes through LDS as fp32 so that a wave owns a row with lane l on features 2 l, 2 l + 1 -- the lane
+//     mapping, fmaf order and wave_sum of head_out_kernel; g_e2 = (sc w4) act'(e2) is elementwise and is formed in the GEMM layout;
+//   * stages 4, 5 = node_bwd_split_kernel (acc_ga = 0, G_f = NULL) with q_k, f_k from registers.
+#define NT_PITCH 132   // floats per row of the fp32 e2 tile (128 + 4 pad; 32 rows fit in the two f16 planes)
+static_assert(32 * NT_PITCH * 4 <= 2 * NS_PLANE, "the fp32 e2 tile must fit in the f16 planes of the LDS tile");
+__global__ void __launch_bounds__(256, NS_WG_PER_CU_BWD) node_turn_split_kernel(const NodeTurnArgs p, const NodeImages im) {
+  NS_TILE_SETUP()
+  WFrag wf;
+  load_wimg(wf, t, im.Wu);
+  float fk[3][16], qk[3][16], a[16];
+  {
+    float upd[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) upd[k] = 0.f;
+    sblk_load(fk[0], p.f, ((size_t)rc * 3 + 0) * NF, t);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      tile_publish(fk[c], t);
+      __syncthreads();
+      const float inv = tile_commit(fk[c], t);
+      __syncthreads();
+      if (c < 2)
+        sblk_load(fk[c + 1], p.f, ((size_t)rc * 3 + c + 1) * NF, t);
+      else
+        sblk_load(a, p.a_mid, (size_t)rc * NF, t);
+      tile_gemm_s(qk[c], t, wf, inv);
+      if (c == 2) load_wimg(wf, t, im.W0);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) upd[k] = fmaf(fk[c][k], qk[c][k], upd[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) a[k] += upd[k];
+  }
+  if (live) sblk_store(a, p.a_out, (size_t)row * NF, t);
+
+  // first two linears of the energy head
+  tile_publish(a, t);
+  __syncthreads();
+  float inv = tile_commit(a, t);
+  __syncthreads();
+  float e1[16], v[16], bv[16];
+  sblk_load(bv, p.b0, 0, t);
+  tile_gemm_s(e1, t, wf, inv);
+  load_wimg(wf, t, im.W2);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) e1[k] += bv[k];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) v[k] = silu_f(e1[k]);
+  tile_publish(v, t);
+  __syncthreads();
+  inv = tile_commit(v, t);
+  __syncthreads();
+  sblk_load(bv, p.b2, 0, t);
+  float e2[16];
+  tile_gemm_s(e2, t, wf, inv);
+  load_wimg(wf, t, im.W2T);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) e2[k] += bv[k];
+
+  // head tail: atom energies from the fp32 e2 tile, wave w on rows 8 w .. 8 w + 7
+  float* et = reinterpret_cast<float*>(lds);
+  __syncthreads();            // every wave is done reading the f16 tile
+  {
+    float4* er = reinterpret_cast<float4*>(et + t.r * NT_PITCH + t.nb * 32 + 4 * t.h);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) er[2 * q] = make_float4(e2[4 * q], e2[4 * q + 1], e2[4 * q + 2], e2[4 * q + 3]);
+  }
+  __syncthreads();
+  {
+    const int lane = threadIdx.x & 63;
+    const float2 w = ld2(p.w4 + 2 * lane);
+    for (int j = 0; j < 8; ++j) {
+      const int rr = t.nb * 8 + j;
+      const int i = blockIdx.x * 32 + rr;
+      if (i >= p.N) break;    // (wave-uniform)
+      const float2 h = *reinterpret_cast<const float2*>(et + rr * NT_PITCH + 2 * lane);
+      const float ax = silu_f(h.x), ay = silu_f(h.y);
+      const float s = wave_sum(fmaf(ax, w.x, ay * w.y));
+      const long zi = clamp_species(p.z[i]);
+      const float sc = p.scale ? p.scale[zi] : 1.0f;
+      const float sh = p.shift ? p.shift[zi] : 0.0f;
+      if (lane == 0) p.atom_energy[i] = fmaf(s + p.b4[0], sc, sh);
+    }
+  }
+  // g_e2 = sc w4 silu'(e2) in the GEMM layout
+  {
+    const float sc = p.scale ? p.scale[clamp_species(p.z[rc])] : 1.0f;
+    sblk_load(bv, p.w4, 0, t);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = sc * bv[k] * dsilu_f(e2[k]);
+  }
+
+  // head adjoint: g_e1 = (g_e2 H2) silu'(e1);  g_a = g_e1 H0
+  float ga[16];
+  tile_publish(v, t);
+  __syncthreads();            // (also: every wave is done reading the fp32 e2 tile)
+  inv = tile_commit(v, t);
+  __syncthreads();
+  tile_gemm_s(v, t, wf, inv);
+  load_wimg(wf, t, im.W0T);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) v[k] *= dsilu_f(e1[k]);
+  tile_publish(v, t);
+  __syncthreads();
+  inv = tile_commit(v, t);
+  __syncthreads();
+  tile_gemm_s(ga, t, wf, inv);
+  load_wimg(wf, t, im.WuT);
+  if (live) sblk_store(ga, p.g_a, (size_t)row * NF, t);
+
+  // adjoint of the last layer's update:  gf_k = g_a * q_k + (g_a * f_k) W_u   (dE/d force_node after the last layer is zero)
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float out[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) fk[c][k] *= ga[k];
+    tile_publish(fk[c], t);
+    __syncthreads();
+    inv = tile_commit(fk[c], t);
+    __syncthreads();
+    tile_gemm_s(out, t, wf, inv);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[k] = fmaf(ga[k], qk[c][k], out[k]);
+    if (live) sblk_store(out, p.gf, ((size_t)row * 3 + c) * NF, t);
+  }
+}
+
 // Tangent of node_fwd (training sweep 3): dq_k = df_k W_u^T;  da_out = da_mid + sum_k (df_k q_k + f_k dq_k);
 // T = da_out W0^T (tangent of hn);  Y = (T silu'(hn)) W2^T (tangent of the next m / of e2).  Images: Wu, W0, W2.
 __global__ void __launch_bounds__(256, 2) node_tan_fwd_split_kernel(const NodeTanFwdArgs p, const NodeImages im) {
@@ -670,6 +802,20 @@ int launch_node_bwd_split(const NodeBwdArgs& a, const NodeImages& im, hipStream_
   ScopedTimer t0(TC_LIN, s);
   ScopedTimer t1(TC_LIN1, s);
   node_bwd_split_kernel<<<cdiv(a.N, 32), 256, 0, s>>>(a, im);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// NNHIP_NODE_TURN=0 (read once per process): the turn-around as its three launches (node_fwd, head_out, node_bwd)
+bool node_turn_enabled() {
+  static const bool on = !(getenv("NNHIP_NODE_TURN") && atoi(getenv("NNHIP_NODE_TURN")) == 0);
+  return on;
+}
+int launch_node_turn_split(const NodeTurnArgs& a, const NodeImages& im, hipStream_t s) {
+  if (a.N <= 0) return 0;
+  ScopedTimer t0(TC_LIN, s);
+  ScopedTimer t1(TC_LIN1, s);
+  node_turn_split_kernel<<<cdiv(a.N, 32), 256, 0, s>>>(a, im);
   LAUNCH_CHECK();
   return 0;
 }

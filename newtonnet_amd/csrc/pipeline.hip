@@ -27,7 +27,8 @@ int launch_force_bwd(bool has_f, const float* gf, const float* phi1, const float
                      float* g_fin, int n_atoms, const int* xg, hipStream_t s, const int* pair_ptr = nullptr, const int* rev = nullptr);
 int launch_msg_bwd(const float* g_msg, const float* g_a, const float* m, const int* xg, const float* table,
                    const int* row_ptr, const int* col, const int* pid, float* g_m, float* g_x, int n_atoms, bool need_gm,
-                   hipStream_t s, const int* pair_ptr = nullptr, const int* mol_ptr = nullptr, int n_mol = 0);
+                   hipStream_t s, const int* pair_ptr = nullptr, const int* mol_ptr = nullptr, int n_mol = 0,
+                   const MsgBwdForceTail* tail = nullptr, bool* tail_done = nullptr);
 int launch_geometry_bwd(const float* g_x, const float* g_u, const float* geo, const float* disp, const float* pos,
                         const float* cell, const int* row_ptr, const int* col, const int* rev, const int* mol_ptr,
                         int n_atoms, int n_edges, int n_mol, int n_layers, float cutoff, float* g_d, float* forces,
@@ -41,6 +42,8 @@ int launch_embed(const int64_t* z, const float* table, const float* m_table, int
 int launch_head_out(const float* e2, const float* w4, const float* b4, const float* scale, const float* shift,
                     const int64_t* z, const int* mol_ptr, int n_atoms, int n_mol, int act, float* atom_energy, float* g_e2,
                     float* energy, hipStream_t s, bool small_molecules = false);
+int launch_mol_energy(const float* atom_energy, const int* mol_ptr, int n_atoms, int n_mol, float* energy, hipStream_t s,
+                      bool small_molecules = false);
 int launch_transposes(const float* const* src, float* const* dst, int count, hipStream_t s);
 // ---- errors ------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -75,7 +78,7 @@ extern "C" int nnhip_config(char* buf, size_t n) {
   }
   static const char* names[] = {"NNHIP_EDGE_LDS", "NNHIP_EDGE_SMALL_ATOMS", "NNHIP_EDGE_WPR", "NNHIP_FORCE_DIRECT_MOL", "NNHIP_FORCE_FWD_MOL", "NNHIP_GRAPH_MOL",
                                 "NNHIP_GRAPH_SMALL_ATOMS", "NNHIP_HEAD_OUT_MOL", "NNHIP_MLP_REGW", "NNHIP_MLP_REGW_SINGLE", "NNHIP_MLP_SPLIT",
-                                "NNHIP_MLP_WIDE_TILES", "NNHIP_MOL_KERNELS_MIN", "NNHIP_MSG_BWD_MOL",
+                                "NNHIP_MLP_WIDE_TILES", "NNHIP_MOL_KERNELS_MIN", "NNHIP_MSG_BWD_FORCE", "NNHIP_MSG_BWD_MOL", "NNHIP_NODE_TURN",
                                 "NNHIP_WGRAD_FORM", "NNHIP_WGRAD_RPC"};
   int small_atoms, mol_min, wpr[4], mol_forms;
   edge_config(&small_atoms, &mol_min, wpr, &mol_forms);
@@ -93,11 +96,14 @@ extern "C" int nnhip_config(char* buf, size_t n) {
       nnhip_graph_small_max_atoms(), (graph_mol && atoi(graph_mol) == 0) ? 0 : 1);
   put("\"edge_rows\": {\"waves_per_row\": {\"msg_fwd\": %d, \"force_fwd\": %d, \"force_bwd\": %d, \"msg_bwd\": %d}, \"four_waves_per_row_up_to_atoms\": %d}, ",
       wpr[0], wpr[1], wpr[2], wpr[3], small_atoms);
-  put("\"molecule_forms\": {\"max_atoms\": %d, \"edge_kernels_from_molecules\": %d, \"force_fwd\": %d, \"msg_bwd\": %d, \"force_direct\": %d, \"head_out\": %d}, ",
-      NNHIP_MOL_STAGE_MAX, mol_min, mol_forms & 1, (mol_forms >> 1) & 1, (mol_forms >> 2) & 1, (mol_forms >> 3) & 1);
+  put("\"molecule_forms\": {\"max_atoms\": %d, \"edge_kernels_from_molecules\": %d, \"force_fwd\": %d, \"msg_bwd\": %d, \"force_direct\": %d, \"head_out\": %d, "
+      "\"msg_bwd_with_forces\": %d}, ",
+      NNHIP_MOL_STAGE_MAX, mol_min, mol_forms & 1, (mol_forms >> 1) & 1, (mol_forms >> 2) & 1, (mol_forms >> 3) & 1, (mol_forms >> 4) & 1);
   put("\"edge_mlp\": {\"row_local_up_to_tiles\": %d, \"one_pass_adjoint\": %d, \"one_pass_forward\": %d, \"one_pass_single_adjoint\": %d, "
       "\"one_pass_single_forward\": %d}, ",
       mlp_wide_max_tiles_silu(), (forms >> 1) & 1, (forms >> 2) & 1, (forms >> 3) & 1, (forms >> 4) & 1);
+  // (the turn-around of the energy+force sweep as one launch: split-f16 products, forces wanted, no LayerNorm on the last layer)
+  put("\"node_turn_fused\": %d, ", ((forms & 1) && node_turn_enabled()) ? 1 : 0);
   put("\"radial_table_intervals\": %d, \"env\": {", FT_G);
   bool first = true;
   for (const char* nm : names) {
@@ -698,6 +704,9 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
   // the last layer writes atom_node / force_node straight into the caller's output arrays when they are given
   auto A_OUT = [&](int l) { return (l == L - 1 && atom_node_out) ? atom_node_out : P(w.pub.a_out[l]); };
   auto F_OUT = [&](int l) { return (l == L - 1 && force_node_out) ? force_node_out : P(w.pub.f_out[l]); };
+  // the turn-around of the sweep (last node_fwd, head tail, head adjoint + last update adjoint) as one launch, node128s.hip:
+  // q[L-1], e1, e2 and g_e then stay unwritten (nobody reads them on this route)
+  const bool node_turn = split_nodes && want_forces && !model->layer[L - 1].ln_w && node_turn_enabled();
   for (int l = 0; l < L; ++l) {
     const nnhip_layer_params& lp = model->layer[l];
     const bool has_f = l > 0;
@@ -729,7 +738,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
                            mol_kernels ? mol_ptr : nullptr, B));
     }
     // equiv_update + energy update + the next layer's message_nodepart: one row-local launch (node128.hip)
-    {
+    if (!(node_turn && l == L - 1)) {
       NodeFwdArgs na;
       memset(&na, 0, sizeof(na));
       na.f = F_OUT(l);
@@ -786,8 +795,37 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
     TRY(launch_mlp(MODE_FWD, false, {a_in, model->head0_w, model->head2_w, P(w.pub.e1), P(w.pub.e2), N, NF, NF, NF,
                                      model->head0_b, model->head2_b, act}, s));
   float* atom_energy = atom_energy_out ? atom_energy_out : P(w.atom_energy);
-  TRY(launch_head_out(P(w.pub.e2), model->head4_w, model->head4_b, model->scale, model->shift, z, mol_ptr, N, B,
-                      act, atom_energy, want_forces ? P(w.g_e) : nullptr, energy, s, mol_kernels));
+  if (node_turn) {
+    NodeTurnArgs nt;
+    memset(&nt, 0, sizeof(nt));
+    nt.f = F_OUT(L - 1);
+    nt.a_mid = P(w.pub.a_mid[L - 1]);
+    nt.a_out = A_OUT(L - 1);
+    nt.b0 = model->head0_b;
+    nt.b2 = model->head2_b;
+    nt.w4 = model->head4_w;
+    nt.b4 = model->head4_b;
+    nt.scale = model->scale;
+    nt.shift = model->shift;
+    nt.z = z;
+    nt.atom_energy = atom_energy;
+    nt.g_a = P(w.pub.g_a);
+    nt.gf = P(w.gf_mid);
+    nt.N = N;
+    NodeImages im;
+    memset(&im, 0, sizeof(im));
+    im.Wu = pbase + pq.img[L - 1][IMG_UPDATE];
+    im.W0 = pbase + pq.img_head[IMG_HEAD0];
+    im.W2 = pbase + pq.img_head[IMG_HEAD2];
+    im.W2T = pbase + pq.img_head[IMG_HEAD2_T];
+    im.W0T = pbase + pq.img_head[IMG_HEAD0_T];
+    im.WuT = pbase + pq.img[L - 1][IMG_UPDATE_T];
+    TRY(launch_node_turn_split(nt, im, s));
+    TRY(launch_mol_energy(atom_energy, mol_ptr, N, B, energy, s, mol_kernels));
+  } else {
+    TRY(launch_head_out(P(w.pub.e2), model->head4_w, model->head4_b, model->scale, model->shift, z, mol_ptr, N, B,
+                        act, atom_energy, want_forces ? P(w.g_e) : nullptr, energy, s, mol_kernels));
+  }
   if (!want_forces) return NNHIP_OK;
 
   // ------------------------------------------------------------------ reverse sweep
@@ -796,7 +834,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
   };
   // head adjoint (g_e1 = (g_e2 H2) * silu'(e1); g_a = g_e1 H0) + update adjoint of the last layer
   // (gf = g_a * q + (g_a * f) W_u; dE/d force_node after the last layer is zero): one row-local launch
-  {
+  if (!node_turn) {
     NodeBwdArgs nb;
     memset(&nb, 0, sizeof(nb));
     nb.g_top = P(w.g_e);
@@ -829,6 +867,11 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
   }
   float* g_fbuf[2] = {P(w.pub.g_f), P(w.g_f2)};
   int pp = 0;
+  // layer 0's molecule-resident msg_bwd may go on with the geometry adjoint + forces of its molecule (where launch_geometry_bwd
+  // would take force_direct_mol_kernel: molecule forms allowed, no virial)
+  MsgBwdForceTail ftail = {P(w.pub.g_u), geo, rev, E, L, 1.0f / model->cutoff, forces};
+  const bool ftail_ok = mol_kernels && !virial && B > 0 && (long)N <= (long)B * NNHIP_MOL_STAGE_MAX;
+  bool forces_done = false;
   for (int l = L - 1; l >= 0; --l) {
     const nnhip_layer_params& lp = model->layer[l];
     (void)lp;
@@ -861,7 +904,8 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
       }
       // message adjoint -> g_m, g_x
       TRY(launch_msg_bwd(P(w.g_msg), P(w.pub.g_a), P(w.pub.m[l]), xg, Q(pq.ftab[l]), row_ptr, col, pid, P(w.g_m),
-                         P(w.pub.g_x) + (size_t)l * E, N, l > 0, s, pair_ptr, mol_kernels ? mol_ptr : nullptr, B));
+                         P(w.pub.g_x) + (size_t)l * E, N, l > 0, s, pair_ptr, mol_kernels ? mol_ptr : nullptr, B,
+                         (l == 0 && ftail_ok) ? &ftail : nullptr, &forces_done));
     }
     // message_nodepart adjoint of this layer (g_hn = (g_m W2) * silu'(hn); g_a += g_hn W0) + update adjoint of the
     // layer below (gf = G_f + g_a * q + (g_a * f) W_u): one row-local launch.  Nothing to do below the first layer: its
@@ -899,8 +943,9 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
     }
     pp ^= 1;
   }
-  TRY(launch_geometry_bwd(P(w.pub.g_x), P(w.pub.g_u), geo, disp, pos, cell, row_ptr, col, rev, mol_ptr, N, E, B, L,
-                          model->cutoff, P(w.g_d), forces, virial, s, mol_kernels));
+  if (!forces_done)
+    TRY(launch_geometry_bwd(P(w.pub.g_x), P(w.pub.g_u), geo, disp, pos, cell, row_ptr, col, rev, mol_ptr, N, E, B, L,
+                            model->cutoff, P(w.g_d), forces, virial, s, mol_kernels));
   return NNHIP_OK;
 }
 

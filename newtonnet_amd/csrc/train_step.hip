@@ -21,7 +21,7 @@ int launch_force_bwd(bool has_f, const float* gf, const float* phi1, const float
                      const int* xg, hipStream_t s, const int* pair_ptr, const int* rev);
 int launch_msg_bwd(const float* g_msg, const float* g_a, const float* m, const int* xg, const float* table, const int* row_ptr,
                    const int* col, const int* pid, float* g_m, float* g_x, int n_atoms, bool need_gm, hipStream_t s,
-                   const int* pair_ptr, const int* mol_ptr, int n_mol);
+                   const int* pair_ptr, const int* mol_ptr, int n_mol, const MsgBwdForceTail* tail = nullptr, bool* tail_done = nullptr);
 
 #define TS_TRY(x)          \
   do {                     \

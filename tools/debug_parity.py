@@ -13,6 +13,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+# the fused turn-around keeps q of the last layer on chip: this tool reads it from the workspace, so it takes the three launches
+os.environ.setdefault('NNHIP_NODE_TURN', '0')
 
 from newtonnet_amd import hip  # noqa: E402
 from newtonnet_amd.models import NewtonNet  # noqa: E402
