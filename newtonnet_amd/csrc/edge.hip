@@ -26,6 +26,7 @@
 #include "common.h"
 
 #include "edge_common.h"
+#include "switches.h"
 
 // ---------------------------------------------------------------------------------------------
 // forward: message + invariant aggregation
@@ -924,27 +925,11 @@ __global__ void __launch_bounds__(256) transpose128_kernel(TransposeList L) {
 // host-side launchers (used by pipeline.hip)
 // ---------------------------------------------------------------------------------------------
 static inline int row_blocks(int n_atoms, int wpr) { return cdiv(n_atoms, EDGE_ROWS / wpr); }
-// Small systems (the one-molecule MD step, small training batches) are bound by the latency chain of a row, not by traffic or
-// occupancy: up to EDGE_SMALL_ATOMS rows every kernel gives a row four waves (NNHIP_EDGE_SMALL_ATOMS overrides, 0 = never).
-// Back-to-back aspirin batches, us per step with / without: 1008 atoms 389 / 404, 2016: 303 / 304, 3024: 390 / 383, 5376: 574 / 568
-// (profiles/r04_small_thresholds.txt).
-#ifndef EDGE_SMALL_ATOMS
-#define EDGE_SMALL_ATOMS 2048
-#endif
-static inline bool edge_small(int n_atoms) {
-  static const int lim = getenv("NNHIP_EDGE_SMALL_ATOMS") ? atoi(getenv("NNHIP_EDGE_SMALL_ATOMS")) : EDGE_SMALL_ATOMS;
-  return n_atoms <= lim;
-}
-// NNHIP_EDGE_WPR=1|2|4 (read once per process) forces one split for every row kernel at every size: the non-default forms stay
-// reachable for tests (tests/test_hip_parity.py::test_non_default_forms_in_child_processes) without a tooling build.
-static inline int edge_wpr_forced() {
-  static const int v = [] {
-    const char* e = getenv("NNHIP_EDGE_WPR");
-    const int w = e ? atoi(e) : 0;
-    return (w == 1 || w == 2 || w == 4) ? w : 0;
-  }();
-  return v;
-}
+// Small systems give every row four waves (switches.h: EDGE_SMALL_ATOMS, NNHIP_EDGE_SMALL_ATOMS).
+static inline bool edge_small(int n_atoms) { return n_atoms <= switches().edge_small_atoms; }
+// NNHIP_EDGE_WPR=1|2|4 forces one split for every row kernel at every size: the non-default forms stay reachable for tests
+// (tests/test_hip_parity.py::test_non_default_forms_in_child_processes) without a tooling build.
+static inline int edge_wpr_forced() { return switches().edge_wpr; }
 #define EDGE_LAUNCH_W(KERNEL_W, W_, ...) KERNEL_W<<<row_blocks(n_atoms, W_), 64 * EDGE_ROWS, edge_lds(), s>>>(__VA_ARGS__)
 #define EDGE_LAUNCH(KERNEL, WPR_, ...)                                                                          \
   do {                                                                                                          \
@@ -967,10 +952,7 @@ static inline int edge_wpr_forced() {
       EDGE_LAUNCH_W((KERNEL<FLAG, 1>), 1, __VA_ARGS__);                                                         \
   } while (0)
 // tooling: NNHIP_EDGE_LDS=<bytes> attaches unused dynamic LDS to the edge kernels to cap their occupancy
-static inline size_t edge_lds() {
-  static const size_t v = getenv("NNHIP_EDGE_LDS") ? (size_t)atol(getenv("NNHIP_EDGE_LDS")) : 0;
-  return v;
-}
+static inline size_t edge_lds() { return (size_t)switches().edge_lds; }
 
 // The molecule-resident kernels (force_fwd_mol_kernel, msg_bwd_mol_kernel: one 8-wave workgroup per molecule) need enough molecules
 // to fill the chip: same box, us per step with / without them -- 100 molecules 370 / 314, 256: 561 / 529, 384: 675 / 654,
@@ -979,19 +961,24 @@ static inline size_t edge_lds() {
 // us per step with / without -- 694 / 672, 885 / 879, 1102 / 1107, 1307 / 1311, 1492 / 1518, 1781 / 1834
 // (profiles/r04_mol_kernels_by_molecule_size.txt): from an average of 8 atoms per molecule up.
 static bool mol_kernels_pay(int n_atoms, int n_mol) {
-  static const int min_mol = getenv("NNHIP_MOL_KERNELS_MIN") ? atoi(getenv("NNHIP_MOL_KERNELS_MIN")) : 640;
-  return n_mol >= min_mol && (long)n_atoms <= (long)n_mol * NNHIP_MOL_STAGE_MAX && (long)n_atoms >= 8L * n_mol;
+  return n_mol >= switches().mol_kernels_min && (long)n_atoms <= (long)n_mol * NNHIP_MOL_STAGE_MAX && (long)n_atoms >= 8L * n_mol;
 }
+
+// The molecule forms that a switch turns off (each launcher below adds the shapes it serves); msg_bwd_mol_kernel goes on with the
+// forces only where both kernels it joins run.
+static bool force_fwd_mol_on() { return switches().force_fwd_mol != 0; }
+static bool msg_bwd_mol_on() { return switches().msg_bwd_mol != 0; }
+static bool force_direct_mol_on() { return switches().force_direct_mol != 0; }
+static bool head_out_mol_on() { return switches().head_out_mol != 0; }
+static bool msg_bwd_force_tail_on() { return switches().msg_bwd_force != 0 && msg_bwd_mol_on() && force_direct_mol_on(); }
 
 // what the launchers below decide with, for nnhip_config (pipeline.hip)
 void edge_config(int* small_atoms, int* mol_min, int* wpr /*[4]: msg_fwd, force_fwd, force_bwd, msg_bwd*/, int* mol_forms /*bits: force_fwd, msg_bwd, force_direct, head_out, msg_bwd going on with the forces*/) {
-  *small_atoms = getenv("NNHIP_EDGE_SMALL_ATOMS") ? atoi(getenv("NNHIP_EDGE_SMALL_ATOMS")) : EDGE_SMALL_ATOMS;
-  *mol_min = getenv("NNHIP_MOL_KERNELS_MIN") ? atoi(getenv("NNHIP_MOL_KERNELS_MIN")) : 640;
+  *small_atoms = switches().edge_small_atoms;
+  *mol_min = switches().mol_kernels_min;
   wpr[0] = EDGE_WPR_MSG_FWD, wpr[1] = EDGE_WPR_FORCE_FWD, wpr[2] = EDGE_WPR_FORCE_BWD, wpr[3] = EDGE_WPR_MSG_BWD;
-  auto off = [](const char* name) { return getenv(name) && atoi(getenv(name)) == 0; };
-  *mol_forms = (off("NNHIP_FORCE_FWD_MOL") ? 0 : 1) | (off("NNHIP_MSG_BWD_MOL") ? 0 : 2) | (off("NNHIP_FORCE_DIRECT_MOL") ? 0 : 4) |
-               (off("NNHIP_HEAD_OUT_MOL") ? 0 : 8) |
-               ((off("NNHIP_MSG_BWD_FORCE") || off("NNHIP_MSG_BWD_MOL") || off("NNHIP_FORCE_DIRECT_MOL")) ? 0 : 16);
+  *mol_forms = (force_fwd_mol_on() ? 1 : 0) | (msg_bwd_mol_on() ? 2 : 0) | (force_direct_mol_on() ? 4 : 0) | (head_out_mol_on() ? 8 : 0) |
+               (msg_bwd_force_tail_on() ? 16 : 0);
 }
 
 int launch_msg_fwd(const float* m, const int* xg, const float* table, const int* row_ptr, const int* col,
@@ -1009,8 +996,7 @@ int launch_force_fwd(bool has_f, const float* phi1, const float* phi2, const flo
   ScopedTimer t0(TC_EDGE, s);
   ScopedTimer t1(TC_EDGE_FWD_FORCE, s);
   // batches of small molecules (the caller passes mol_ptr only when it may: see force_fwd_mol_kernel); NNHIP_FORCE_FWD_MOL=0: never
-  static const bool mol_off = getenv("NNHIP_FORCE_FWD_MOL") && atoi(getenv("NNHIP_FORCE_FWD_MOL")) == 0;
-  if (has_f && mol_ptr && mol_kernels_pay(n_atoms, n_mol) && !mol_off) {
+  if (has_f && mol_ptr && mol_kernels_pay(n_atoms, n_mol) && force_fwd_mol_on()) {
     // (eight waves: 4 workgroups x 36 KB of LDS = the CU's 32 wave slots; 7 waves -- no idle slot in the last round of a 21-atom
     // molecule -- 0.198 against 0.159 ms per step, 16 waves 0.173: profiles/r04_force_fwd_mol_waves_ab.txt)
     force_fwd_mol_kernel<<<n_mol, 64 * FM_WAVES, 0, s>>>(phi1, phi2, geo, mol_ptr, row_ptr, col, pid, f_in, f_out, n_mol,
@@ -1031,8 +1017,7 @@ int launch_force_bwd(bool has_f, const float* gf, const float* phi1, const float
                      float* g_fin, int n_atoms, const int* xg, hipStream_t s, const int* pair_ptr, const int* rev) {
   ScopedTimer t0(TC_EDGE, s);
   ScopedTimer t1(TC_EDGE_BWD_FORCE, s);
-  static const bool owner_off = getenv("NNHIP_FORCE_BWD_OWNER_GU") && atoi(getenv("NNHIP_FORCE_BWD_OWNER_GU")) == 0;   // (A/B)
-  if (owner_off) rev = nullptr;
+  if (!switches().force_bwd_owner_gu) rev = nullptr;   // (A/B: NNHIP_FORCE_BWD_OWNER_GU=0)
   if (has_f)
     EDGE_LAUNCH_B(force_bwd_kernel, true, EDGE_WPR_FORCE_BWD, gf, phi1, phi2, geo, row_ptr, col, pid, f_in, g_h12, g_u, g_fin, n_atoms, reinterpret_cast<const int2*>(xg), pair_ptr, rev);
   else
@@ -1049,17 +1034,14 @@ int launch_msg_bwd(const float* g_msg, const float* g_a, const float* m, const i
   ScopedTimer t1(TC_EDGE_BWD_MSG, s);
   if (tail_done) *tail_done = false;
   // batches of small molecules (see launch_force_fwd); NNHIP_MSG_BWD_MOL=0: never
-  static const bool mol_off = getenv("NNHIP_MSG_BWD_MOL") && atoi(getenv("NNHIP_MSG_BWD_MOL")) == 0;
-  if (mol_ptr && pair_ptr && mol_kernels_pay(n_atoms, n_mol) && !mol_off) {
+  if (mol_ptr && pair_ptr && mol_kernels_pay(n_atoms, n_mol) && msg_bwd_mol_on()) {
     const MsgBwdForceTail none = {};
     // the geometry adjoint + forces in the same launch: layer 0 (nobody needs g_m), where force_direct_mol_kernel would run next
     // (launch_geometry_bwd's test); NNHIP_MSG_BWD_FORCE=0: never
-    static const bool tail_off = (getenv("NNHIP_MSG_BWD_FORCE") && atoi(getenv("NNHIP_MSG_BWD_FORCE")) == 0) ||
-                                 (getenv("NNHIP_FORCE_DIRECT_MOL") && atoi(getenv("NNHIP_FORCE_DIRECT_MOL")) == 0);
     if (need_gm)
       msg_bwd_mol_kernel<true, false><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr,
                                                                      row_ptr, col, pid, g_m, g_x, n_mol, pair_ptr, none);
-    else if (tail && tail_done && !tail_off) {
+    else if (tail && tail_done && msg_bwd_force_tail_on()) {
       msg_bwd_mol_kernel<false, true><<<n_mol, 64 * FM_WAVES, 0, s>>>(g_msg, g_a, m, reinterpret_cast<const int2*>(xg), table, mol_ptr,
                                                                      row_ptr, col, pid, g_m, g_x, n_mol, pair_ptr, *tail);
       *tail_done = true;
@@ -1128,8 +1110,7 @@ int launch_geometry_bwd(const float* g_x, const float* g_u, const float* geo, co
                         int n_atoms, int n_edges, int n_mol, int n_layers, float cutoff, float* g_d, float* forces,
                         float* virial, hipStream_t s, bool small_molecules) {
   ScopedTimer t0(TC_OTHER, s);
-  static const bool mol_off = getenv("NNHIP_FORCE_DIRECT_MOL") && atoi(getenv("NNHIP_FORCE_DIRECT_MOL")) == 0;
-  if (!virial && small_molecules && mol_ptr && n_mol > 0 && (long)n_atoms <= (long)n_mol * NNHIP_MOL_STAGE_MAX && !mol_off) {
+  if (!virial && small_molecules && mol_ptr && n_mol > 0 && (long)n_atoms <= (long)n_mol * NNHIP_MOL_STAGE_MAX && force_direct_mol_on()) {
     force_direct_mol_kernel<<<n_mol, 256, 0, s>>>(g_x, g_u, geo, mol_ptr, row_ptr, rev, n_edges, n_layers, 1.0f / cutoff, forces);
     LAUNCH_CHECK();
     return 0;
@@ -1194,8 +1175,7 @@ int launch_head_out(const float* e2, const float* w4, const float* b4, const flo
                     const int64_t* z, const int* mol_ptr, int n_atoms, int n_mol, int act, float* atom_energy, float* g_e2,
                     float* energy, hipStream_t s, bool small_molecules) {
   ScopedTimer t0(TC_OTHER, s);
-  static const bool mol_off = getenv("NNHIP_HEAD_OUT_MOL") && atoi(getenv("NNHIP_HEAD_OUT_MOL")) == 0;
-  if (small_molecules && n_mol > 0 && (long)n_atoms <= (long)n_mol * NNHIP_MOL_STAGE_MAX && !mol_off) {
+  if (small_molecules && n_mol > 0 && (long)n_atoms <= (long)n_mol * NNHIP_MOL_STAGE_MAX && head_out_mol_on()) {
     head_out_mol_kernel<<<n_mol, 64 * HM_WAVES, 0, s>>>(e2, w4, b4, scale, shift, z, mol_ptr, act, atom_energy, g_e2, energy);
     LAUNCH_CHECK();
     return 0;

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 // ---------------------------------------------------------------------------------------------
 // molecule extents from the (sorted) batch vector
@@ -836,12 +837,8 @@ extern "C" int nnhip_graph_small_dev(const float* pos, const float* cell, const 
 // atoms (back-to-back aspirin batches, us per step, single launch vs fourteen: 21 atoms 182 vs 206, 84: 207 vs 216, 168: 218 vs 208,
 // 336: 257 vs 231, 1008: 390 vs 255; profiles/r04_small_thresholds.txt).  NNHIP_GRAPH_SMALL_ATOMS overrides (0 = never).
 extern "C" int nnhip_graph_small_max_atoms(void) {
-  static const int lim = [] {
-    const char* v = getenv("NNHIP_GRAPH_SMALL_ATOMS");
-    const int n = v ? atoi(v) : 128;
-    return n < 0 ? 0 : (n > SG_MAX_ATOMS ? SG_MAX_ATOMS : n);
-  }();
-  return lim;
+  const int n = switches().graph_small_atoms;   // (default 128)
+  return n < 0 ? 0 : (n > SG_MAX_ATOMS ? SG_MAX_ATOMS : n);
 }
 
 // ---------------------------------------------------------------------------------------------

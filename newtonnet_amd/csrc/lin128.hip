@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "switches.h"
 
 // compile-time ablation switches for tools/bench_lin.py (all 0 in the shipped library)
 #ifndef LIN_ABLATE_NO_LOAD
@@ -191,21 +192,15 @@ __global__ void __launch_bounds__(256, 2) lin128_kernel(const LinArgs p) {
   }
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 template <int PRO, int EPI>
 static int launch_lin_t(const LinArgs& a, int groups, hipStream_t s) {
-  static const int block_cap = env_int("NNHIP_LIN_BLOCKS", 512);  // tuning knob (tools/bench_lin.py)
   // one-time kernel attribute; a function-local static is initialised exactly once even with concurrent host threads
   static const hipError_t attr_rc = hipFuncSetAttribute((const void*)lin128_kernel<PRO, EPI>,
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, LIN_LDS_BYTES);
   HIP_TRY(attr_rc);
   const int n_tiles = (a.M + 31) / 32;
   int blocks = cdiv(n_tiles, 4);
-  const int cap = block_cap / groups;  // default 512: 2 resident workgroups per CU x 256 CUs
+  const int cap = switches().lin_blocks / groups;  // NNHIP_LIN_BLOCKS, default 512: 2 resident workgroups per CU x 256 CUs
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   lin128_kernel<PRO, EPI><<<dim3(blocks, groups), 256, LIN_LDS_BYTES, s>>>(a);

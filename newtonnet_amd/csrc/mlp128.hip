@@ -27,6 +27,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "switches.h"
 
 #ifndef MLP_NT_H
 #define MLP_NT_H 1   // hidden pre-activations bypass the caches (streaming): they would only evict phi / msg
@@ -347,10 +348,7 @@ int launch_mlp_split(int mode, bool accum_last, const MlpPair& P, hipStream_t s)
 // time, and closer to fp64 than the fp32 MFMA chain below); NNHIP_MLP_SPLIT=0 keeps them on v_mfma_f32_32x32x2_f32 (tooling,
 // A/B).  The other activations of the factory run the fp32 form.
 extern "C" int nnhip_split_products(void) { return split_products_enabled() ? 1 : 0; }
-bool split_products_enabled() {
-  static const bool on = !(getenv("NNHIP_MLP_SPLIT") && atoi(getenv("NNHIP_MLP_SPLIT")) == 0);
-  return on;
-}
+bool split_products_enabled() { return switches().mlp_split != 0; }
 
 static int launch_mlp_dispatch(int mode, bool accum_last, const MlpPair& P, hipStream_t s) {
   if (split_products_enabled() && P.a[0].act == NNHIP_ACT_SILU) return launch_mlp_split(mode, accum_last, P, s);
@@ -374,15 +372,14 @@ static int launch_mlp_dispatch(int mode, bool accum_last, const MlpPair& P, hipS
   return NNHIP_E_INVALID;
 }
 
-int mlp_wide_max_tiles_silu() {   // (nnhip_config: below this many 32-row tiles the edge MLPs take the row-local form)
-  static const int env_max = getenv("NNHIP_MLP_WIDE_TILES") ? atoi(getenv("NNHIP_MLP_WIDE_TILES")) : -1;   // (read once: no getenv on a call path)
-  return env_max >= 0 ? env_max : (split_products_enabled() ? MLPS_WIDE_MAX_TILES : MLP_WIDE_MAX_TILES);
+// up to how many 32-row tiles a launch takes the row-local form (NNHIP_MLP_WIDE_TILES >= 0 overrides both thresholds)
+static int mlp_wide_max_tiles(bool split_silu) {
+  const int env_max = switches().mlp_wide_tiles;
+  return env_max >= 0 ? env_max : (split_silu ? MLPS_WIDE_MAX_TILES : MLP_WIDE_MAX_TILES);
 }
+int mlp_wide_max_tiles_silu() { return mlp_wide_max_tiles(split_products_enabled()); }   // (nnhip_config: the edge MLPs)
 static bool mlp_use_wide(const MlpArgs& a) {
-  static const int env_max = getenv("NNHIP_MLP_WIDE_TILES") ? atoi(getenv("NNHIP_MLP_WIDE_TILES")) : -1;
-  const int wide_max = env_max >= 0 ? env_max
-                                    : (split_products_enabled() && a.act == NNHIP_ACT_SILU ? MLPS_WIDE_MAX_TILES : MLP_WIDE_MAX_TILES);
-  return cdiv(a.M, 32) <= wide_max || a.b1 || a.b2;
+  return cdiv(a.M, 32) <= mlp_wide_max_tiles(split_products_enabled() && a.act == NNHIP_ACT_SILU) || a.b1 || a.b2;
 }
 
 int launch_mlp(int mode, bool accum, const MlpArgs& a, hipStream_t s) {

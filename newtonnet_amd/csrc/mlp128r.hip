@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -465,18 +466,9 @@ __global__ void __launch_bounds__(RW_THREADS, 2) mlp_regw_kernel(const MlpPair P
 // NNHIP_MLP_REGW: 1 (default) = the adjoint launches take this form (measured 106 us against 121 us per launch on the config-2
 // batch: g_msg is written once); 2 = the forward launches too (108 us against 106 us: the message rows are read once, but the
 // per-tile cost of passing activations through LDS eats the gain -- mlp128s.hip hands them over in registers); 0 = off
-static int mlp_regw_level() {
-  static const int level = [] {
-    const char* v = getenv("NNHIP_MLP_REGW");
-    return v ? atoi(v) : 1;
-  }();
-  return level;
-}
+static int mlp_regw_level() { return switches().mlp_regw; }
 // one MLP (layer 0): NNHIP_MLP_REGW_SINGLE = 0 off, 1 the adjoint, 2 the forward too (A/B timing)
-static int mlp_regw_single() {
-  static const int single = getenv("NNHIP_MLP_REGW_SINGLE") ? atoi(getenv("NNHIP_MLP_REGW_SINGLE")) : 1;
-  return single;
-}
+static int mlp_regw_single() { return switches().mlp_regw_single; }
 // what the library does with the switches above, for callers that model its traffic (bench.py); include/newtonnet_hip.h
 extern "C" int nnhip_mlp_forms(void) {
   const bool split = split_products_enabled();
@@ -491,8 +483,7 @@ bool mlp_regw_serves(int mode, const MlpPair& P) {
   if (mode == MODE_TAN || mode == MODE_TAN2) {
     // the adjoint-shaped launches of the training sweeps: one MLP (layer 0, no accumulate), or two MLPs whose outputs are summed
     // into one Y (the second accumulating); H / T / T2 / Hd / G row-major with one pitch.  NNHIP_MLP_REGW_TRAIN=0: the two-phase form
-    static const bool train_on = !(getenv("NNHIP_MLP_REGW_TRAIN") && atoi(getenv("NNHIP_MLP_REGW_TRAIN")) == 0);
-    if (level <= 0 || !train_on || P.n < 1 || P.n > 2) return false;
+    if (level <= 0 || !switches().mlp_regw_train || P.n < 1 || P.n > 2) return false;
     for (int k = 0; k < P.n; ++k) {
       const MlpArgs& a = P.a[k];
       if (!a.W1_img || !a.W2_img || a.h_frag || a.act != NNHIP_ACT_SILU || a.b1 || a.b2 || a.M_dev || a.ldh != P.a[0].ldh) return false;

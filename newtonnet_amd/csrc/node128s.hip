@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "switches.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -806,11 +807,8 @@ int launch_node_bwd_split(const NodeBwdArgs& a, const NodeImages& im, hipStream_
   return 0;
 }
 
-// NNHIP_NODE_TURN=0 (read once per process): the turn-around as its three launches (node_fwd, head_out, node_bwd)
-bool node_turn_enabled() {
-  static const bool on = !(getenv("NNHIP_NODE_TURN") && atoi(getenv("NNHIP_NODE_TURN")) == 0);
-  return on;
-}
+// NNHIP_NODE_TURN=0: the turn-around as its three launches (node_fwd, head_out, node_bwd)
+bool node_turn_enabled() { return switches().node_turn != 0; }
 int launch_node_turn_split(const NodeTurnArgs& a, const NodeImages& im, hipStream_t s) {
   if (a.N <= 0) return 0;
   ScopedTimer t0(TC_LIN, s);

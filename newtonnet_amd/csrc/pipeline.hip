@@ -10,9 +10,11 @@
 
 #include <atomic>
 #include <mutex>
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
+#include "switches.h"
 
 // ---- pieces defined in the other translation units ---------------------------------------------------
 int launch_filter_tables(const float* const* edge_w, float* const* tables, int n_layers, const float* freq, int nb,
@@ -71,19 +73,20 @@ void edge_config(int* small_atoms, int* mol_min, int* wpr, int* mol_forms);   //
 int mlp_wide_max_tiles_silu();                                                 // mlp128.hip
 extern "C" int nnhip_mlp_forms(void);
 extern "C" int nnhip_graph_small_max_atoms(void);
+// NNHIP_GRAPH_MOL=0: the deferred step never takes the per-molecule neighbor list (graph.hip:graph_mol_*_kernel)
+static bool graph_mol_on() { return switches().graph_mol != 0; }
 extern "C" int nnhip_config(char* buf, size_t n) {
   if (!buf || n < 64) {
     nnhip_set_error("nnhip_config: buffer of at least 64 bytes");
     return NNHIP_E_INVALID;
   }
-  static const char* names[] = {"NNHIP_EDGE_LDS", "NNHIP_EDGE_SMALL_ATOMS", "NNHIP_EDGE_WPR", "NNHIP_FORCE_DIRECT_MOL", "NNHIP_FORCE_FWD_MOL", "NNHIP_GRAPH_MOL",
-                                "NNHIP_GRAPH_SMALL_ATOMS", "NNHIP_HEAD_OUT_MOL", "NNHIP_MLP_REGW", "NNHIP_MLP_REGW_SINGLE", "NNHIP_MLP_SPLIT",
-                                "NNHIP_MLP_WIDE_TILES", "NNHIP_MOL_KERNELS_MIN", "NNHIP_MSG_BWD_FORCE", "NNHIP_MSG_BWD_MOL", "NNHIP_NODE_TURN",
-                                "NNHIP_WGRAD_FORM", "NNHIP_WGRAD_RPC"};
+  // (the library's switches and those that the Python package reads, sorted by name: the order of "env" is stable)
+  std::vector<const char*> names(std::begin(kSwitchNames), std::end(kSwitchNames));
+  names.insert(names.end(), std::begin(kPythonSwitchNames), std::end(kPythonSwitchNames));
+  std::sort(names.begin(), names.end(), [](const char* a, const char* b) { return strcmp(a, b) < 0; });
   int small_atoms, mol_min, wpr[4], mol_forms;
   edge_config(&small_atoms, &mol_min, wpr, &mol_forms);
   const int forms = nnhip_mlp_forms();
-  const char* graph_mol = getenv("NNHIP_GRAPH_MOL");
   size_t o = 0;
   auto put = [&](const char* fmt, auto... a) {
     if (o < n) {
@@ -93,7 +96,7 @@ extern "C" int nnhip_config(char* buf, size_t n) {
   };
   put("{\"version\": %d, \"tooling_build\": %d, \"split_f16_products\": %d, ", nnhip_version(), nnhip_build_flags(), forms & 1);
   put("\"neighbor_list\": {\"single_launch_max_atoms\": %d, \"per_molecule_kernels\": %d, \"cell_list\": \"one periodic molecule (host choice)\"}, ",
-      nnhip_graph_small_max_atoms(), (graph_mol && atoi(graph_mol) == 0) ? 0 : 1);
+      nnhip_graph_small_max_atoms(), graph_mol_on() ? 1 : 0);
   put("\"edge_rows\": {\"waves_per_row\": {\"msg_fwd\": %d, \"force_fwd\": %d, \"force_bwd\": %d, \"msg_bwd\": %d}, \"four_waves_per_row_up_to_atoms\": %d}, ",
       wpr[0], wpr[1], wpr[2], wpr[3], small_atoms);
   put("\"molecule_forms\": {\"max_atoms\": %d, \"edge_kernels_from_molecules\": %d, \"force_fwd\": %d, \"msg_bwd\": %d, \"force_direct\": %d, \"head_out\": %d, "
@@ -107,7 +110,7 @@ extern "C" int nnhip_config(char* buf, size_t n) {
   put("\"radial_table_intervals\": %d, \"env\": {", FT_G);
   bool first = true;
   for (const char* nm : names) {
-    const char* v = getenv(nm);
+    const char* v = switch_text(nm);
     if (!v) continue;
     // (the value goes into a JSON string: keep [A-Za-z0-9_.,+-] and blank out everything else -- a quote or a backslash in a switch
     // must not cost the caller its whole bench line)
@@ -1073,9 +1076,8 @@ extern "C" int nnhip_forward_dev(const nnhip_model* model, const nnhip_step_dev*
                               F + lay.atom_energy, st->atom_node, st->force_node, st->prepared, pair_ptr + N, pair_ptr, stream_,
                             (st->flags & 1) != 0, embedded);
   }
-  static const bool mol_graph_off = getenv("NNHIP_GRAPH_MOL") && atoi(getenv("NNHIP_GRAPH_MOL")) == 0;
   const int32_t* changes = nullptr;
-  if ((st->flags & 1) && B >= 1 && (long)N <= (long)B * NNHIP_MOL_STAGE_MAX && !mol_graph_off) {
+  if ((st->flags & 1) && B >= 1 && (long)N <= (long)B * NNHIP_MOL_STAGE_MAX && graph_mol_on()) {
     // a batch of small molecules: the list by one workgroup per molecule (graph.hip:graph_mol_*_kernel), five launches instead of nine
     // (the parameter check's launch also clears status / mol_ptr / row_ptr)
     TRY(prepare_check_counter_impl(model, st->prepared, st->prepared_bytes, &changes, stream_,

@@ -1,5 +1,5 @@
-"""NNHIP_NODE_TURN / NNHIP_MSG_BWD_FORCE and their nnhip_config fields (no GPU needed: the call only formats text), and that the
-switches are documented where the others are."""
+"""NNHIP_NODE_TURN / NNHIP_MSG_BWD_FORCE and their nnhip_config fields (no GPU needed: the call only formats text).  That the
+switches are documented where the others are: tests/test_switches_host.py::test_one_source_of_truth."""
 import json
 import os
 import subprocess
@@ -34,10 +34,3 @@ def test_defaults_and_switches():
     assert _config(NNHIP_MSG_BWD_MOL='0')['molecule_forms']['msg_bwd_with_forces'] == 0
     assert _config(NNHIP_NODE_TURN='1')['node_turn_fused'] == 1
 
-
-def test_switches_are_documented():
-    for doc in ('README.md', 'INTEGRATION.md', os.path.join('tools', 'README.md')):
-        with open(os.path.join(ROOT, doc)) as f:
-            text = f.read()
-        for name in ('NNHIP_NODE_TURN', 'NNHIP_MSG_BWD_FORCE'):
-            assert name in text, (doc, name)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the dense 128x128 linear kernels through the C ABI (nnhip_linear128).
-usage: python tools/bench_lin.py [M ...]      env: NNHIP_LIN_BLOCKS, NNHIP_SMALL_TILES"""
+usage: python tools/bench_lin.py [M ...]      env: NNHIP_LIN_BLOCKS"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,7 +18,7 @@ def timeit(fn, reps=20):
 Ms = [int(a) for a in sys.argv[1:]] or [21504, 64512, 313006]
 W = torch.randn(128, 128, device='cuda') / 11
 b = torch.randn(128, device='cuda')
-print('NNHIP_LIN_BLOCKS', os.environ.get('NNHIP_LIN_BLOCKS'), 'NNHIP_SMALL_TILES', os.environ.get('NNHIP_SMALL_TILES'))
+print('NNHIP_LIN_BLOCKS', os.environ.get('NNHIP_LIN_BLOCKS'))
 for M in Ms:
     A = torch.randn(M, 128, device='cuda'); H = torch.randn(M, 128, device='cuda'); C = torch.empty_like(A)
     ref = A @ W.T
