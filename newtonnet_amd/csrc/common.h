@@ -319,7 +319,7 @@ struct NodeFwdArgs {
   const float* f;      // [N][3][F] force_node after the edge phase (f')
   const float* a_mid;  // [N][F]
   const float* Wu;     // [F][F]
-  float* q;            // [N][3][F] out
+  float* q;            // [N][3][F] out (NULL: not stored)
   float* a_out;        // [N][F] out
   const float *W0, *b0, *W2, *b2;  // next layer's message_nodepart (W0 == NULL: no next layer)
   float *hn, *m;       // [N][F] out (next layer)
@@ -332,7 +332,7 @@ struct NodeBwdArgs {
   const float *W2T, *W0T;  // transposed weights of the upper node MLP / head
   float* g_a;          // [N][F]  running dE/d atom_node  (acc_ga: g_a += ..., else g_a = ...)
   const float* f;      // [N][3][F] force_node of the lower layer after its edge phase
-  const float* q;      // [N][3][F]
+  const float* q;      // [N][3][F] (split-f16 kernel: NULL = form it again from f and NodeImages::Wu)
   const float* G_f;    // [N][3][F] dE/d f_out of the lower layer from above (NULL = 0)
   const float* WuT;    // [F][F] transposed equiv_update of the lower layer
   float* gf;           // [N][3][F] out
@@ -407,6 +407,9 @@ struct NodeTurnArgs {
 };
 int launch_node_turn_split(const NodeTurnArgs& a, const NodeImages& im, hipStream_t s);
 bool node_turn_enabled();        // node128s.hip (NNHIP_NODE_TURN=0 keeps the three launches)
+// launch_node_bwd_split with a.q == NULL and im.Wu set forms q = f W_u^T again instead of reading it (the bits node_fwd would have
+// stored); launch_node_fwd / launch_node_fwd_split with a.q == NULL do not store it
+bool node_bwd_q_enabled();       // node128s.hip (NNHIP_NODE_BWD_Q=0 keeps the stored q)
 int launch_mlp_wide_split(int mode, bool accum, const MlpArgs& a, hipStream_t s);      // needs a.W1_img / a.W2_img, SiLU
 int launch_mlp_wide_pair_split(int mode, const MlpPair& P, hipStream_t s);
 int launch_lin_wide_split(const float* X, int ldx, const char* img, float* Y, int ldy, int M, bool acc, hipStream_t s);

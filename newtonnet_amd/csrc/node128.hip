@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(256, NODE_WG_PER_CU) node_fwd_kernel(const Nod
       blk_load(a, p.a_mid, (size_t)rc * NF, t);
     acc_to(qv, tile_gemm(t, wf));
     if (c == 2 && p.W0) load_w(wf, t, p.W0);
-    if (live) blk_store<NODE_NT != 0>(qv, p.q, ((size_t)row * 3 + c) * NF, t);
+    if (p.q && live) blk_store<NODE_NT != 0>(qv, p.q, ((size_t)row * 3 + c) * NF, t);
 #pragma unroll
     for (int k = 0; k < 16; ++k) upd[k] = fmaf(cur[k], qv[k], upd[k]);
   }

@@ -274,8 +274,8 @@ __device__ __forceinline__ void sblk_store(const float (&v)[16], float* __restri
 #define NS_DBG_STAMP()
 #define NS_DBG_PRINT(tag)
 #endif
-#define NS_TILE_SETUP()                                                      \
-  __shared__ __attribute__((aligned(16))) char lds[(NS_MERGE3 ? 3 : 1) * NS_LDS_BYTES]; \
+#define NS_TILE_SETUP_N(NTILES)                                              \
+  __shared__ __attribute__((aligned(16))) char lds[(NTILES) * NS_LDS_BYTES]; \
   STile t;                                                                   \
   t.img = lds;                                                               \
   t.pmax = reinterpret_cast<float*>(lds + 2 * NS_PLANE);                     \
@@ -285,6 +285,7 @@ __device__ __forceinline__ void sblk_store(const float (&v)[16], float* __restri
   const int row = blockIdx.x * 32 + t.r;                                     \
   const int rc = min(row, p.N - 1);                                          \
   const bool live = row < p.N;
+#define NS_TILE_SETUP() NS_TILE_SETUP_N(NS_MERGE3 ? 3 : 1)
 
 // equiv_update + energy update + the next layer's message_nodepart (or the first two linears of the energy head)
 __global__ void __launch_bounds__(256, NS_WG_PER_CU) node_fwd_split_kernel(const NodeFwdArgs p, const NodeImages im) {
@@ -315,16 +316,16 @@ __global__ void __launch_bounds__(256, NS_WG_PER_CU) node_fwd_split_kernel(const
     __syncthreads();
     sblk_load(a, p.a_mid, (size_t)rc * NF, t);
     tile_gemm_s(qv, t, wf, inv0);
-    if (live) sblk_store(qv, p.q, ((size_t)row * 3 + 0) * NF, t);
+    if (p.q && live) sblk_store(qv, p.q, ((size_t)row * 3 + 0) * NF, t);
 #pragma unroll
     for (int k = 0; k < 16; ++k) upd[k] = x0[k] * qv[k];
     tile_gemm_s(qv, t1, wf, inv1);
-    if (live) sblk_store(qv, p.q, ((size_t)row * 3 + 1) * NF, t);
+    if (p.q && live) sblk_store(qv, p.q, ((size_t)row * 3 + 1) * NF, t);
 #pragma unroll
     for (int k = 0; k < 16; ++k) upd[k] = fmaf(x1[k], qv[k], upd[k]);
     tile_gemm_s(qv, t2, wf, inv2);
     if (p.W0) load_wimg(wf, t, im.W0);
-    if (live) sblk_store(qv, p.q, ((size_t)row * 3 + 2) * NF, t);
+    if (p.q && live) sblk_store(qv, p.q, ((size_t)row * 3 + 2) * NF, t);
 #pragma unroll
     for (int k = 0; k < 16; ++k) upd[k] = fmaf(x2[k], qv[k], upd[k]);
   }
@@ -349,7 +350,7 @@ __global__ void __launch_bounds__(256, NS_WG_PER_CU) node_fwd_split_kernel(const
     NS_DBG_STAMP()
     if (c == 2 && p.W0) load_wimg(wf, t, im.W0);
 #ifndef NS_ABL_NO_Q   // tooling (wrong forces): the update without its q = f W_u^T round trip -- what recomputing q in the adjoint could save at most
-    if (live) sblk_store(qv, p.q, ((size_t)row * 3 + c) * NF, t);
+    if (p.q && live) sblk_store(qv, p.q, ((size_t)row * 3 + c) * NF, t);   // (p.q == NULL: nobody reads q -- energy only, or node_bwd recomputes it)
 #endif
 #pragma unroll
     for (int k = 0; k < 16; ++k) upd[k] = fmaf(cur[k], qv[k], upd[k]);
@@ -392,11 +393,16 @@ __global__ void __launch_bounds__(256, NS_WG_PER_CU) node_fwd_split_kernel(const
 }
 
 // adjoint of the upper node MLP / head, then of the lower layer's update (see node128.hip:node_bwd_kernel)
+// RQ: q_k = f_k W_u^T is not read back (p.q == NULL) but formed again from the f_k tile the kernel loads anyway and the image of W_u
+// (im.Wu) -- the commit and the GEMM of node_fwd_split_kernel on the same operands, so the same bits (node_turn_split_kernel does
+// the same for the last layer).  The f_k tile and the g_a f_k tile go to two LDS tiles behind ONE publish / barrier / commit /
+// barrier round, so a component costs two barriers as before; both fragment sets (W_u, W_u^T) stay in registers.
 #ifndef NS_WG_PER_CU_BWD
 #define NS_WG_PER_CU_BWD NS_WG_PER_CU
 #endif
+template <bool RQ>
 __global__ void __launch_bounds__(256, NS_WG_PER_CU_BWD) node_bwd_split_kernel(const NodeBwdArgs p, const NodeImages im) {
-  NS_TILE_SETUP()
+  NS_TILE_SETUP_N(NS_MERGE3 ? 3 : (RQ ? 2 : 1))
   float ga[16];
   WFrag wf;
   if (p.W2T) {
@@ -474,33 +480,66 @@ __global__ void __launch_bounds__(256, NS_WG_PER_CU_BWD) node_bwd_split_kernel(c
 #else
   float fa[16], fb[16];
   sblk_load(fa, p.f, ((size_t)rc * 3 + 0) * NF, t);
+  if constexpr (RQ) {
+    WFrag wq;
+    load_wimg(wq, t, im.Wu);
+    STile tg = t;
+    tg.img = lds + NS_LDS_BYTES;
+    tg.pmax = reinterpret_cast<float*>(lds + NS_LDS_BYTES + 2 * NS_PLANE);
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float (&cur)[16] = (c & 1) ? fb : fa;
-    float (&nxt)[16] = (c & 1) ? fa : fb;
-    float out[16], qv[16], gin[16];
+    for (int c = 0; c < 3; ++c) {
+      float (&cur)[16] = (c & 1) ? fb : fa;
+      float (&nxt)[16] = (c & 1) ? fa : fb;
+      float out[16], qv[16], gin[16], gq[16];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) cur[k] *= ga[k];
-    tile_publish(cur, t);
-    __syncthreads();
-    const float inv = tile_commit(cur, t);
-    __syncthreads();
-    if (c < 2) sblk_load(nxt, p.f, ((size_t)rc * 3 + c + 1) * NF, t);
+      for (int k = 0; k < 16; ++k) gq[k] = cur[k] * ga[k];
+      tile_publish(cur, t);       // the f_k tile as node_fwd_split_kernel commits it: row maxima of the unscaled rows
+      tile_publish(gq, tg);
+      __syncthreads();
+      const float invf = tile_commit(cur, t);
+      const float invg = tile_commit(gq, tg);
+      __syncthreads();
+      if (c < 2) sblk_load(nxt, p.f, ((size_t)rc * 3 + c + 1) * NF, t);
+      if (p.G_f) sblk_load(gin, p.G_f, ((size_t)rc * 3 + c) * NF, t);
+      tile_gemm_s(qv, t, wq, invf);
+      tile_gemm_s(out, tg, wf, invg);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) out[k] = fmaf(ga[k], qv[k], out[k]);
+      if (p.G_f) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) out[k] += gin[k];
+      }
+      if (live) sblk_store(out, p.gf, ((size_t)row * 3 + c) * NF, t);
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float (&cur)[16] = (c & 1) ? fb : fa;
+      float (&nxt)[16] = (c & 1) ? fa : fb;
+      float out[16], qv[16], gin[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) cur[k] *= ga[k];
+      tile_publish(cur, t);
+      __syncthreads();
+      const float inv = tile_commit(cur, t);
+      __syncthreads();
+      if (c < 2) sblk_load(nxt, p.f, ((size_t)rc * 3 + c + 1) * NF, t);
 #ifdef NS_ABL_NO_Q
 #pragma unroll
-    for (int k = 0; k < 16; ++k) qv[k] = cur[k];
+      for (int k = 0; k < 16; ++k) qv[k] = cur[k];
 #else
-    sblk_load(qv, p.q, ((size_t)rc * 3 + c) * NF, t);
+      sblk_load(qv, p.q, ((size_t)rc * 3 + c) * NF, t);
 #endif
-    if (p.G_f) sblk_load(gin, p.G_f, ((size_t)rc * 3 + c) * NF, t);
-    tile_gemm_s(out, t, wf, inv);
+      if (p.G_f) sblk_load(gin, p.G_f, ((size_t)rc * 3 + c) * NF, t);
+      tile_gemm_s(out, t, wf, inv);
 #pragma unroll
-    for (int k = 0; k < 16; ++k) out[k] = fmaf(ga[k], qv[k], out[k]);
-    if (p.G_f) {
+      for (int k = 0; k < 16; ++k) out[k] = fmaf(ga[k], qv[k], out[k]);
+      if (p.G_f) {
 #pragma unroll
-      for (int k = 0; k < 16; ++k) out[k] += gin[k];
+        for (int k = 0; k < 16; ++k) out[k] += gin[k];
+      }
+      if (live) sblk_store(out, p.gf, ((size_t)row * 3 + c) * NF, t);
     }
-    if (live) sblk_store(out, p.gf, ((size_t)row * 3 + c) * NF, t);
   }
 #endif
 }
@@ -802,10 +841,20 @@ int launch_node_bwd_split(const NodeBwdArgs& a, const NodeImages& im, hipStream_
   if (a.N <= 0) return 0;
   ScopedTimer t0(TC_LIN, s);
   ScopedTimer t1(TC_LIN1, s);
-  node_bwd_split_kernel<<<cdiv(a.N, 32), 256, 0, s>>>(a, im);
+  if (a.WuT && !a.q) {   // the recompute form of the update adjoint: needs the image of W_u beside that of W_u^T
+    if (!im.Wu || NS_MERGE3) {
+      nnhip_set_error("node_bwd: no q and no image of the update weights to form it from");
+      return NNHIP_E_INVALID;
+    }
+    node_bwd_split_kernel<true><<<cdiv(a.N, 32), 256, 0, s>>>(a, im);
+  } else {
+    node_bwd_split_kernel<false><<<cdiv(a.N, 32), 256, 0, s>>>(a, im);
+  }
   LAUNCH_CHECK();
   return 0;
 }
+// NNHIP_NODE_BWD_Q=0: node_fwd stores q = f W_u^T and node_bwd reads it back (the route of everything but the energy+force sweep)
+bool node_bwd_q_enabled() { return !NS_MERGE3 && switches().node_bwd_q != 0; }
 
 // NNHIP_NODE_TURN=0: the turn-around as its three launches (node_fwd, head_out, node_bwd)
 bool node_turn_enabled() { return switches().node_turn != 0; }

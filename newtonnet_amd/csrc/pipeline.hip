@@ -107,6 +107,8 @@ extern "C" int nnhip_config(char* buf, size_t n) {
       mlp_wide_max_tiles_silu(), (forms >> 1) & 1, (forms >> 2) & 1, (forms >> 3) & 1, (forms >> 4) & 1);
   // (the turn-around of the energy+force sweep as one launch: split-f16 products, forces wanted, no LayerNorm on the last layer)
   put("\"node_turn_fused\": %d, ", ((forms & 1) && node_turn_enabled()) ? 1 : 0);
+  // (q = f W_u^T formed again in the update adjoint of the energy+force sweep: split-f16 products, SiLU, no LayerNorm on that layer)
+  put("\"node_bwd_recomputes_q\": %d, ", ((forms & 1) && node_bwd_q_enabled()) ? 1 : 0);
   put("\"radial_table_intervals\": %d, \"env\": {", FT_G);
   bool first = true;
   for (const char* nm : names) {
@@ -710,6 +712,10 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
   // the turn-around of the sweep (last node_fwd, head tail, head adjoint + last update adjoint) as one launch, node128s.hip:
   // q[L-1], e1, e2 and g_e then stay unwritten (nobody reads them on this route)
   const bool node_turn = split_nodes && want_forces && !model->layer[L - 1].ln_w && node_turn_enabled();
+  // q[l] = f W_u^T of a layer without LayerNorm is formed again by the node_bwd launch that needs it (node128s.hip) instead of going
+  // through the workspace; an energy-only call has no reader of q at all.  (The q slots stay: every other route stores q.)
+  const bool recompute_q = split_nodes && want_forces && node_bwd_q_enabled();
+  auto q_stored = [&](int l) { return want_forces && !(recompute_q && !model->layer[l].ln_w); };
   for (int l = 0; l < L; ++l) {
     const nnhip_layer_params& lp = model->layer[l];
     const bool has_f = l > 0;
@@ -747,7 +753,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
       na.f = F_OUT(l);
       na.a_mid = P(w.pub.a_mid[l]);
       na.Wu = lp.update_w;
-      na.q = P(w.pub.q[l]);
+      na.q = q_stored(l) ? P(w.pub.q[l]) : nullptr;
       na.a_out = A_OUT(l);
       if (l + 1 < L && !lp.ln_w) {
         const nnhip_layer_params& nx = model->layer[l + 1];
@@ -847,7 +853,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
     nb.g_a = P(w.pub.g_a);
     nb.acc_ga = 0;
     nb.f = F_OUT(L - 1);
-    nb.q = P(w.pub.q[L - 1]);
+    nb.q = q_stored(L - 1) ? P(w.pub.q[L - 1]) : nullptr;
     nb.G_f = nullptr;
     nb.WuT = Q(pq.wT[L - 1][6]);
     nb.gf = P(w.gf_mid);
@@ -858,6 +864,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
     bim.W2T = pbase + pq.img_head[IMG_HEAD2_T];
     bim.W0T = pbase + pq.img_head[IMG_HEAD0_T];
     bim.WuT = pbase + pq.img[L - 1][IMG_UPDATE_T];
+    bim.Wu = pbase + pq.img[L - 1][IMG_UPDATE];
     const nnhip_layer_params& top = model->layer[L - 1];
     if (top.ln_w) {   // the LayerNorm adjoint sits between the head adjoint and the update adjoint: three launches
       NodeBwdArgs head = nb;
@@ -923,7 +930,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
       nb.g_a = P(w.pub.g_a);
       nb.acc_ga = 1;
       nb.f = F_OUT(l - 1);
-      nb.q = P(w.pub.q[l - 1]);
+      nb.q = q_stored(l - 1) ? P(w.pub.q[l - 1]) : nullptr;
       nb.G_f = g_fin;   // dE/d f_out of layer l-1, produced by force_bwd of layer l just above
       nb.WuT = Q(pq.wT[l - 1][6]);
       nb.gf = P(w.gf_mid);
@@ -934,6 +941,7 @@ static int energy_forces_impl(const nnhip_model* model, const int64_t* z, const 
       bim.W2T = pbase + pq.img[l][IMG_NODE2_T];
       bim.W0T = pbase + pq.img[l][IMG_NODE0_T];
       bim.WuT = pbase + pq.img[l - 1][IMG_UPDATE_T];
+      bim.Wu = pbase + pq.img[l - 1][IMG_UPDATE];
       const nnhip_layer_params& below = model->layer[l - 1];
       if (below.ln_w) {
         NodeBwdArgs mlp = nb;

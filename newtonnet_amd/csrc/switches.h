@@ -32,6 +32,7 @@
   X(int, num, mol_kernels_min, "NNHIP_MOL_KERNELS_MIN", 640)          /* molecule-resident edge kernels from this many molecules (profiles/r04_mol_kernels_crossover.txt) */ \
   X(int, flag, msg_bwd_force, "NNHIP_MSG_BWD_FORCE", 1)               /* 0: layer 0's msg_bwd_mol_kernel never goes on with the forces */ \
   X(int, flag, msg_bwd_mol, "NNHIP_MSG_BWD_MOL", 1)                   /* 0: never msg_bwd_mol_kernel */ \
+  X(int, flag, node_bwd_q, "NNHIP_NODE_BWD_Q", 1)                     /* 0: node_fwd stores q = f W_u^T and node_bwd reads it back, instead of forming it again */ \
   X(int, flag, node_turn, "NNHIP_NODE_TURN", 1)                       /* 0: the turn-around as its three launches (node_fwd, head_out, node_bwd) */
 
 struct Switches {

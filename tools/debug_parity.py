@@ -13,8 +13,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# the fused turn-around keeps q of the last layer on chip: this tool reads it from the workspace, so it takes the three launches
+# the fused turn-around keeps q of the last layer on chip and the update adjoint forms q of the other layers again: this tool reads q
+# from the workspace, so it takes the three launches and the stored q
 os.environ.setdefault('NNHIP_NODE_TURN', '0')
+os.environ.setdefault('NNHIP_NODE_BWD_Q', '0')
 
 from newtonnet_amd import hip  # noqa: E402
 from newtonnet_amd.models import NewtonNet  # noqa: E402
