@@ -890,6 +890,30 @@ int nnhip_mode_sample_large(const float* modes, const float* evals, const int64_
                             float* amplitudes, int32_t* n_skipped, int32_t min_dim, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Molecular dynamics on the device (csrc/md.hip): ONE launch on `stream` integrates every atom of a batch between two force
+ * evaluations.  The scheme is BAOAB with the O step exact; c1 = 1 with sigma = noise = NULL is velocity Verlet.  Per atom i and
+ * coordinate k, all in fp32, every multiply-add one fma and every lone product one rounding (tests/md_ref.py restates the chain):
+ *   finish (NNHIP_MD_FINISH):  v = fma(hk_i, F_ik, v)                         the second half kick of the step just evaluated
+ *                              ke_out[i] = (0.5 mass_i) (vx vx + vy vy + vz vz)  only when ke_out != NULL (summed x, y, z by fma)
+ *   begin  (NNHIP_MD_BEGIN):   v = fma(hk_i, F_ik, v);  x = fma(dth, v, pos_in);  v = fma(sigma_i, noise_ik, c1 v) [skipped when
+ *                              noise == NULL];  pos_out = fma(dth, v, x)
+ * flags = FINISH | BEGIN does both in that order with the same forces.  pos_in, force, noise [N,3]; vel [N,3] is updated in place;
+ * hk [N] = dt / (2 m_i); mass [N] (read only for ke_out); sigma [N] and noise are both given or both NULL; dth = dt / 2.
+ * pos_out [N,3] may NOT overlap pos_in (NNHIP_E_INVALID, nothing is launched): the caller of a deferred forward step must be able
+ * to repeat that step from the positions it was queued with.  With FINISH alone pos_in / pos_out are not touched and may be NULL.
+ * ke_out needs FINISH and mass.  n_atoms == 0: success, nothing is launched.  An atom with hk = sigma = 0 and v = 0 keeps its
+ * position bit for bit (x = fma(dth, 0, x) twice).
+ *   nnhip_md_kinetic: out[b] = sum of ke[mol_ptr[b] .. mol_ptr[b+1] - 1], one wave64 per molecule, lane l adds the atoms l, l + 64,
+ *   ... in that order and the 64 partial sums meet in a fixed butterfly: no float atomics, bitwise repeatable, any molecule size.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_MD_FINISH 1
+#define NNHIP_MD_BEGIN 2
+int nnhip_md_step(const float* pos_in, float* vel, const float* force, const float* hk, const float* mass, const float* sigma,
+                  const float* noise, float dth, float c1, int32_t flags, int32_t n_atoms, float* pos_out, float* ke_out,
+                  void* stream);
+int nnhip_md_kinetic(const float* ke, const int32_t* mol_ptr, int32_t n_mol, float* out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

@@ -1,0 +1,299 @@
+"""Batched molecular dynamics on the HIP path: every molecule of a batch is integrated on the device, one force evaluation and one
+integrator launch (nnhip_md_step, csrc/md.hip) per step, with no host round trip of positions or forces.
+
+The reference leaves dynamics to an outside driver that calls its calculator once per step for one structure.
+Here `Dynamics` owns positions, velocities and forces of B molecules as device tensors and advances them together: microcanonical
+(velocity Verlet) with friction = 0, Langevin in the BAOAB splitting (Leimkuhler & Matthews 2013, the O step exact) otherwise.
+
+Units: positions in Angstrom, energies in eV, masses in amu, hence time in Angstrom sqrt(amu / eV) = 10.18 fs; `timestep` is given in
+fs and `friction` in 1 / fs (FS converts), temperatures in K, velocities in Angstrom per internal time unit.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from newtonnet_amd import hip
+from newtonnet_amd.vibrations import K_BOLTZMANN, _AMU, _E_CHARGE, table_masses
+
+# one femtosecond in the internal time unit Angstrom sqrt(amu / eV): 1e-15 s x sqrt(e / (1e-20 amu)) s^-1 = 0.0982269
+FS = 1e-15 * math.sqrt(_E_CHARGE / (1e-20 * _AMU))
+
+
+def _per_atom_temperature(temperature, batch: torch.Tensor, n_mol: Optional[int] = None) -> torch.Tensor:
+    """fp64 [N]: the temperature of every atom's molecule; `temperature` is a number or a [B] tensor (a ladder)"""
+    if isinstance(temperature, torch.Tensor) and temperature.dim() > 0:
+        T = temperature.detach().to(device=batch.device, dtype=torch.float64).reshape(-1)
+        if n_mol is not None and T.numel() != n_mol:
+            raise ValueError(f'temperature: a number or one value per molecule ({n_mol}) expected (got {T.numel()})')
+        return T[batch.long()]
+    return torch.full((batch.numel(),), float(temperature), dtype=torch.float64, device=batch.device)
+
+
+def _check_temperature(temperature, n_mol: int):
+    if temperature is None:
+        return
+    if isinstance(temperature, torch.Tensor) and temperature.dim() > 0:
+        if temperature.numel() != n_mol:
+            raise ValueError(f'temperature: a number or one value per molecule ({n_mol}) expected (got {temperature.numel()})')
+        return        # (its values live on the device: a negative one gives NaN velocities, not an exception)
+    T = float(temperature)
+    if not (T >= 0.0 and math.isfinite(T)):
+        raise ValueError(f'temperature: a finite value >= 0 K expected (got {temperature!r})')
+
+
+def langevin_coefficients(timestep_fs: float, friction_per_fs: float, temperature, masses: torch.Tensor, batch: torch.Tensor):
+    """(c1, sigma [N] fp32) of the exact Ornstein-Uhlenbeck step v <- c1 v + sigma xi over one time step:
+    c1 = exp(-gamma dt), sigma_i = sqrt((1 - c1^2) k_B T_{batch[i]} / m_i).  Computed in fp64 and rounded once to fp32 (c1 comes back
+    as the Python float of its fp32 value).  temperature: a number, or a [B] tensor -- one temperature per molecule."""
+    gdt = float(friction_per_fs) * float(timestep_fs)
+    if not (gdt >= 0.0 and math.isfinite(gdt)):
+        raise ValueError(f'friction x timestep: a finite value >= 0 expected (got {gdt!r})')
+    c1 = math.exp(-gdt)
+    one_minus_c1sq = -math.expm1(-2.0 * gdt)
+    T = _per_atom_temperature(temperature, batch)
+    sigma = torch.sqrt(one_minus_c1sq * K_BOLTZMANN * T / masses.detach().double().reshape(-1))
+    return float(np.float32(c1)), sigma.float()
+
+
+def _mol_ptr(batch: torch.Tensor, n_mol: int) -> torch.Tensor:
+    """int32 [B+1] atom offsets of a sorted batch vector"""
+    ptr = torch.zeros(n_mol + 1, dtype=torch.int32, device=batch.device)
+    if batch.numel():
+        ptr[1:] = torch.cumsum(torch.bincount(batch.long(), minlength=n_mol), 0).to(torch.int32)
+    return ptr
+
+
+def _molecule_sums(x: torch.Tensor, batch: torch.Tensor, n_mol: int) -> torch.Tensor:
+    """[B, W] sums of the rows x [N, W] (W even) per molecule: the library's deterministic segment sum on the device"""
+    if x.is_cuda:
+        return hip.segment_sum(x.contiguous(), _mol_ptr(batch, n_mol), n_mol)
+    return torch.zeros(n_mol, x.shape[1], dtype=x.dtype).index_add_(0, batch.long(), x)
+
+
+def maxwell_boltzmann(masses: torch.Tensor, batch: torch.Tensor, temperature, generator: Optional[torch.Generator] = None,
+                      n_mol: Optional[int] = None) -> torch.Tensor:
+    """Velocities fp32 [N,3] drawn from the Maxwell-Boltzmann distribution at `temperature` (a number or a [B] ladder) with exactly
+    one torch.randn((N, 3)) call on the device of `masses`, then each molecule's centre-of-mass momentum removed."""
+    m = masses.detach().float().reshape(-1)
+    n_mol = int(batch.max()) + 1 if n_mol is None else int(n_mol)
+    xi = torch.randn((m.numel(), 3), generator=generator, device=m.device, dtype=torch.float32)
+    T = _per_atom_temperature(temperature, batch, n_mol)
+    v = xi * torch.sqrt(K_BOLTZMANN * T / m.double()).float()[:, None]
+    s = _molecule_sums(torch.cat([m[:, None] * v, m[:, None]], dim=1), batch, n_mol)       # [B, 4]: momentum, mass
+    return v - (s[:, :3] / s[:, 3:].clamp(min=1e-30))[batch.long()]
+
+
+class Trajectory:
+    """What Dynamics.run recorded, as device tensors:
+
+    step              int64 [R]      step numbers since the Dynamics was made
+    pos, vel          fp32 [R,N,3]   positions (unwrapped) and full-step velocities
+    potential_energy  fp32 [R,B]     the model's energy at pos
+    kinetic_energy    fp32 [R,B]     sum of m v^2 / 2 per molecule
+    total_energy      fp32 [R,B]     their sum;  temperature fp32 [R,B] = 2 KE / (3 n_b k_B)
+    """
+
+    def __init__(self, step, pos, vel, potential_energy, kinetic_energy, counts):
+        self.step, self.pos, self.vel = step, pos, vel
+        self.potential_energy, self.kinetic_energy, self._counts = potential_energy, kinetic_energy, counts
+
+    @property
+    def total_energy(self):
+        return self.potential_energy + self.kinetic_energy
+
+    @property
+    def temperature(self):
+        return 2.0 * self.kinetic_energy / (3.0 * K_BOLTZMANN * self._counts.clamp(min=1).float())
+
+
+class Dynamics:
+    """B molecules advanced together on the device.
+
+    model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads.  z, pos, cell, batch: as for model(...), on the
+    device; none of them is modified (the positions are copied).  masses: fp32 [N] amu (None: standard atomic weights of z).
+    timestep in fs, friction in 1 / fs: 0 = microcanonical (velocity Verlet; no random numbers are drawn), > 0 = Langevin at
+    `temperature` (K; a number or a [B] tensor, one temperature per molecule).  velocities: fp32 [N,3] in Angstrom per internal time
+    unit (None: Maxwell-Boltzmann at `temperature` when one is given, else zero).  fixed: bool [N], atoms that never move.
+    generator: a generator of the device for the initial velocities and the noise (None: torch's global one).
+
+    Periodic molecules: positions stay unwrapped; the model's neighbor list takes the minimum image of every pair itself."""
+
+    def __init__(self, model, z, pos, cell, batch, masses=None, velocities=None, temperature=None, friction=0.0, timestep=0.5,
+                 fixed=None, generator=None):
+        # ---- everything that can be refused without touching the device
+        if getattr(model, 'training', False):
+            raise ValueError('Dynamics needs the model in eval mode: call model.eval()')
+        props = list(getattr(model, 'output_properties', []))
+        if 'energy' not in props or 'gradient_force' not in props:
+            raise ValueError(f"Dynamics needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
+        for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
+        N = pos.shape[0]
+        if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
+            raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
+        B = cell.shape[0]
+        if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
+            raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
+        if pos.dtype != torch.float32 or cell.dtype != torch.float32:
+            raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
+        if masses is not None and (not isinstance(masses, torch.Tensor) or masses.numel() != N):
+            raise ValueError(f'masses: a tensor of {N} values expected')
+        if velocities is not None and (not isinstance(velocities, torch.Tensor) or tuple(velocities.shape) != (N, 3)):
+            raise ValueError(f'velocities: a tensor [{N},3] expected')
+        if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
+            raise ValueError(f'fixed: a bool tensor [{N}] expected')
+        timestep, friction = float(timestep), float(friction)
+        if not (timestep > 0.0 and math.isfinite(timestep)):
+            raise ValueError(f'timestep: a finite value > 0 fs expected (got {timestep!r})')
+        if not (friction >= 0.0 and math.isfinite(friction)):
+            raise ValueError(f'friction: a finite value >= 0 per fs expected (got {friction!r})')
+        _check_temperature(temperature, B)
+        if friction > 0.0 and temperature is None:
+            raise ValueError('friction > 0 (Langevin dynamics) needs a temperature')
+        if not pos.is_cuda:
+            raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
+        dev = pos.device
+        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('masses', masses), ('velocities', velocities), ('fixed', fixed),
+                        ('temperature', temperature)):
+            if isinstance(t, torch.Tensor) and t.dim() > 0 and t.device != dev:
+                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        if generator is not None and torch.device(generator.device).type != dev.type:
+            raise ValueError(f'generator is on {generator.device}, pos on {dev}')
+        # ---- state
+        self.model, self.z, self.cell, self.batch = model, z, cell, batch
+        self.n_atoms, self.n_mol = N, B
+        self.timestep, self.friction, self.temperature, self.generator = timestep, friction, temperature, generator
+        self.step_count = 0
+        with torch.no_grad():
+            m = table_masses(z) if masses is None else masses.detach().float().reshape(-1).clone()
+            if N and not bool(((m > 0) & torch.isfinite(m)).all()):
+                raise ValueError('masses: positive finite values expected')
+            self.masses = m.contiguous()
+            dt = timestep * FS
+            self._dth = float(np.float32(0.5 * dt))
+            free = None if fixed is None else ~fixed
+            hk = (0.5 * dt) / m.double()
+            self._hk = (hk if free is None else hk * free).float().contiguous()
+            self._c1, self._sigma = 1.0, None
+            if friction > 0.0:
+                self._c1, sigma = langevin_coefficients(timestep, friction, temperature, m, batch)
+                self._sigma = (sigma if free is None else sigma * free).contiguous()
+            if velocities is not None:
+                vel = velocities.detach().float().clone()
+            elif temperature is not None:
+                vel = maxwell_boltzmann(m, batch, temperature, generator, n_mol=B)
+            else:
+                vel = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+            self._vel = (vel if free is None else vel * free[:, None]).contiguous()
+            # two position buffers: a step reads one and writes the other, so the forward call queued on the one it read can still
+            # be repeated from it (NewtonNet._forward_deferred)
+            self._pos = [pos.detach().clone().contiguous(), torch.empty(N, 3, dtype=torch.float32, device=dev)]
+            self._cur = 0
+            self._mol_ptr = _mol_ptr(batch, B)
+            self._counts = (self._mol_ptr[1:] - self._mol_ptr[:-1]).long()
+            self._ke_atom = torch.zeros(N, dtype=torch.float32, device=dev)
+            self._ke = torch.zeros(B, dtype=torch.float32, device=dev)
+            self._force = self._energy = None
+
+    # ------------------------------------------------------------------------------------------
+    def _evaluate(self):
+        """forces and energies at the current positions.  Touching gradient_force settles the deferred record of the call -- a
+        repeat, if one is needed, happens HERE, from the buffer the call was queued with and before any kernel writes a buffer"""
+        out = self.model(self.z, self._pos[self._cur], self.cell, self.batch)
+        self._force = out.gradient_force
+        self._energy = out.energy
+
+    def _finish(self):
+        """the second half kick with the current forces, and the kinetic energies of the full-step velocities"""
+        hip.md_step(None, self._vel, self._force, self._hk, self._dth, self._c1, hip.MD_FINISH, mass=self.masses,
+                    ke_out=self._ke_atom)
+        hip.md_kinetic(self._ke_atom, self._mol_ptr, out=self._ke)
+
+    def _ensure_state(self):
+        if self._force is None:
+            with torch.no_grad():
+                self._evaluate()
+                # (kinetic energies of the initial velocities from the kernel that computes every later one: a kick with zero forces)
+                hip.md_step(None, self._vel, torch.zeros_like(self._force), self._hk, self._dth, self._c1, hip.MD_FINISH,
+                            mass=self.masses, ke_out=self._ke_atom)
+                hip.md_kinetic(self._ke_atom, self._mol_ptr, out=self._ke)
+
+    @property
+    def positions(self):
+        return self._pos[self._cur].detach().clone()
+
+    @property
+    def velocities(self):
+        return self._vel.clone()
+
+    @property
+    def forces(self):
+        self._ensure_state()
+        return self._force
+
+    @property
+    def potential_energy(self):
+        self._ensure_state()
+        return self._energy
+
+    @property
+    def kinetic_energy(self):
+        self._ensure_state()
+        return self._ke.clone()
+
+    # ------------------------------------------------------------------------------------------
+    def run(self, n_steps: int, record_every: int = 0) -> Trajectory:
+        """Advance every molecule by n_steps and return what was recorded: the steps record_every, 2 record_every, ... of this call
+        and its final step (record_every = 0: the final step only; n_steps = 0: the current state).  May be called again: the state
+        between calls is (positions, velocities, forces, energies) at a full step, and run(a); run(b) leaves the same bits as
+        run(a + b).  Langevin dynamics draws exactly one torch.randn((N, 3)) per step from the generator, in step order."""
+        if int(n_steps) != n_steps or n_steps < 0:
+            raise ValueError(f'n_steps: an integer >= 0 expected (got {n_steps!r})')
+        if int(record_every) != record_every or record_every < 0:
+            raise ValueError(f'record_every: an integer >= 0 expected (got {record_every!r})')
+        n_steps, every = int(n_steps), int(record_every)
+        recorded = list(range(every, n_steps + 1, every)) if every else []
+        if not recorded or recorded[-1] != n_steps:
+            recorded.append(n_steps)
+        R, N, B, dev = len(recorded), self.n_atoms, self.n_mol, self._vel.device
+        with torch.no_grad():
+            self._ensure_state()
+            traj = Trajectory(torch.tensor([self.step_count + k for k in recorded], dtype=torch.int64, device=dev),
+                              torch.empty(R, N, 3, dtype=torch.float32, device=dev), torch.empty(R, N, 3, dtype=torch.float32, device=dev),
+                              torch.empty(R, B, dtype=torch.float32, device=dev), torch.empty(R, B, dtype=torch.float32, device=dev),
+                              self._counts)
+            r = 0
+            pending = False          # the second half kick of the previous step has not been launched yet
+            for k in range(1, n_steps + 1):
+                noise = None
+                if self._sigma is not None:
+                    noise = torch.randn((N, 3), generator=self.generator, device=dev, dtype=torch.float32)
+                other = 1 - self._cur
+                hip.md_step(self._pos[self._cur], self._vel, self._force, self._hk, self._dth, self._c1,
+                            (hip.MD_FINISH | hip.MD_BEGIN) if pending else hip.MD_BEGIN, pos_out=self._pos[other],
+                            sigma=self._sigma, noise=noise)
+                self._cur = other
+                self._evaluate()
+                pending = True
+                if k == recorded[r]:
+                    self._finish()
+                    pending = False
+                    traj.pos[r].copy_(self._pos[self._cur])
+                    traj.vel[r].copy_(self._vel)
+                    traj.potential_energy[r].copy_(self._energy)
+                    traj.kinetic_energy[r].copy_(self._ke)
+                    r += 1
+            if n_steps == 0:
+                traj.pos[0].copy_(self._pos[self._cur])
+                traj.vel[0].copy_(self._vel)
+                traj.potential_energy[0].copy_(self._energy)
+                traj.kinetic_energy[0].copy_(self._ke)
+            self.step_count += n_steps
+        return traj

@@ -249,6 +249,10 @@ def lib():
     L.nnhip_mode_sample_large_max_dim.restype = C.c_int
     L.nnhip_mode_sample_large.argtypes = L.nnhip_mode_sample.argtypes[:-1] + [i32, vp]
     L.nnhip_mode_sample_large.restype = C.c_int
+    L.nnhip_md_step.argtypes = [vp] * 7 + [f32, f32, i32, i32, vp, vp, vp]
+    L.nnhip_md_step.restype = C.c_int
+    L.nnhip_md_kinetic.argtypes = [vp, vp, i32, vp, vp]
+    L.nnhip_md_kinetic.restype = C.c_int
     L.nnhip_weight_image_bytes.restype = sz
     L.nnhip_weight_images.argtypes = [vp, vp, i32, vp]
     L.nnhip_mse_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -296,7 +300,8 @@ EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_
                     'nnhip_edge_index_from_csr', 'nnhip_config', 'nnhip_weight_images_bf16', 'nnhip_bf16_mlp_launches',
                     'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute', 'nnhip_eig_blocks',
                     'nnhip_eig_max_dim', 'nnhip_mode_sample', 'nnhip_eig_large_max_dim', 'nnhip_eig_large_ws_bytes',
-                    'nnhip_eig_blocks_large', 'nnhip_mode_sample_large_max_dim', 'nnhip_mode_sample_large')
+                    'nnhip_eig_blocks_large', 'nnhip_mode_sample_large_max_dim', 'nnhip_mode_sample_large', 'nnhip_md_step',
+                    'nnhip_md_kinetic')
 
 
 def _check(rc: int, what: str):
@@ -834,6 +839,48 @@ def segment_sum(x: torch.Tensor, row_ptr: torch.Tensor, n_rows: int) -> torch.Te
     out = torch.empty((n_rows,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
     _check(lib().nnhip_segment_sum(_ptr(x), _ptr(row_ptr), n_rows, width, _ptr(out), _stream(x.device)),
            'nnhip_segment_sum')
+    return out
+
+
+MD_FINISH, MD_BEGIN = 1, 2      # flags of nnhip_md_step
+
+
+def md_step(pos_in: Optional[torch.Tensor], vel: torch.Tensor, force: torch.Tensor, hk: torch.Tensor, dth: float, c1: float,
+            flags: int, pos_out: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None,
+            sigma: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, ke_out: Optional[torch.Tensor] = None):
+    """One launch of the integrator (nnhip_md_step, csrc/md.hip) on the current stream: MD_FINISH = the second half kick with
+    `force` (and the per-atom kinetic energies into `ke_out`), MD_BEGIN = half kick, half drift, the exact Ornstein-Uhlenbeck
+    step v = c1 v + sigma noise (only with `noise`), half drift.  `vel` is updated in place and `pos_out` written: both must be
+    contiguous float32 (a copy would take the result away); `pos_out` may not overlap `pos_in`."""
+    for name, t in (('vel', vel), ('pos_out', pos_out), ('ke_out', ke_out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
+    N = vel.shape[0]
+    ins = [None if t is None else _f32c(t, name) for name, t in (('pos_in', pos_in), ('force', force), ('hk', hk), ('mass', mass),
+                                                                 ('sigma', sigma), ('noise', noise))]
+    for name, t, numel in (('pos_in', ins[0], 3 * N), ('force', ins[1], 3 * N), ('hk', ins[2], N), ('mass', ins[3], N),
+                           ('sigma', ins[4], N), ('noise', ins[5], 3 * N), ('pos_out', pos_out, 3 * N), ('ke_out', ke_out, N),
+                           ('vel', vel, 3 * N)):
+        if t is not None and (t.numel() != numel or t.device != vel.device):
+            raise ValueError(f'{name}: {numel} values on {vel.device} expected (got {t.numel()} on {t.device})')
+    _check(lib().nnhip_md_step(_ptr(ins[0]), _ptr(vel), _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]), _ptr(ins[5]),
+                               float(dth), float(c1), int(flags), N, _ptr(pos_out), _ptr(ke_out), _stream(vel.device)),
+           'nnhip_md_step')
+
+
+def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b] = sum of ke[mol_ptr[b]:mol_ptr[b+1]] (mol_ptr int32 [B+1]): the deterministic per-molecule sum of nnhip_md_kinetic."""
+    ke = _f32c(ke, 'ke')
+    if mol_ptr.dtype != torch.int32 or not mol_ptr.is_contiguous() or mol_ptr.numel() < 1:
+        raise ValueError('mol_ptr: contiguous int32 [B+1] expected')
+    B = mol_ptr.numel() - 1
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=ke.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B:
+        raise ValueError(f'out: contiguous float32 [{B}] expected')
+    if ke.numel() == 0:
+        return out.zero_()
+    _check(lib().nnhip_md_kinetic(_ptr(ke), _ptr(mol_ptr), B, _ptr(out), _stream(ke.device)), 'nnhip_md_kinetic')
     return out
 
 

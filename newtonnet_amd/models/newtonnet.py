@@ -774,6 +774,15 @@ class NewtonNet(nn.Module):
         normal_modes(..., modes=False).frequencies.  solver: as in normal_modes ('auto' serves molecules above 42 atoms)."""
         return self.normal_modes(z, pos, cell, batch, masses=masses, project=project, modes=False, solver=solver).frequencies
 
+    def dynamics(self, z, pos, cell, batch, **kw):
+        """Molecular dynamics of every molecule of the batch on the device: a newtonnet_amd.dynamics.Dynamics whose run(n_steps,
+        record_every) advances them together, one force evaluation and one integrator launch (csrc/md.hip) per step.  Keywords:
+        masses, velocities, temperature (K, a number or one per molecule), friction (1 / fs; 0 = microcanonical velocity Verlet,
+        > 0 = BAOAB Langevin), timestep (fs), fixed, generator.  Eval mode only; needs the 'energy' and 'gradient_force' heads.
+        The reference leaves dynamics to an outside driver, one structure and one calculator call per step."""
+        from newtonnet_amd import dynamics as _d
+        return _d.Dynamics(self, z, pos, cell, batch, **kw)
+
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated
         (trainer.py:301-313): newtonnet_amd/train_fused.py, no torch autograd graph inside the step."""

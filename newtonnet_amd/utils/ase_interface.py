@@ -168,6 +168,61 @@ class MLAseCalculator(_Base):
                                               generator=gen, solver=solver)
         return out.pos.cpu().numpy().reshape(int(n_samples), len(atoms), 3)
 
+    def run_md(self, atoms_or_list, n_steps: int, timestep: float = 0.5, temperature=None, friction: float = 0.0,
+               record_every: int = 0, seed=None):
+        """n_steps of molecular dynamics of one structure or a list of equally sized ones, all advanced together on the device
+        (NewtonNet.dynamics): timestep in fs, friction in 1 / fs (0: microcanonical; > 0: Langevin at `temperature`, K).  Masses
+        from atoms.get_masses() when the objects have it, else standard atomic weights; initial velocities from
+        atoms.get_momenta() (amu Angstrom per Angstrom sqrt(amu / eV), ase's unit) when they have it, else Maxwell-Boltzmann at
+        `temperature`, or zero without one.  seed: of the device generator behind velocities and noise (None: torch's global one).
+        Returns a dict of numpy arrays over the R recorded steps (record_every, 2 record_every, ... and the last; 0: the last
+        only): positions and velocities [R, n_frames, n_atoms, 3], energy and kinetic_energy [R, n_frames], step [R]; one
+        structure drops the frame axis.  The Atoms objects are not modified."""
+        from newtonnet_amd import dynamics as _d
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('run_md: at least one structure expected')
+        n_frames, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('run_md: frames of different sizes cannot share one array; use model.dynamics (packed per molecule)')
+        if int(n_steps) != n_steps or n_steps < 0:
+            raise ValueError(f'n_steps: an integer >= 0 expected (got {n_steps!r})')
+        if int(record_every) != record_every or record_every < 0:
+            raise ValueError(f'record_every: an integer >= 0 expected (got {record_every!r})')
+        if not (float(timestep) > 0.0) or not (float(friction) >= 0.0):
+            raise ValueError(f'timestep > 0 fs and friction >= 0 per fs expected (got {timestep!r}, {friction!r})')
+        if float(friction) > 0.0 and temperature is None:
+            raise ValueError('friction > 0 (Langevin dynamics) needs a temperature')
+        _d._check_temperature(temperature, n_frames)
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: make the calculator with device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        masses = velocities = gen = None
+        if all(hasattr(a, 'get_masses') for a in atoms):
+            masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
+                                  dtype=torch.float32, device=pos.device)
+        if all(hasattr(a, 'get_momenta') for a in atoms):
+            p = np.concatenate([np.asarray(a.get_momenta(), dtype=np.float64).reshape(-1, 3) for a in atoms])
+            m = masses.cpu().double().numpy() if masses is not None else _d.table_masses(z.cpu()).double().numpy()
+            velocities = torch.tensor(p / m[:, None], dtype=torch.float32, device=pos.device)
+        if seed is not None:
+            gen = torch.Generator(device=pos.device)
+            gen.manual_seed(int(seed))
+        if isinstance(temperature, (list, tuple, np.ndarray)):
+            temperature = torch.tensor(np.asarray(temperature, dtype=np.float64), dtype=torch.float32, device=pos.device)
+        dyn = self.model.dynamics(z, pos.float(), cell.float(), batch, masses=masses, velocities=velocities, temperature=temperature,
+                                  friction=friction, timestep=timestep, generator=gen)
+        traj = dyn.run(int(n_steps), int(record_every))
+        R = traj.step.numel()
+        out = dict(positions=traj.pos.cpu().numpy().reshape(R, n_frames, n_atoms, 3),
+                   velocities=traj.vel.cpu().numpy().reshape(R, n_frames, n_atoms, 3),
+                   energy=traj.potential_energy.cpu().numpy(), kinetic_energy=traj.kinetic_energy.cpu().numpy(),
+                   step=traj.step.cpu().numpy())
+        if n_frames == 1:
+            for k in ('positions', 'velocities', 'energy', 'kinetic_energy'):
+                out[k] = out[k][:, 0]
+        return out
+
     # ------------------------------------------------------------------ MD-loop latency path (SURVEY 8f rank 2)
     def _calculate_md(self, atoms):
         """One structure per call, called thousands of times by an MD driver (simulate.py:21-30): keep everything that does
