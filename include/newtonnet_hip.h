@@ -914,6 +914,52 @@ int nnhip_md_step(const float* pos_in, float* vel, const float* force, const flo
 int nnhip_md_kinetic(const float* ke, const int32_t* mol_ptr, int32_t n_mol, float* out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Geometry relaxation on the device (csrc/relax.hip): ONE launch on `stream` moves every molecule of a batch by one L-BFGS step
+ * from the forces just evaluated.  L-BFGS without line search in ASE's convention (fixed H0 = 1 / alpha, the longest atomic
+ * displacement capped at maxstep); every molecule has its own history, one wave64 works on one molecule, every reduction is a
+ * lane-local sum / max in atom order and a fixed butterfly: no float atomics, a molecule's outputs are bitwise independent of the
+ * rest of the batch and of its place in it.  All arithmetic in fp32, every operation one rounding (tests/relax_ref.py restates it).
+ *
+ * State of molecule b (device arrays of the caller, zero before the first step; memory = m, 1 <= m <= NNHIP_LBFGS_MAX_MEMORY):
+ *   converged[b] (sticky), n_steps[b], n_pairs[b] (<= m), head[b] (the slot of the pending pair)      int32 [B] each
+ *   S, Y   fp32 [m][N][3], slot-major: displacements s and force differences y of the stored pairs
+ *   rho    fp32 [B][m] = 1 / (y.s) per slot;      f_prev  fp32 [N][3]: the (masked) forces of the previous step
+ * Per launch: pos_in, force [N,3]; free_mask uint8 [N] (0 = fixed atom) or NULL (all free); mol_ptr int32 [B+1] atom offsets;
+ * tol2 = fl32(fmax^2); alpha; maxstep; flags; work [N,3] scratch (the two-loop vector of molecules above 64 atoms; may be NULL when
+ * n_atoms <= 64); outputs pos_out [N,3] and fmax_out [B].
+ *
+ * One step for molecule b:
+ *   1. f_i = F_i for free atoms and exactly 0 for fixed ones.
+ *   2. fmax2 = max_i |f_i|^2;  fmax_out[b] = sqrt(fmax2).
+ *   3. Frozen when converged[b] is set, or fmax2 < tol2 (an empty molecule always), or flags has NNHIP_LBFGS_CHECK_ONLY:
+ *      converged[b] is set in the first two cases only, pos_out = pos_in bitwise, every other state word is left untouched.
+ *   4. Otherwise, when n_steps[b] > 0, the pending pair in slot `head` is completed:  y = f_prev - f,  s = S[head];  it is ACCEPTED
+ *      iff  y.s > 0  and  (y.s)^2 > NNHIP_LBFGS_CURVATURE_MIN^2 (y.y)(s.s)  -- then Y[head] = y, rho[head] = 1 / y.s,
+ *      n_pairs = min(n_pairs + 1, m), head = (head + 1) % m -- and otherwise the slot is reused; a rejection with n_pairs == m
+ *      sets n_pairs = m - 1, because the pending s had taken the place of the oldest pair's in the ring.  This is a deviation from ASE,
+ *      which takes every pair: below cos(y, s) = 1e-4 the curvature along s is not distinguishable from the fp32 rounding of the
+ *      forces, and one pair with y.s <= 0 makes the inverse Hessian indefinite.
+ *   5. Two-loop recursion over the n_pairs newest pairs:  q = -f;  newest first  a_i = rho_i (s_i.q), q -= a_i y_i;  z = q / alpha;
+ *      oldest first  z += s_i (a_i - rho_i (y_i.z)).
+ *   6. p = -z;  longest = max_i |p_i|;  when longest >= maxstep:  p *= maxstep / longest.
+ *   7. pos_out = pos_in + p (a fixed atom keeps its bits);  S[head] = pos_out - pos_in, in fp32 on the stored values;  f_prev = f;
+ *      n_steps[b] += 1.
+ * pos_out may NOT overlap pos_in (NNHIP_E_INVALID, nothing is launched), for the reason given at nnhip_md_step.  NULL mandatory
+ * pointers, memory outside 1 .. NNHIP_LBFGS_MAX_MEMORY, unknown flag bits, tol2 < 0, alpha <= 0 or maxstep <= 0 (or NaN) are
+ * refused likewise.  n_mol == 0 is success without a launch; n_atoms == 0 marks every molecule converged.  A molecule whose state
+ * words are impossible (head outside 0 .. m-1, n_pairs outside 0 .. m, n_steps < 0, atom offsets outside 0 .. n_atoms) is not
+ * touched and gets fmax_out = NaN.
+ * Cost: a molecule of n atoms takes about 2 m ceil(n / 64) dependent sweeps of ONE wave -- a kernel for batches of molecules.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_LBFGS_CHECK_ONLY 1
+#define NNHIP_LBFGS_MAX_MEMORY 64
+#define NNHIP_LBFGS_CURVATURE_MIN 1e-4f
+int nnhip_lbfgs_step(const float* pos_in, const float* force, const uint8_t* free_mask, const int32_t* mol_ptr, int32_t n_mol,
+                     int32_t n_atoms, int32_t memory, float tol2, float alpha, float maxstep, int32_t flags, int32_t* converged,
+                     int32_t* n_steps, int32_t* n_pairs, int32_t* head, float* S, float* Y, float* rho, float* f_prev, float* work,
+                     float* pos_out, float* fmax_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

@@ -253,6 +253,8 @@ def lib():
     L.nnhip_md_step.restype = C.c_int
     L.nnhip_md_kinetic.argtypes = [vp, vp, i32, vp, vp]
     L.nnhip_md_kinetic.restype = C.c_int
+    L.nnhip_lbfgs_step.argtypes = [vp] * 4 + [i32, i32, i32, f32, f32, f32, i32] + [vp] * 12
+    L.nnhip_lbfgs_step.restype = C.c_int
     L.nnhip_weight_image_bytes.restype = sz
     L.nnhip_weight_images.argtypes = [vp, vp, i32, vp]
     L.nnhip_mse_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -301,7 +303,7 @@ EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_
                     'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute', 'nnhip_eig_blocks',
                     'nnhip_eig_max_dim', 'nnhip_mode_sample', 'nnhip_eig_large_max_dim', 'nnhip_eig_large_ws_bytes',
                     'nnhip_eig_blocks_large', 'nnhip_mode_sample_large_max_dim', 'nnhip_mode_sample_large', 'nnhip_md_step',
-                    'nnhip_md_kinetic')
+                    'nnhip_md_kinetic', 'nnhip_lbfgs_step')
 
 
 def _check(rc: int, what: str):
@@ -882,6 +884,51 @@ def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tens
         return out.zero_()
     _check(lib().nnhip_md_kinetic(_ptr(ke), _ptr(mol_ptr), B, _ptr(out), _stream(ke.device)), 'nnhip_md_kinetic')
     return out
+
+
+LBFGS_CHECK_ONLY = 1             # flag of nnhip_lbfgs_step
+LBFGS_MAX_MEMORY = 64
+LBFGS_CURVATURE_MIN = 1e-4       # a pair enters the history iff y.s > 0 and cos(y, s) > this (include/newtonnet_hip.h)
+
+
+def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.Tensor], mol_ptr: torch.Tensor, memory: int,
+               tol2: float, alpha: float, maxstep: float, flags: int, converged: torch.Tensor, n_steps: torch.Tensor,
+               n_pairs: torch.Tensor, head: torch.Tensor, S: torch.Tensor, Y: torch.Tensor, rho: torch.Tensor,
+               f_prev: torch.Tensor, work: Optional[torch.Tensor], pos_out: torch.Tensor, fmax_out: torch.Tensor):
+    """One launch of the L-BFGS step (nnhip_lbfgs_step, csrc/relax.hip; the contract is in include/newtonnet_hip.h) on the
+    current stream, for the B molecules mol_ptr (int32 [B+1]) delimits.  pos_in, force [N,3] are read; free: bool / uint8 [N]
+    (False = fixed atom) or None; the state (converged, n_steps, n_pairs, head int32 [B]; S, Y fp32 [memory,N,3]; rho fp32
+    [B,memory]; f_prev fp32 [N,3]) is updated in place, pos_out [N,3] and fmax_out [B] are written: all of these must be contiguous
+    tensors of exactly that type (a copy would take the result away).  work: fp32 [N,3] scratch, needed when N > 64.  pos_out may
+    not overlap pos_in."""
+    if mol_ptr.dtype != torch.int32 or not mol_ptr.is_contiguous() or mol_ptr.numel() < 1:
+        raise ValueError('mol_ptr: contiguous int32 [B+1] expected')
+    dev, B, m = mol_ptr.device, mol_ptr.numel() - 1, int(memory)
+    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
+        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
+    N = pos_out.shape[0]
+    for name, t, dtype, numel in (('converged', converged, torch.int32, B), ('n_steps', n_steps, torch.int32, B),
+                                  ('n_pairs', n_pairs, torch.int32, B), ('head', head, torch.int32, B),
+                                  ('S', S, torch.float32, m * N * 3), ('Y', Y, torch.float32, m * N * 3),
+                                  ('rho', rho, torch.float32, B * m), ('f_prev', f_prev, torch.float32, 3 * N),
+                                  ('work', work, torch.float32, 3 * N), ('pos_out', pos_out, torch.float32, 3 * N),
+                                  ('fmax_out', fmax_out, torch.float32, B)):
+        if t is None and name == 'work':
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != max(numel, 0) or t.device != dev:
+            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
+    pos_in, force = _f32c(pos_in, 'pos_in'), _f32c(force, 'force')
+    if free is not None:
+        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
+            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
+        free = free.contiguous()
+    for name, t in (('pos_in', pos_in), ('force', force)):
+        if t.numel() != 3 * N or t.device != dev:
+            raise ValueError(f'{name}: {3 * N} values on {dev} expected (got {t.numel()} on {t.device})')
+    _check(lib().nnhip_lbfgs_step(_ptr(pos_in), _ptr(force), _ptr(free), _ptr(mol_ptr), B, N, m, float(tol2), float(alpha),
+                                  float(maxstep), int(flags), _ptr(converged), _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S),
+                                  _ptr(Y), _ptr(rho), _ptr(f_prev), _ptr(work), _ptr(pos_out), _ptr(fmax_out), _stream(dev)),
+           'nnhip_lbfgs_step')
 
 
 def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:

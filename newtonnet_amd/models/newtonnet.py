@@ -783,6 +783,17 @@ class NewtonNet(nn.Module):
         from newtonnet_amd import dynamics as _d
         return _d.Dynamics(self, z, pos, cell, batch, **kw)
 
+    def relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
+        """Relaxation of every molecule of the batch to a minimum on the device: a newtonnet_amd.relax.Relaxation whose
+        run(max_steps, check_every, record_every) steps them together, one force evaluation and one L-BFGS launch (csrc/relax.hip)
+        per step, each molecule with its own history and convergence flag.  L-BFGS without line search in ASE's convention:
+        fmax (eV / Angstrom) is the convergence threshold on the largest atomic force, memory the pairs kept, maxstep (Angstrom) the
+        cap on the longest atomic displacement, 1 / alpha the initial inverse Hessian; fixed: bool [N], atoms that never move.
+        Eval mode only; needs the 'energy' and 'gradient_force' heads.  The reference leaves optimisation to an outside driver,
+        one structure and one calculator call per step."""
+        from newtonnet_amd import relax as _r
+        return _r.Relaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, fixed=fixed)
+
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated
         (trainer.py:301-313): newtonnet_amd/train_fused.py, no torch autograd graph inside the step."""

@@ -1,0 +1,222 @@
+"""Batched geometry relaxation on the HIP path: every molecule of a batch is relaxed to a minimum on the device, one force
+evaluation and one optimiser launch (nnhip_lbfgs_step, csrc/relax.hip) per step, with no host round trip of positions or forces.
+
+The reference leaves optimisation to an outside driver that calls its calculator once per step for one structure.
+Here `Relaxation` owns the positions and the L-BFGS histories of B molecules as device tensors and steps them together.  The
+method is L-BFGS without line search in ASE's convention (ase.optimize.LBFGS: fixed H0 = 1 / alpha, the longest atomic displacement
+of a step capped at maxstep), every molecule with its own history and its own sticky `converged` flag.  One deviation from ASE,
+stated in include/newtonnet_hip.h: a curvature pair enters the history only when y.s > 0 and cos(y, s) > 1e-4.
+
+A molecule that has converged is frozen -- later launches leave every bit of it alone -- but model() keeps evaluating it with the
+rest of the batch: compacting the batch is not done here.  Minima only: no saddles, no Hessian-based steps, no cell relaxation, no
+constraint other than fixed atoms.  The launch gives one wave64 to a molecule, whatever its size: it is meant for batches of
+molecules, and one large system pays about 2 memory ceil(n / 64) dependent sweeps of a single wave per step.
+
+Units: positions in Angstrom, forces and fmax in eV / Angstrom, alpha in eV / Angstrom^2."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from newtonnet_amd import hip
+from newtonnet_amd.dynamics import _mol_ptr
+
+
+class RelaxResult:
+    """What Relaxation.run returns, as device tensors:
+
+    pos        fp32 [N,3]   positions after the last step
+    energy     fp32 [B]     the model's energy at pos;  fmax fp32 [B]: the largest force norm on a free atom at pos
+    converged  bool [B]     fmax < the threshold, now or at an earlier step (the flag is sticky);  n_steps int64 [B]: steps taken
+    traj_*     only with record_every > 0, over the R recorded steps: traj_step int64 [R] (steps since the Relaxation was made),
+               traj_pos and traj_force fp32 [R,N,3] (the forces are the ones the next launch consumed at those positions),
+               traj_energy fp32 [R,B], traj_n_pairs int64 [R,B] (pairs in each molecule's history after that step)
+    """
+
+    def __init__(self, pos, energy, fmax, converged, n_steps, traj=None):
+        self.pos, self.energy, self.fmax, self.converged, self.n_steps = pos, energy, fmax, converged, n_steps
+        self.traj_step = self.traj_pos = self.traj_force = self.traj_energy = self.traj_n_pairs = None
+        if traj is not None:
+            self.traj_step, self.traj_pos, self.traj_force, self.traj_energy, self.traj_n_pairs = traj
+
+
+def check_arguments(fmax, memory, maxstep, alpha):
+    """the optimiser's numbers, refused without touching the device; returns them as (float, int, float, float)"""
+    if int(memory) != memory or not 1 <= memory <= hip.LBFGS_MAX_MEMORY:
+        raise ValueError(f'memory: an integer in 1 .. {hip.LBFGS_MAX_MEMORY} expected (got {memory!r})')
+    fmax, maxstep, alpha = float(fmax), float(maxstep), float(alpha)
+    if not (fmax > 0.0 and math.isfinite(fmax)):
+        raise ValueError(f'fmax: a finite value > 0 eV/Angstrom expected (got {fmax!r})')
+    if not (maxstep > 0.0 and math.isfinite(maxstep)):
+        raise ValueError(f'maxstep: a finite value > 0 Angstrom expected (got {maxstep!r})')
+    if not (alpha > 0.0 and math.isfinite(alpha)):
+        raise ValueError(f'alpha: a finite value > 0 eV/Angstrom^2 expected (got {alpha!r})')
+    return fmax, int(memory), maxstep, alpha
+
+
+def check_run_arguments(max_steps, check_every, record_every):
+    for name, v in (('max_steps', max_steps), ('check_every', check_every), ('record_every', record_every)):
+        if int(v) != v or v < 0:
+            raise ValueError(f'{name}: an integer >= 0 expected (got {v!r})')
+    return int(max_steps), int(check_every), int(record_every)
+
+
+class Relaxation:
+    """B molecules relaxed together on the device.
+
+    model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads.  z, pos, cell, batch: as for model(...), on the
+    device; none of them is modified (the positions are copied).  fmax: a molecule has converged when the largest force norm on one
+    of its free atoms is below it (compared as squares in fp32: |f|^2 < fl32(fmax^2)).  memory: pairs kept per molecule.  maxstep:
+    cap on the longest atomic displacement of a step.  alpha: the initial inverse Hessian is 1 / alpha.  fixed: bool [N], atoms
+    that never move.
+
+    Periodic molecules: the cell is fixed and positions stay unwrapped; the model's neighbor list takes the minimum image itself."""
+
+    def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
+        # ---- everything that can be refused without touching the device
+        if getattr(model, 'training', False):
+            raise ValueError('Relaxation needs the model in eval mode: call model.eval()')
+        props = list(getattr(model, 'output_properties', []))
+        if 'energy' not in props or 'gradient_force' not in props:
+            raise ValueError(f"Relaxation needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
+        for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
+        N = pos.shape[0]
+        if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
+            raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
+        B = cell.shape[0]
+        if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
+            raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
+        if pos.dtype != torch.float32 or cell.dtype != torch.float32:
+            raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
+        if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
+            raise ValueError(f'fixed: a bool tensor [{N}] expected')
+        fmax, memory, maxstep, alpha = check_arguments(fmax, memory, maxstep, alpha)
+        if not pos.is_cuda:
+            raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: move the model and the inputs to '
+                               '"cuda"')
+        dev = pos.device
+        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('fixed', fixed)):
+            if t is not None and t.device != dev:
+                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        # ---- state
+        self.model, self.z, self.cell, self.batch = model, z, cell, batch
+        self.n_atoms, self.n_mol = N, B
+        self.fmax, self.memory = fmax, memory
+        # the numbers the kernel gets, as the Python floats of their fp32 values
+        self._tol2 = float(np.float32(fmax * fmax))
+        self._maxstep, self._alpha = float(np.float32(maxstep)), float(np.float32(alpha))
+        self.step_count = 0
+        with torch.no_grad():
+            self._free = None if fixed is None else (~fixed).contiguous()
+            # two position buffers: a step reads one and writes the other, so the forward call queued on the one it read can still
+            # be repeated from it (NewtonNet._forward_deferred)
+            self._pos = [pos.detach().clone().contiguous(), torch.empty(N, 3, dtype=torch.float32, device=dev)]
+            self._cur = 0
+            self._mol_ptr = _mol_ptr(batch, B)
+
+            def ints():
+                return torch.zeros(B, dtype=torch.int32, device=dev)
+            self._converged, self._n_steps, self._n_pairs, self._head = ints(), ints(), ints(), ints()
+            self._S = torch.zeros(memory, N, 3, dtype=torch.float32, device=dev)
+            self._Y = torch.zeros(memory, N, 3, dtype=torch.float32, device=dev)
+            self._rho = torch.zeros(B, memory, dtype=torch.float32, device=dev)
+            self._f_prev = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+            self._work = torch.empty(N, 3, dtype=torch.float32, device=dev) if N > 64 else None
+            self._fmax = torch.zeros(B, dtype=torch.float32, device=dev)
+            self._force = self._energy = None
+
+    # ------------------------------------------------------------------------------------------
+    def _evaluate(self):
+        """forces and energies at the current positions.  Touching gradient_force settles the deferred record of the call -- a
+        repeat, if one is needed, happens HERE, from the buffer the call was queued with and before any kernel writes a buffer"""
+        out = self.model(self.z, self._pos[self._cur], self.cell, self.batch)
+        self._force = out.gradient_force
+        self._energy = out.energy
+
+    def _launch(self, flags=0):
+        """one launch: reads the current buffer and the current forces, writes the other buffer, and the buffers swap"""
+        other = 1 - self._cur
+        hip.lbfgs_step(self._pos[self._cur], self._force, self._free, self._mol_ptr, self.memory, self._tol2, self._alpha,
+                       self._maxstep, flags, self._converged, self._n_steps, self._n_pairs, self._head, self._S, self._Y, self._rho,
+                       self._f_prev, self._work, self._pos[other], self._fmax)
+        self._cur = other
+
+    def _ensure_state(self):
+        if self._force is None:
+            with torch.no_grad():
+                self._evaluate()
+
+    @property
+    def positions(self):
+        return self._pos[self._cur].detach().clone()
+
+    @property
+    def forces(self):
+        self._ensure_state()
+        return self._force
+
+    @property
+    def potential_energy(self):
+        self._ensure_state()
+        return self._energy
+
+    @property
+    def n_steps(self):
+        return self._n_steps.long()
+
+    @property
+    def n_pairs(self):
+        return self._n_pairs.long()
+
+    # ------------------------------------------------------------------------------------------
+    def run(self, max_steps: int, check_every: int = 10, record_every: int = 0) -> RelaxResult:
+        """Up to max_steps L-BFGS steps of every molecule that has not converged, then the result at the positions reached.
+        Every check_every steps the host reads ONE number, the count of molecules that have not converged, and stops when it is 0
+        (check_every = 0: never reads, always max_steps launches).  A converged molecule is frozen bit for bit, so check_every
+        changes no bit of any result.  record_every > 0 records the steps record_every, 2 record_every, ... of this call that were
+        taken, and the last one.  May be called again to continue: run(a); run(b) leaves the bits of run(a + b)."""
+        max_steps, check_every, every = check_run_arguments(max_steps, check_every, record_every)
+        B, dev = self.n_mol, self._fmax.device
+        frames = []
+        with torch.no_grad():
+            self._ensure_state()
+            taken = 0
+            for k in range(1, max_steps + 1):
+                self._launch()
+                self._evaluate()
+                taken = k
+                if every and k % every == 0:
+                    frames.append(self._frame(k))
+                if check_every and k % check_every == 0 and int((self._converged == 0).sum()) == 0:
+                    break
+            if every and taken and (not frames or frames[-1][0] != self.step_count + taken):
+                frames.append(self._frame(taken))
+            self.step_count += taken
+            # the state at the positions reached: their forces are evaluated already; a check-only launch measures fmax and
+            # marks what has converged there, and moves nothing (it copies the positions into the other buffer)
+            self._launch(hip.LBFGS_CHECK_ONLY)
+            result = RelaxResult(self._pos[self._cur].clone(), self._energy.clone(), self._fmax.clone(), self._converged != 0,
+                                 self._n_steps.long())
+            if every:
+                if frames:
+                    result.traj_step = torch.tensor([f[0] for f in frames], dtype=torch.int64, device=dev)
+                    result.traj_pos, result.traj_force, result.traj_energy, result.traj_n_pairs = (
+                        torch.stack([f[j] for f in frames]) for j in (1, 2, 3, 4))
+                else:
+                    N = self.n_atoms
+                    result.traj_step = torch.zeros(0, dtype=torch.int64, device=dev)
+                    result.traj_pos = torch.zeros(0, N, 3, dtype=torch.float32, device=dev)
+                    result.traj_force = torch.zeros(0, N, 3, dtype=torch.float32, device=dev)
+                    result.traj_energy = torch.zeros(0, B, dtype=torch.float32, device=dev)
+                    result.traj_n_pairs = torch.zeros(0, B, dtype=torch.int64, device=dev)
+        return result
+
+    def _frame(self, k):
+        return (self.step_count + k, self._pos[self._cur].clone(), self._force.clone(), self._energy.clone(), self._n_pairs.long())

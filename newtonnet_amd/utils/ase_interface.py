@@ -223,6 +223,39 @@ class MLAseCalculator(_Base):
                 out[k] = out[k][:, 0]
         return out
 
+    def relax(self, atoms_or_list, fmax: float = 0.01, max_steps: int = 500, memory: int = 16, maxstep: float = 0.2,
+              alpha: float = 70.0, check_every: int = 10, fixed=None):
+        """Relax one structure or a list of equally sized ones to a minimum, all stepped together on the device
+        (NewtonNet.relaxation): L-BFGS without line search in ase.optimize.LBFGS's convention, until the largest atomic force of a
+        structure is below fmax (eV / Angstrom) or max_steps steps have been taken.  fixed: bool array [n_atoms], the same atoms
+        held in every structure.  Returns a dict of numpy arrays: positions [n_frames, n_atoms, 3], energy, fmax, converged,
+        n_steps [n_frames]; one structure drops the frame axis.  The Atoms objects are not modified."""
+        from newtonnet_amd import relax as _r
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('relax: at least one structure expected')
+        n_frames, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('relax: frames of different sizes cannot share one array; use model.relaxation (packed per molecule)')
+        _r.check_arguments(fmax, memory, maxstep, alpha)
+        _r.check_run_arguments(max_steps, check_every, 0)
+        if fixed is not None:
+            fixed = np.asarray(fixed)
+            if fixed.dtype != np.bool_ or fixed.shape != (n_atoms,):
+                raise ValueError(f'fixed: a bool array [{n_atoms}] expected')
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: make the calculator with device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        held = None if fixed is None else torch.from_numpy(np.tile(fixed, n_frames)).to(pos.device)
+        rel = self.model.relaxation(z, pos.float(), cell.float(), batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha,
+                                    fixed=held)
+        res = rel.run(int(max_steps), int(check_every))
+        out = dict(positions=res.pos.cpu().numpy().reshape(n_frames, n_atoms, 3), energy=res.energy.cpu().numpy(),
+                   fmax=res.fmax.cpu().numpy(), converged=res.converged.cpu().numpy(), n_steps=res.n_steps.cpu().numpy())
+        if n_frames == 1:
+            out = {k: v[0] for k, v in out.items()}
+        return out
+
     # ------------------------------------------------------------------ MD-loop latency path (SURVEY 8f rank 2)
     def _calculate_md(self, atoms):
         """One structure per call, called thousands of times by an MD driver (simulate.py:21-30): keep everything that does
