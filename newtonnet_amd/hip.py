@@ -2,7 +2,9 @@
 
 PyTorch is plumbing here: it owns device memory and the stream; every kernel is
 in the shared library.  There is no fallback: if the library is missing or a
-call fails, this module raises.
+call fails, this module raises.  The structs, the constants and every function's
+argtypes / restype are derived from the header (newtonnet_amd/abi.py); the wrappers
+below add validation and tensor plumbing.
 """
 from __future__ import annotations
 
@@ -13,107 +15,30 @@ from typing import Optional
 
 import torch
 
+from . import abi
+from .abi import HipLibraryError  # noqa: F401  (raised here and by every caller as hip.HipLibraryError)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', os.environ.get('NNHIP_LIB_NAME', 'libnewtonnet_hip.so'))  # env: tooling only
 BUILD_SCRIPT = os.path.join(_HERE, 'csrc', 'build.sh')
 
-NNHIP_F = 128
-NNHIP_NB = 20
-NNHIP_MAX_NB = 32
+_K = abi.CONSTANTS
+NNHIP_F, NNHIP_NB, NNHIP_MAX_NB, NNHIP_MAX_LAYERS = _K['NNHIP_F'], _K['NNHIP_NB'], _K['NNHIP_MAX_NB'], _K['NNHIP_MAX_LAYERS']
 # activation ids of include/newtonnet_hip.h, keyed by the reference's factory names (activations.py:5-30)
-ACTIVATION_IDS = {'swish': 0, 'silu': 0, 'relu': 1, 'elu': 2, 'leaky_relu': 3, 'tanh': 4, 'sigmoid': 5, 'softplus': 6,
-                  'gelu': 7, 'ssp': 8}
-NNHIP_MAX_LAYERS = 8
-N_TIMER_CLASSES = 14
+ACTIVATION_IDS = {name: _K['NNHIP_ACT_' + ('SILU' if name == 'swish' else name.upper())]
+                  for name in ('swish', 'silu', 'relu', 'elu', 'leaky_relu', 'tanh', 'sigmoid', 'softplus', 'gelu', 'ssp')}
+N_TIMER_CLASSES = _K['NNHIP_N_TIMER_CLASSES']
 TIMER_CLASSES = ('edge_all', 'linear_mfma', 'other', 'edge_msg_fwd', 'edge_force_fwd', 'edge_force_bwd',
                  'edge_msg_bwd', 'graph', 'mlp128', 'lin128', 'wgrad', 'mlp_onepass', 'mol_fwd', 'mol_bwd')
 
-_fp = C.POINTER(C.c_float)
-
-
-class LayerParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ('node0_w', 'node0_b', 'node2_w', 'node2_b', 'edge_w', 'eq1_0_w', 'eq1_2_w',
-                                         'eq2_0_w', 'eq2_2_w', 'update_w', 'ln_w', 'ln_b')]
-
-
-class Model(C.Structure):
-    _fields_ = [('n_features', C.c_int32), ('n_basis', C.c_int32), ('n_layers', C.c_int32), ('cutoff', C.c_float),
-                ('node_embedding', C.c_void_p), ('frequencies', C.c_void_p),
-                ('layer', LayerParams * NNHIP_MAX_LAYERS),
-                ('head0_w', C.c_void_p), ('head0_b', C.c_void_p), ('head2_w', C.c_void_p), ('head2_b', C.c_void_p),
-                ('head4_w', C.c_void_p), ('head4_b', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
-                ('activation', C.c_int32), ('envelope', C.c_int32)]
-
-
-class WsLayout(C.Structure):
-    _fields_ = ([(n, C.c_size_t * NNHIP_MAX_LAYERS) for n in ('m', 'hn', 'msg', 'h12', 'phi1', 'phi2', 'a_mid', 'a_out',
-                                                               'f_out', 'q')]
-                + [(n, C.c_size_t) for n in ('a0', 'e1', 'e2', 'g_x', 'g_u', 'g_a', 'g_f', 'total')])
-
-
-class MlpDesc(C.Structure):
-    """nnhip_mlp_desc (include/newtonnet_hip.h)."""
-    _fields_ = [('X', C.c_void_p), ('ldx', C.c_int32), ('W1', C.c_void_p), ('W2', C.c_void_p), ('b1', C.c_void_p),
-                ('b2', C.c_void_p), ('H', C.c_void_p), ('ldh', C.c_int32), ('Y', C.c_void_p), ('ldy', C.c_int32),
-                ('M', C.c_int32), ('mode', C.c_int32), ('accumulate', C.c_int32), ('activation', C.c_int32),
-                ('T', C.c_void_p), ('T2', C.c_void_p), ('Hd', C.c_void_p), ('G', C.c_void_p),
-                ('W1_image', C.c_void_p), ('W2_image', C.c_void_p), ('precision', C.c_int32), ('pad_', C.c_int32)]
-
-
-class WgradProblem(C.Structure):
-    """nnhip_wgrad_problem."""
-    _fields_ = [(n, C.c_void_p) for n in ('A1', 'B1', 'A2', 'B2', 'hA', 'hB', 'dhB', 'out')] + \
-               [(n, C.c_int32) for n in ('M', 'lda1', 'lda2', 'ldb1', 'ldb2', 'ldh', 'type', 'b_cols32', 'activation', 'ldo',
-                                         'ncols', 'pad_')]
-
-
-class ColsumProblem(C.Structure):
-    """nnhip_colsum_problem."""
-    _fields_ = [('src', C.c_void_p), ('out', C.c_void_p), ('rows', C.c_int32), ('pad_', C.c_int32)]
-
-
-def _train_ws_fields():
-    L, vp, i32 = NNHIP_MAX_LAYERS, C.c_void_p, C.c_int32
-    one = lambda *names: [(n, vp) for n in names]            # noqa: E731
-    per = lambda *names: [(n, vp * L) for n in names]        # noqa: E731
-    return ([(n, i32) for n in ('n_atoms', 'n_edges', 'n_mol', 'n_layers', 'n_basis', 'envelope', 'bf16_wgrad', 'flags')]
-            + one('z', 'pos', 'cell', 'batch', 'mol_ptr', 'row_ptr', 'col', 'rev', 'pid', 'edge_index', 'geo', 'disp', 'rbf',
-                  'drbf', 'xg')
-            + [('wT', (vp * 7) * L), ('headT', vp * 2)] + per('ftab') + [('wimg', (vp * 14) * L), ('himg', vp * 4)]
-            + one('a0') + per('hn', 'm', 'msg', 'h1', 'h2', 'phi1', 'phi2', 'a_mid', 'a_out', 'f_out', 'q')
-            + one('e1', 'e2', 'g_e2', 'atom_energy', 'energy', 'forces')
-            + one('t_e1') + per('GA', 'gf') + [('Gf', vp * 2)] + per('g_h12', 't1', 't2', 'g_msg', 'g_m', 't_n')
-            + one('g_x', 'g_u', 'g_d')
-            + one('tgeo', 'da_mid') + per('da_out', 'dhn', 'dm', 'dmsg', 'dh1', 'dh2', 'dphi1', 'dphi2', 'df_out', 'dq')
-            + one('de1', 'de2')
-            + one('dg_e2', 'w4row', 'scal', 'dg_e1', 'dGA', 'dgf') + [('dGf', vp * 2)]
-            + per('gq', 'dgq', 'dg_h12', 'dg_h1', 'dg_h2') + one('dg_msg') + per('g_eps', 'dg_eps', 'dg_m', 'dg_hn')
-            + one('rb', 'zeros_nf')
-            + one('probs', 'sums', 'slabs', 'cs_scratch', 'sp_scratch')
-            + [(n, i32) for n in ('n_probs', 'chunks', 'n_sums', 'pad2_')]
-            + one('g_embedding', 'g_scale', 'g_shift', 'g_head4_b')
-            + per('ln_xhat', 'ln_rstd', 'ln_dxhat', 'ln_drstd', 'ln_gy', 'ln_row_w', 'ln_row_b')
-            + one('pair_ptr'))
-
-
-class TrainWs(C.Structure):
-    """nnhip_train_ws: device pointers of one training step (newtonnet_amd/train_fused.py:TrainWorkspace fills it)."""
-    _fields_ = _train_ws_fields()
-
-
-class HvpWs(C.Structure):
-    """nnhip_hvp_ws: the extra buffers of the Hessian-vector products (newtonnet_amd/hessian.py fills it)."""
-    _fields_ = [(n, C.c_void_p) for n in ('dg_x', 'dg_u', 'dg_d', 'v', 'hv', 'zeros_b', 'blk_ptr')] + \
-               [('n_rep', C.c_int32), ('n_mol0', C.c_int32)]
-
+# the structs of the header (generated: abi.parse): every pointer member is a c_void_p, callers assign data_ptr() integers
+(LayerParams, Model, WsLayout, StepLayout, StepDev, MlpDesc, WgradProblem, ColsumProblem, TrainWs, HvpWs) = (
+    abi.STRUCTS['nnhip_' + name] for name in ('layer_params', 'model', 'ws_layout', 'step_layout', 'step_dev', 'mlp_desc',
+                                              'wgrad_problem', 'colsum_problem', 'train_ws', 'hvp_ws'))
 
 MODE_FWD, MODE_BWD, MODE_TAN, MODE_TAN2 = 0, 1, 2, 3
-LOSS_MODES = {'mse': 0, 'mae': 1, 'huber': 2}          # newtonnet/train/loss.py:53-103
+LOSS_MODES = {name: _K['NNHIP_LOSS_' + name.upper()] for name in ('mse', 'mae', 'huber')}   # newtonnet/train/loss.py:53-103
 WG_PLAIN, WG_ACT, WG_TDACT = 0, 1, 2
-
-
-class HipLibraryError(RuntimeError):
-    pass
 
 
 _lib = None
@@ -140,170 +65,17 @@ def lib():
             f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
             f'or `bash {BUILD_SCRIPT}`.  newtonnet_amd has no CPU fallback.')
     L = C.CDLL(LIB_PATH)
-    vp, i32, f32, sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
-    L.nnhip_version.restype = C.c_int
-    L.nnhip_build_flags.restype = C.c_int
+    abi.bind(L, ('nnhip_version', 'nnhip_build_flags'))
     if L.nnhip_build_flags() & 1 and os.environ.get('NNHIP_ALLOW_TOOLING_LIB') != '1':
         raise HipLibraryError(f'{LIB_PATH} is a TOOLING build (compiled with extra flags such as an ablation switch: its results '
                               'may be wrong).  Rebuild with `bash newtonnet_amd/csrc/build.sh --force`, or set '
                               'NNHIP_ALLOW_TOOLING_LIB=1 for measurements.')
-    L.nnhip_last_error.restype = C.c_char_p
-    L.nnhip_graph_count.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
-    L.nnhip_graph_fill.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
-    L.nnhip_graph_count_pairs.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]
-    L.nnhip_graph_pair_scan.argtypes = [vp, i32, vp, vp]
-    L.nnhip_graph_count_cells_pairs.argtypes = [vp, vp, i32, f32, _fp, vp, vp, vp, vp, vp]
-    L.nnhip_graph_finish_cells.argtypes = [vp, vp, i32, i32, f32, _fp] + [vp] * 9 + [i32, vp, vp, vp, vp, i32, vp]
-    L.nnhip_graph_finish.argtypes = [vp] * 6 + [i32, i32, i32, f32] + [vp] * 6 + [i32, vp, vp, vp, vp, i32, vp]
-    L.nnhip_graph_finish_early.argtypes = L.nnhip_graph_finish.argtypes
-    L.nnhip_graph_finish_dev.argtypes = L.nnhip_graph_finish.argtypes[:-1] + [vp, vp, vp, i32, vp]
-    L.nnhip_energy_forces_dev.argtypes = [C.POINTER(Model), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz,
-                                          vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.nnhip_mlp_forms.restype = C.c_int
-    L.nnhip_step_layout_of.argtypes = [i32, i32, i32, vp]
-    L.nnhip_step_layout_of.restype = C.c_int
-    L.nnhip_forward_dev.argtypes = [C.POINTER(Model), vp, vp]
-    L.nnhip_forward_dev.restype = C.c_int
-    L.nnhip_edge_embed.argtypes = [vp, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp]
-    L.nnhip_edge_disp.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-    L.nnhip_edge_refresh.argtypes = [vp, vp, vp, vp, i32, f32, vp, i32, vp, vp, vp, vp, vp, i32, vp]
-    L.nnhip_check_species.argtypes = [vp, i32, vp, vp]
-    L.nnhip_graph_cells_scratch_bytes.argtypes = [i32, _fp, f32]
-    L.nnhip_graph_cells_scratch_bytes.restype = sz
-    L.nnhip_graph_count_cells.argtypes = [vp, vp, i32, f32, _fp, vp, vp, vp, vp]
-    L.nnhip_graph_fill_cells.argtypes = [vp, vp, i32, i32, f32, _fp, vp, vp, vp, vp, vp, vp, vp]
-    L.nnhip_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.nnhip_workspace_bytes.restype = sz
-    L.nnhip_workspace_layout.argtypes = [i32, i32, i32, i32, C.POINTER(WsLayout)]
-    L.nnhip_graph_pairs.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.nnhip_energy_forces.argtypes = [C.POINTER(Model), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz,
-                                      vp, vp, vp, vp, vp, vp, vp, vp]
-    L.nnhip_energy_forces_pp.argtypes = L.nnhip_energy_forces.argtypes[:-1] + [vp, i32, vp]
-    L.nnhip_energy_forces_pp.restype = C.c_int
-    L.nnhip_edge_index_from_csr.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    L.nnhip_prepared_bytes.argtypes = [i32]
-    L.nnhip_prepared_bytes.restype = sz
-    L.nnhip_prepare.argtypes = [C.POINTER(Model), vp, sz, vp]
-    L.nnhip_prepare_check.argtypes = [C.POINTER(Model), vp, sz, vp, i32, vp]
-    L.nnhip_linear128.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]
-    L.nnhip_mlp128.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]
-    L.nnhip_direct_force.argtypes = [vp] * 10 + [i32, i32, vp, vp, vp]
-    L.nnhip_segment_sum.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.nnhip_gather_rows.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.nnhip_timers_enable.argtypes = [i32]
-    L.nnhip_timers_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
-    # per-stage entry points and training kernels
-    pp = C.POINTER(vp)
-    L.nnhip_embed.argtypes = [vp, vp, i32, vp, vp]
-    L.nnhip_filter_table_bytes.restype = sz
-    L.nnhip_filter_tables.argtypes = [pp, pp, i32, vp, i32, i32, vp]
-    L.nnhip_transpose128.argtypes = [pp, pp, i32, vp]
-    L.nnhip_message_fwd.argtypes = [vp] * 9 + [i32, vp]
-    L.nnhip_message_bwd.argtypes = [vp] * 10 + [i32, i32, vp]
-    L.nnhip_force_message_fwd.argtypes = [vp] * 9 + [i32, vp]
-    L.nnhip_force_message_bwd.argtypes = [vp] * 12 + [i32, vp]
-    L.nnhip_edge_embed_bwd.argtypes = [vp] * 10 + [i32, i32, i32, i32, f32, vp, vp, vp, vp]
-    L.nnhip_node_fwd.argtypes = [vp] * 11 + [i32, i32, vp]
-    L.nnhip_node_bwd.argtypes = [vp] * 5 + [i32] + [vp] * 5 + [i32, i32, vp]
-    L.nnhip_head_out.argtypes = [vp] * 7 + [i32, i32, i32, vp, vp, vp, vp]
-    L.nnhip_mlp128_ex.argtypes = [C.POINTER(MlpDesc), vp]
-    L.nnhip_mlp128_pair_ex.argtypes = [C.POINTER(MlpDesc), C.POINTER(MlpDesc), vp]
-    L.nnhip_edge_tangent_geom.argtypes = [vp, f32, vp, vp, i32, f32, vp, vp]
-    L.nnhip_message_tan_fwd.argtypes = [vp] * 11 + [i32, vp]
-    L.nnhip_force_message_tan_fwd.argtypes = [vp] * 13 + [i32, vp]
-    L.nnhip_force_message_tan_bwd.argtypes = [vp] * 14 + [i32, vp]
-    L.nnhip_message_tan_bwd.argtypes = [vp] * 15 + [i32, vp]
-    L.nnhip_update_tan_fwd.argtypes = [vp] * 5 + [i32, vp, vp]
-    L.nnhip_update_tan_bwd.argtypes = [vp] * 7 + [i32, vp, vp, vp, vp]
-    L.nnhip_head_seed_tan.argtypes = [vp] * 8 + [i32, i32, vp, vp, vp, vp]
-    L.nnhip_pair_rbf.argtypes = [vp] * 5 + [i32, i32, vp, vp]
-    L.nnhip_species_scratch_bytes.argtypes = [i32]
-    L.nnhip_species_scratch_bytes.restype = sz
-    L.nnhip_species_sum.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp]
-    L.nnhip_colsum_scratch_bytes.argtypes = [i32]
-    L.nnhip_colsum_scratch_bytes.restype = sz
-    L.nnhip_wgrad_slab_bytes.argtypes = [i32, i32]
-    L.nnhip_wgrad_slab_bytes.restype = sz
-    L.nnhip_wgrad_batch.argtypes = [vp, i32, i32, vp, i32, i32, vp]
-    L.nnhip_colsum_batch.argtypes = [vp, i32, vp, vp]
-    L.nnhip_train_values.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), vp]
-    L.nnhip_train_grads.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), vp, vp, vp]
-    L.nnhip_train_grads_seeded.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), vp, vp, vp, vp, vp]
-    L.nnhip_direct_force_bwd_work_floats.argtypes = [i32]
-    L.nnhip_direct_force_bwd_work_floats.restype = sz
-    L.nnhip_direct_force_bwd.argtypes = [vp] * 7 + [i32, i32] + [vp] * 8
-    L.nnhip_train_ws_bytes.restype = sz
-    L.nnhip_hvp_ws_bytes.restype = sz
-    L.nnhip_hessian_vp.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), C.POINTER(HvpWs), vp, vp, vp]
-    L.nnhip_hessian_blocks.argtypes = [C.POINTER(Model), C.POINTER(TrainWs), C.POINTER(HvpWs), i32, vp, vp]
-    L.nnhip_eig_max_dim.restype = C.c_int
-    L.nnhip_eig_blocks.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-    L.nnhip_eig_blocks.restype = C.c_int
-    L.nnhip_eig_large_max_dim.restype = C.c_int
-    L.nnhip_eig_large_ws_bytes.argtypes = [vp, i32, i32]
-    L.nnhip_eig_large_ws_bytes.restype = sz
-    L.nnhip_eig_blocks_large.argtypes = L.nnhip_eig_blocks.argtypes[:-1] + [vp, vp, sz, vp]
-    L.nnhip_eig_blocks_large.restype = C.c_int
-    L.nnhip_mode_sample.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.nnhip_mode_sample.restype = C.c_int
-    L.nnhip_mode_sample_large_max_dim.restype = C.c_int
-    L.nnhip_mode_sample_large.argtypes = L.nnhip_mode_sample.argtypes[:-1] + [i32, vp]
-    L.nnhip_mode_sample_large.restype = C.c_int
-    L.nnhip_md_step.argtypes = [vp] * 7 + [f32, f32, i32, i32, vp, vp, vp]
-    L.nnhip_md_step.restype = C.c_int
-    L.nnhip_md_kinetic.argtypes = [vp, vp, i32, vp, vp]
-    L.nnhip_md_kinetic.restype = C.c_int
-    L.nnhip_lbfgs_step.argtypes = [vp] * 4 + [i32, i32, i32, f32, f32, f32, i32] + [vp] * 12
-    L.nnhip_lbfgs_step.restype = C.c_int
-    L.nnhip_weight_image_bytes.restype = sz
-    L.nnhip_weight_images.argtypes = [vp, vp, i32, vp]
-    L.nnhip_mse_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.nnhip_loss_grad.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, i32, f32, f32, vp, vp, vp, vp]
-    L.nnhip_clip_adam_dev.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
-    L.nnhip_clip_adam_scratch_bytes.restype = sz
-    L.nnhip_clip_adam.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, f32, f32, f32, f32, f32, vp]
-    for fn in STAGE_SYMBOLS:
-        if fn not in ('nnhip_filter_table_bytes', 'nnhip_wgrad_slab_bytes', 'nnhip_species_scratch_bytes',
-                      'nnhip_colsum_scratch_bytes', 'nnhip_clip_adam_scratch_bytes', 'nnhip_train_ws_bytes',
-                      'nnhip_weight_image_bytes', 'nnhip_direct_force_bwd_work_floats', 'nnhip_hvp_ws_bytes'):
-            getattr(L, fn).restype = C.c_int
-    for fn in ('nnhip_graph_count', 'nnhip_graph_fill', 'nnhip_edge_embed', 'nnhip_workspace_layout',
-               'nnhip_energy_forces', 'nnhip_timers_enable', 'nnhip_timers_read', 'nnhip_linear128', 'nnhip_segment_sum', 'nnhip_gather_rows', 'nnhip_graph_count_cells',
-               'nnhip_graph_fill_cells', 'nnhip_mlp128', 'nnhip_graph_pairs', 'nnhip_direct_force', 'nnhip_edge_disp',
-               'nnhip_prepare', 'nnhip_prepare_check', 'nnhip_check_species', 'nnhip_graph_count_pairs', 'nnhip_graph_pair_scan', 'nnhip_graph_finish', 'nnhip_graph_finish_early', 'nnhip_edge_refresh', 'nnhip_graph_count_cells_pairs', 'nnhip_graph_finish_cells',
-               'nnhip_graph_finish_dev', 'nnhip_energy_forces_dev'):
-        getattr(L, fn).restype = C.c_int
+    abi.bind(L)
     _lib = L
     return L
 
 
-STAGE_SYMBOLS = ('nnhip_embed', 'nnhip_filter_table_bytes', 'nnhip_filter_tables', 'nnhip_transpose128', 'nnhip_message_fwd',
-                 'nnhip_message_bwd', 'nnhip_force_message_fwd', 'nnhip_force_message_bwd', 'nnhip_edge_embed_bwd',
-                 'nnhip_node_fwd', 'nnhip_node_bwd', 'nnhip_head_out', 'nnhip_mlp128_ex', 'nnhip_mlp128_pair_ex', 'nnhip_edge_tangent_geom',
-                 'nnhip_message_tan_fwd', 'nnhip_force_message_tan_fwd', 'nnhip_force_message_tan_bwd',
-                 'nnhip_message_tan_bwd', 'nnhip_update_tan_fwd', 'nnhip_update_tan_bwd', 'nnhip_head_seed_tan',
-                 'nnhip_pair_rbf', 'nnhip_species_sum', 'nnhip_species_scratch_bytes', 'nnhip_wgrad_slab_bytes',
-                 'nnhip_wgrad_batch', 'nnhip_colsum_batch', 'nnhip_colsum_scratch_bytes', 'nnhip_mse_loss_grad', 'nnhip_loss_grad',
-                 'nnhip_clip_adam', 'nnhip_clip_adam_dev', 'nnhip_clip_adam_scratch_bytes', 'nnhip_train_values', 'nnhip_train_grads',
-                 'nnhip_train_ws_bytes', 'nnhip_weight_image_bytes', 'nnhip_weight_images', 'nnhip_train_grads_seeded',
-                 'nnhip_direct_force_bwd', 'nnhip_direct_force_bwd_work_floats', 'nnhip_hvp_ws_bytes', 'nnhip_hessian_vp',
-                 'nnhip_hessian_blocks')
-
-EXPORTED_SYMBOLS = STAGE_SYMBOLS + ('nnhip_version', 'nnhip_last_error', 'nnhip_graph_count', 'nnhip_graph_fill', 'nnhip_edge_embed',
-                    'nnhip_workspace_bytes', 'nnhip_workspace_layout', 'nnhip_energy_forces', 'nnhip_timers_enable',
-                    'nnhip_timers_read', 'nnhip_linear128', 'nnhip_segment_sum', 'nnhip_gather_rows',
-                    'nnhip_graph_cells_scratch_bytes', 'nnhip_graph_count_cells', 'nnhip_graph_fill_cells',
-                    'nnhip_mlp128', 'nnhip_graph_pairs', 'nnhip_direct_force', 'nnhip_edge_disp', 'nnhip_prepared_bytes',
-                    'nnhip_prepare', 'nnhip_prepare_check', 'nnhip_check_species', 'nnhip_split_products', 'nnhip_build_flags', 'nnhip_graph_count_pairs',
-                    'nnhip_graph_pair_scan', 'nnhip_graph_finish', 'nnhip_graph_finish_early', 'nnhip_edge_refresh', 'nnhip_graph_count_cells_pairs',
-                    'nnhip_graph_finish_cells', 'nnhip_graph_finish_dev', 'nnhip_energy_forces_dev', 'nnhip_mlp_forms',
-                    'nnhip_step_layout_of', 'nnhip_forward_dev', 'nnhip_graph_small_dev', 'nnhip_graph_small_max_atoms',
-                    'nnhip_energy_forces_pp', 'nnhip_graph_count_pairs_z', 'nnhip_prepare_check_counter', 'nnhip_graph_mol_dev',
-                    'nnhip_edge_index_from_csr', 'nnhip_config', 'nnhip_weight_images_bf16', 'nnhip_bf16_mlp_launches',
-                    'nnhip_spatial_order_scratch_bytes', 'nnhip_spatial_order', 'nnhip_permute_rows', 'nnhip_edge_index_unpermute', 'nnhip_eig_blocks',
-                    'nnhip_eig_max_dim', 'nnhip_mode_sample', 'nnhip_eig_large_max_dim', 'nnhip_eig_large_ws_bytes',
-                    'nnhip_eig_blocks_large', 'nnhip_mode_sample_large_max_dim', 'nnhip_mode_sample_large', 'nnhip_md_step',
-                    'nnhip_md_kinetic', 'nnhip_lbfgs_step')
+EXPORTED_SYMBOLS = tuple(abi.FUNCTIONS)     # every entry point the header declares
 
 
 def _check(rc: int, what: str):
@@ -552,22 +324,6 @@ def refresh_graph(g: Graph, pos: torch.Tensor, cell: torch.Tensor, batch: torch.
     return g
 
 
-class StepLayout(C.Structure):
-    """nnhip_step_layout."""
-    _fields_ = [(n, C.c_size_t) for n in ('i32_count', 'f32_count', 'mol_ptr', 'row_ptr', 'status', 'pair_ptr', 'pair_scan',
-                                          'tail', 'mol_scratch', 'xg', 'col', 'rev', 'pid', 'geo', 'disp', 'energy', 'forces', 'virial',
-                                          'atom_energy')]
-
-
-class StepDev(C.Structure):
-    """nnhip_step_dev."""
-    _fields_ = ([(n, C.c_void_p) for n in ('z', 'pos', 'cell', 'batch')]
-                + [(n, C.c_int32) for n in ('n_atoms', 'n_mol', 'capacity', 'want_forces', 'want_virial', 'seq', 'flags', 'pad_')]
-                + [(n, C.c_void_p) for n in ('i32', 'f32', 'edge_index', 'atom_node', 'force_node', 'workspace')]
-                + [('workspace_bytes', C.c_size_t), ('prepared', C.c_void_p), ('prepared_bytes', C.c_size_t),
-                   ('tail_host', C.c_void_p), ('event', C.c_void_p)])
-
-
 _step_layouts = {}
 
 
@@ -672,9 +428,6 @@ def spatial_order(pos: torch.Tensor, z: torch.Tensor, cutoff: float):
     """(perm, inv, z_perm, pos_perm): the atoms of ONE big system in Morton order of cells (nnhip_spatial_order; int32 perm / inv on
     pos.device, no host round trip, deterministic: by cell, then by input index)."""
     L = lib()
-    L.nnhip_spatial_order_scratch_bytes.restype = C.c_size_t
-    L.nnhip_spatial_order_scratch_bytes.argtypes = [C.c_int32]
-    L.nnhip_spatial_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float] + [C.c_void_p] * 6
     pos = _f32c(pos, 'pos')
     N, dev = pos.shape[0], pos.device
     perm = torch.empty(N, dtype=torch.int32, device=dev)
@@ -689,7 +442,6 @@ def spatial_order(pos: torch.Tensor, z: torch.Tensor, cutoff: float):
 def permute_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[k] = x[idx[k]] over dim 0 (idx int32): the per-atom results of a permuted step in the caller's order."""
     L = lib()
-    L.nnhip_permute_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     x = _f32c(x, 'x')
     width = 1
     for d in x.shape[1:]:
@@ -702,7 +454,6 @@ def permute_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 def edge_index_unpermute(row_ptr, col, perm, inv, n_atoms: int, n_edges: int) -> torch.Tensor:
     """The [2][E] int64 neighbor list of a permuted step in the reference's order for the caller's atom order."""
     L = lib()
-    L.nnhip_edge_index_unpermute.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     dev = perm.device
     ei = torch.empty(2, n_edges, dtype=torch.int64, device=dev)
     scratch = torch.empty(n_atoms + 1 + n_atoms // 1024 + 2, dtype=torch.int32, device=dev)
@@ -713,9 +464,7 @@ def edge_index_unpermute(row_ptr, col, perm, inv, n_atoms: int, n_edges: int) ->
 
 def bf16_mlp_launches() -> int:
     """Edge-MLP launches that took the bf16 compute mode (training under torch.autocast(bfloat16)) since the library was loaded."""
-    L = lib()
-    L.nnhip_bf16_mlp_launches.restype = C.c_int64
-    return int(L.nnhip_bf16_mlp_launches())
+    return int(lib().nnhip_bf16_mlp_launches())
 
 
 def mlp_forms() -> dict:
@@ -729,8 +478,6 @@ def config() -> dict:
     """Every form choice the library makes in this process (nnhip_config), as a dict."""
     import json
     L = lib()
-    L.nnhip_config.argtypes = [C.c_char_p, C.c_size_t]
-    L.nnhip_config.restype = C.c_int
     buf = C.create_string_buffer(4096)
     _check(L.nnhip_config(buf, 4096), 'nnhip_config')
     return json.loads(buf.value.decode())
@@ -844,7 +591,7 @@ def segment_sum(x: torch.Tensor, row_ptr: torch.Tensor, n_rows: int) -> torch.Te
     return out
 
 
-MD_FINISH, MD_BEGIN = 1, 2      # flags of nnhip_md_step
+MD_FINISH, MD_BEGIN = _K['NNHIP_MD_FINISH'], _K['NNHIP_MD_BEGIN']      # flags of nnhip_md_step
 
 
 def md_step(pos_in: Optional[torch.Tensor], vel: torch.Tensor, force: torch.Tensor, hk: torch.Tensor, dth: float, c1: float,
@@ -886,8 +633,8 @@ def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tens
     return out
 
 
-LBFGS_CHECK_ONLY = 1             # flag of nnhip_lbfgs_step
-LBFGS_MAX_MEMORY = 64
+LBFGS_CHECK_ONLY = _K['NNHIP_LBFGS_CHECK_ONLY']             # flag of nnhip_lbfgs_step
+LBFGS_MAX_MEMORY = _K['NNHIP_LBFGS_MAX_MEMORY']
 LBFGS_CURVATURE_MIN = 1e-4       # a pair enters the history iff y.s > 0 and cos(y, s) > this (include/newtonnet_hip.h)
 
 

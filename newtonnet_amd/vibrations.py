@@ -37,6 +37,7 @@ K_BOLTZMANN = 8.617333262e-5
 EV_PER_SQRT_EIGENVALUE = EV_PER_WAVENUMBER * WAVENUMBER_PER_SQRT_EIGENVALUE
 
 EPS32 = 2.0 ** -24
+EIG_PROJECT = hip.abi.CONSTANTS['NNHIP_EIG_PROJECT']      # flag of nnhip_eig_blocks / nnhip_eig_blocks_large
 
 # Standard atomic weights (IUPAC abridged values, amu).  Only elements whose value is beyond doubt; pass masses= for the rest.
 STANDARD_ATOMIC_WEIGHTS = {
@@ -425,7 +426,7 @@ def eig_blocks(blocks: torch.Tensor, blk_ptr: torch.Tensor, batch: torch.Tensor,
     n_proj, sweeps, status = (torch.zeros(n_mol, dtype=torch.int32, device=dev) for _ in range(3))
     if n_mol and n_atoms and not any(large):
         rc = hip.lib().nnhip_eig_blocks(hip._ptr(blocks), hip._ptr(blk_ptr), hip._ptr(mol_dev), mol_host.data_ptr(), n_mol,
-                                        hip._ptr(pos_c), hip._ptr(cell_c), hip._ptr(m_c), 1 if project else 0, hip._ptr(evals),
+                                        hip._ptr(pos_c), hip._ptr(cell_c), hip._ptr(m_c), EIG_PROJECT if project else 0, hip._ptr(evals),
                                         hip._ptr(vecs), hip._ptr(n_proj), hip._ptr(sweeps), hip._ptr(status), hip._stream(dev))
         if rc == 2:
             raise NotImplementedError(hip.lib().nnhip_last_error().decode())
@@ -443,7 +444,7 @@ def _solve_mixed(blocks, blk_ptr, mol_dev, mol_host, cl, large, pos_c, cell_c, m
     """solver='auto' / 'blocked': nnhip_eig_blocks on every run of consecutive molecules the one-workgroup solver serves (it takes a
     batch as offsets into the packed arrays, so a run is the same call with the per-molecule pointers moved up), one
     nnhip_eig_blocks_large call on the others; both write the same packed outputs."""
-    L, dev, n_mol, flags = hip.lib(), blocks.device, len(cl), 1 if project else 0
+    L, dev, n_mol, flags = hip.lib(), blocks.device, len(cl), EIG_PROJECT if project else 0
     b = 0
     while b < n_mol:
         if large[b]:
