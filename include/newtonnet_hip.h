@@ -960,6 +960,59 @@ int nnhip_lbfgs_step(const float* pos_in, const float* force, const uint8_t* fre
                      float* pos_out, float* fmax_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Nudged elastic band on the device (csrc/neb.hip): ONE launch on `stream` moves every band of a batch by one FIRE step on its NEB
+ * forces, from the forces and energies just evaluated.  Improved tangent (Henkelman and Jonsson 2000), one spring constant,
+ * climbing image (Henkelman, Uberuaga and Jonsson 2000), FIRE as ase.optimize.FIRE states it (mass 1, one step length per band).
+ * One workgroup per band, its images dealt to the waves; per-image sums are lane-local in atom order plus a fixed butterfly, band
+ * sums go through one LDS slot per image and are added in image order: no float atomics, a band's outputs are bitwise independent
+ * of the rest of the batch and of its place in it.  All arithmetic in fp32, every operation one rounding (tests/neb_ref.py).
+ *
+ * Layout: band k owns the consecutive molecules band_ptr[k] .. band_ptr[k+1] - 1, its images in path order (int32 [K+1], on the
+ * device; band_ptr_host is the same array in host memory, for the checks below); mol_ptr int32 [B+1] gives each image's atoms.  All
+ * images of a band have the same atom count; bands may differ in atom count and in image count (3 .. NNHIP_NEB_MAX_IMAGES).  The
+ * first and the last image of a band are endpoints and never move.
+ * State of band k (device arrays of the caller, zero before the first step):  converged[k], climbing[k] (both sticky), n_steps[k],
+ * n_pos[k]  int32 [K] each;  dt[k], a[k]  fp32 [K] (set from dt_start / a_start in the band's first step);  vel fp32 [N][3].
+ * Per launch: pos_in, force [N,3]; energy [B]; free_mask uint8 [N] (0 = fixed atom) or NULL; spring (eV/A^2); tol2 = fl32(fmax^2);
+ * climb2 = fl32(climb_below^2); the FIRE constants dt_start, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep (ASE: 0.1, 1.0, 5,
+ * 1.1, 0.5, 0.1, 0.99, 0.2); flags.  Outputs: pos_out, neb_force_out, tangent_out [N,3]; fmax_out [K]; saddle_out int32 [K].
+ *
+ * One launch for band k (f = force of free atoms, exactly 0 for fixed ones; a fixed atom is in no sum and never moves):
+ *   1. Tangent of interior image i:  t+ = R_{i+1} - R_i,  t- = R_i - R_{i-1}  (fp32 differences of the stored positions, no minimum
+ *      image).  E_{i+1} > E_i > E_{i-1}: tau = t+;  E_{i+1} < E_i < E_{i-1}: tau = t-;  otherwise, with a = max(|E_{i+1} - E_i|,
+ *      |E_{i-1} - E_i|) and b the min:  tau = a t+ + b t-  if E_{i+1} > E_{i-1}, else  b t+ + a t-.  that = tau / |tau| (0 when
+ *      tau.tau == 0: the image gets its plain force).  tangent_out = that (endpoints: 0).
+ *   2. NEB force  F_i = f_i - (f_i.that) that + spring (|t+| - |t-|) that.  The climbing image is the interior image of highest
+ *      energy, the lowest index at a tie; saddle_out[k] = its molecule index.  When climbing[k] was set BEFORE the launch it gets
+ *      F = f - 2 (f.that) that instead.  neb_force_out = F (endpoints: 0).  fmax_out[k] = sqrt(fmax2), fmax2 = max |F|^2 over the
+ *      free atoms of the interior images.
+ *   3. Flags (never with NNHIP_NEB_CHECK_ONLY, never for a band converged before):  with NNHIP_NEB_CLIMB, climbing[k] is set when
+ *      fmax2 < climb2 and takes effect from the next launch;  converged[k] is set when fmax2 < tol2 and either NNHIP_NEB_CLIMB is
+ *      absent or climbing[k] was set before this launch.
+ *   4. Frozen when converged before, converging now, or NNHIP_NEB_CHECK_ONLY:  pos_out = pos_in bitwise; vel, dt, a, n_pos, n_steps
+ *      untouched.
+ *   5. Otherwise one FIRE step over the whole band.  First step (n_steps == 0): v = 0, dt = dt_start, a = a_start, n_pos = 0 and P
+ *      is not tested.  Else P = sum F.v;  P > 0:  v = (1 - a) v + a |v| F / |F|, then if n_pos > n_min: dt = min(dt f_inc, dt_max),
+ *      a = a f_a;  n_pos += 1.   P <= 0:  v = 0, a = a_start, dt = dt f_dec, n_pos = 0.   Then v += dt F;  dr = dt v;  if |dr| over
+ *      the band > maxstep:  dr *= maxstep / |dr|;  pos_out = pos_in + dr (endpoints and fixed atoms: pos_in bitwise); n_steps += 1.
+ * The energies enter only comparisons and differences of neighbouring images, so their absolute size costs no precision here.
+ * A band whose images differ in atom count, whose offsets leave the arrays or whose state words no step can have left behind
+ * (n_steps < 0; after the first step n_pos < 0, dt <= 0 or a <= 0, or NaN) is not touched and gets fmax_out = NaN.
+ * NNHIP_E_INVALID, nothing launched: pos_out overlapping pos_in (the reason is given at nnhip_md_step), NULL mandatory pointers,
+ * unknown flag bits, a band of fewer than 3 or more than NNHIP_NEB_MAX_IMAGES images (from band_ptr_host, which must run from 0 to
+ * n_mol), n_min < 0, any other parameter <= 0 or NaN.  n_bands == 0 is success without a launch.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_NEB_CHECK_ONLY 1
+#define NNHIP_NEB_CLIMB 2
+#define NNHIP_NEB_MAX_IMAGES 64
+int nnhip_neb_step(const float* pos_in, const float* force, const float* energy, const uint8_t* free_mask, const int32_t* mol_ptr,
+                   const int32_t* band_ptr, const int32_t* band_ptr_host, int32_t n_bands, int32_t n_mol, int32_t n_atoms,
+                   float spring, float tol2, float climb2, float dt_start, float dt_max, int32_t n_min, float f_inc, float f_dec,
+                   float a_start, float f_a, float maxstep, int32_t flags, int32_t* converged, int32_t* climbing, int32_t* n_steps,
+                   int32_t* n_pos, float* dt, float* a, float* vel, float* pos_out, float* neb_force_out, float* tangent_out,
+                   float* fmax_out, int32_t* saddle_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

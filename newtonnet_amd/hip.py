@@ -678,6 +678,58 @@ def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.T
            'nnhip_lbfgs_step')
 
 
+NEB_CHECK_ONLY, NEB_CLIMB = _K['NNHIP_NEB_CHECK_ONLY'], _K['NNHIP_NEB_CLIMB']      # flags of nnhip_neb_step
+NEB_MAX_IMAGES = _K['NNHIP_NEB_MAX_IMAGES']
+# ase.optimize.FIRE's defaults, in the order nnhip_neb_step takes them: dt, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep
+NEB_FIRE_DEFAULTS = (0.1, 1.0, 5, 1.1, 0.5, 0.1, 0.99, 0.2)
+
+
+def neb_step(pos_in: torch.Tensor, force: torch.Tensor, energy: torch.Tensor, free: Optional[torch.Tensor], mol_ptr: torch.Tensor,
+             band_ptr: torch.Tensor, band_ptr_host: torch.Tensor, spring: float, tol2: float, climb2: float, fire, flags: int,
+             converged: torch.Tensor, climbing: torch.Tensor, n_steps: torch.Tensor, n_pos: torch.Tensor, dt: torch.Tensor,
+             a: torch.Tensor, vel: torch.Tensor, pos_out: torch.Tensor, neb_force_out: torch.Tensor, tangent_out: torch.Tensor,
+             fmax_out: torch.Tensor, saddle_out: torch.Tensor):
+    """One launch of the nudged-elastic-band step (nnhip_neb_step, csrc/neb.hip; the contract is in include/newtonnet_hip.h) on
+    the current stream, for the K bands band_ptr (int32 [K+1], device; band_ptr_host: the same on the host) delimits among the B
+    molecules of mol_ptr (int32 [B+1]).  pos_in, force [N,3] and energy [B] are read; free: bool / uint8 [N] (False = fixed atom)
+    or None; fire = (dt, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep).  The state (converged, climbing, n_steps, n_pos int32
+    [K]; dt, a fp32 [K]; vel fp32 [N,3]) is updated in place, pos_out, neb_force_out, tangent_out [N,3], fmax_out [K] and saddle_out
+    (int32 [K]) are written: all of these must be contiguous tensors of exactly that type (a copy would take the result away).
+    pos_out may not overlap pos_in."""
+    for name, t in (('mol_ptr', mol_ptr), ('band_ptr', band_ptr), ('band_ptr_host', band_ptr_host)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
+            raise ValueError(f'{name}: contiguous int32 expected')
+    if band_ptr_host.device.type != 'cpu' or band_ptr_host.numel() != band_ptr.numel():
+        raise ValueError('band_ptr_host: the host copy of band_ptr expected')
+    dev, B, K = mol_ptr.device, mol_ptr.numel() - 1, band_ptr.numel() - 1
+    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
+        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
+    N = pos_out.shape[0]
+    for name, t, dtype, numel in (('converged', converged, torch.int32, K), ('climbing', climbing, torch.int32, K),
+                                  ('n_steps', n_steps, torch.int32, K), ('n_pos', n_pos, torch.int32, K),
+                                  ('dt', dt, torch.float32, K), ('a', a, torch.float32, K), ('vel', vel, torch.float32, 3 * N),
+                                  ('pos_out', pos_out, torch.float32, 3 * N), ('neb_force_out', neb_force_out, torch.float32, 3 * N),
+                                  ('tangent_out', tangent_out, torch.float32, 3 * N), ('fmax_out', fmax_out, torch.float32, K),
+                                  ('saddle_out', saddle_out, torch.int32, K)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
+    pos_in, force, energy = _f32c(pos_in, 'pos_in'), _f32c(force, 'force'), _f32c(energy, 'energy')
+    if free is not None:
+        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
+            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
+        free = free.contiguous()
+    for name, t, numel in (('pos_in', pos_in, 3 * N), ('force', force, 3 * N), ('energy', energy, B), ('band_ptr', band_ptr, K + 1)):
+        if t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+    dt0, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep = fire
+    _check(lib().nnhip_neb_step(_ptr(pos_in), _ptr(force), _ptr(energy), _ptr(free), _ptr(mol_ptr), _ptr(band_ptr),
+                                _ptr(band_ptr_host), K, B, N, float(spring), float(tol2), float(climb2), float(dt0), float(dt_max),
+                                int(n_min), float(f_inc), float(f_dec), float(a_start), float(f_a), float(maxstep), int(flags),
+                                _ptr(converged), _ptr(climbing), _ptr(n_steps), _ptr(n_pos), _ptr(dt), _ptr(a), _ptr(vel),
+                                _ptr(pos_out), _ptr(neb_force_out), _ptr(tangent_out), _ptr(fmax_out), _ptr(saddle_out),
+                                _stream(dev)), 'nnhip_neb_step')
+
+
 def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[e] = x[idx[e]] (idx int32)."""
     x = _f32c(x, 'x')

@@ -794,6 +794,19 @@ class NewtonNet(nn.Module):
         from newtonnet_amd import relax as _r
         return _r.Relaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, fixed=fixed)
 
+    def band(self, z, pos, cell, batch, n_images, spring=0.1, fmax=0.05, climb=True, climb_below=None, fixed=None, dt=0.1,
+             dt_max=1.0, maxstep=0.2):
+        """Nudged-elastic-band saddle search on the device: a newtonnet_amd.neb.Band whose run(max_steps, check_every,
+        record_every) steps every band of the batch together, one model() call over all images and one launch (csrc/neb.hip) per
+        step.  The images of a band are consecutive molecules in path order; n_images: images per band (an int, or one count per
+        band), the first and last being fixed endpoints.  Improved tangents, one spring constant (eV / Angstrom^2), FIRE with
+        ASE's constants (dt, dt_max, maxstep), a climbing image per band switched on below climb_below (None: 5 fmax); a band has
+        converged when its largest NEB force is below fmax (eV / Angstrom) with the climbing image on.  fixed: bool [N], atoms that
+        never move.  Eval mode only; needs the 'energy' and 'gradient_force' heads.  neb.interpolate builds linear images."""
+        from newtonnet_amd import neb as _n
+        return _n.Band(self, z, pos, cell, batch, n_images, spring=spring, fmax=fmax, climb=climb, climb_below=climb_below,
+                       fixed=fixed, dt=dt, dt_max=dt_max, maxstep=maxstep)
+
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated
         (trainer.py:301-313): newtonnet_amd/train_fused.py, no torch autograd graph inside the step."""

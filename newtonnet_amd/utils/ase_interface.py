@@ -256,6 +256,56 @@ class MLAseCalculator(_Base):
             out = {k: v[0] for k, v in out.items()}
         return out
 
+    def neb(self, images_or_list_of_bands, spring: float = 0.1, fmax: float = 0.05, max_steps: int = 500, climb: bool = True,
+            climb_below=None, dt: float = 0.1, dt_max: float = 1.0, maxstep: float = 0.2, check_every: int = 10, fixed=None):
+        """Nudged-elastic-band saddle search of one band (a list of Atoms-like images in path order, the first and last being the
+        fixed endpoints) or a list of bands, all stepped together on the device (NewtonNet.band): improved tangents, FIRE, a
+        climbing image switched on below climb_below (None: 5 fmax), until the largest NEB force of a band is below fmax (eV /
+        Angstrom) or max_steps steps have been taken.  Every image of a band has the same atoms; bands may differ.  fixed: bool
+        array [n_atoms] (only when all bands have n_atoms atoms per image), the same atoms held in every image.  Returns a dict of
+        numpy arrays: positions (per band [n_images, n_atoms, 3]), energy (per band [n_images]), fmax, converged, climbing,
+        n_steps, saddle_image (index within the band), barrier_forward, barrier_reverse [n_bands]; one band drops the band axis,
+        several bands give lists for positions and energy.  The Atoms objects are not modified."""
+        from newtonnet_amd import neb as _n
+        from newtonnet_amd import relax as _r
+        arg = list(images_or_list_of_bands)
+        if not arg:
+            raise ValueError('neb: at least one band expected')
+        single = _is_single(arg[0])
+        bands = [arg] if single else [list(b) for b in arg]
+        counts = [len(b) for b in bands]
+        for k, b in enumerate(bands):
+            if not 3 <= len(b) <= _n.hip.NEB_MAX_IMAGES:
+                raise ValueError(f'neb: band {k} has {len(b)} images (3 .. {_n.hip.NEB_MAX_IMAGES} expected)')
+            if any(len(a) != len(b[0]) for a in b):
+                raise ValueError(f'neb: the images of band {k} have different sizes')
+        _n.check_arguments(spring, fmax, climb_below, dt, dt_max, maxstep)
+        _r.check_run_arguments(max_steps, check_every, 0)
+        sizes = [len(b[0]) for b in bands]
+        if fixed is not None:
+            fixed = np.asarray(fixed)
+            if fixed.dtype != np.bool_ or any(fixed.shape != (n,) for n in sizes):
+                raise ValueError(f'fixed: a bool array [{sizes[0]}] expected, and every band with that many atoms per image')
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd band searches run on an MI355X (ROCm) device only: make the calculator with '
+                               'device="cuda"')
+        z, pos, cell, batch = self.format_data([a for b in bands for a in b])
+        held = None if fixed is None else torch.from_numpy(np.tile(fixed, sum(counts))).to(pos.device)
+        band = self.model.band(z, pos.float(), cell.float(), batch, counts, spring=spring, fmax=fmax, climb=climb,
+                               climb_below=climb_below, fixed=held, dt=dt, dt_max=dt_max, maxstep=maxstep)
+        res = band.run(int(max_steps), int(check_every))
+        p, e = res.pos.cpu().numpy(), res.energy.cpu().numpy()
+        first = np.concatenate([[0], np.cumsum(counts)])
+        atom0 = np.concatenate([[0], np.cumsum([c * n for c, n in zip(counts, sizes)])])
+        out = dict(positions=[p[atom0[k]:atom0[k + 1]].reshape(counts[k], sizes[k], 3) for k in range(len(bands))],
+                   energy=[e[first[k]:first[k + 1]] for k in range(len(bands))], fmax=res.fmax.cpu().numpy(),
+                   converged=res.converged.cpu().numpy(), climbing=res.climbing.cpu().numpy(), n_steps=res.n_steps.cpu().numpy(),
+                   saddle_image=res.saddle_image.cpu().numpy() - first[:-1], barrier_forward=res.barrier_forward.cpu().numpy(),
+                   barrier_reverse=res.barrier_reverse.cpu().numpy())
+        if single:
+            out = {k: v[0] for k, v in out.items()}
+        return out
+
     # ------------------------------------------------------------------ MD-loop latency path (SURVEY 8f rank 2)
     def _calculate_md(self, atoms):
         """One structure per call, called thousands of times by an MD driver (simulate.py:21-30): keep everything that does
