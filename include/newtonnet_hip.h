@@ -1013,6 +1013,60 @@ int nnhip_neb_step(const float* pos_in, const float* force, const float* energy,
                    float* fmax_out, int32_t* saddle_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Replica exchange (parallel tempering) on the device (csrc/remd.hip): ONE launch on `stream` attempts every neighbouring pair of
+ * one parity in every temperature ladder of a batch, from the energies just evaluated, and swaps the temperatures of an accepted
+ * pair in place.  One workgroup of four waves per ladder, the ladders by a grid-stride loop; thread k decides pair k and posts the
+ * new rank and velocity scale of its two slots in LDS, one barrier reached by every thread follows (a skipped ladder skips the
+ * work, never the barrier), then all 256 threads walk the ladder's atoms.  No float atomics, no communication between workgroups: a
+ * ladder's outputs are bitwise independent of the rest of the batch and of its place in it.  Every float operation is one
+ * rounding (tests/remd_ref.py restates the launch bitwise).
+ *
+ * Layout: ladder g owns the consecutive molecules ladder_ptr[g] .. ladder_ptr[g+1] - 1, its SLOTS: replicas of one system, all of
+ * the same atom count (int32 [G+1], on the device; ladder_ptr_host and mol_ptr_host are the same arrays in host memory, for the
+ * checks below); mol_ptr int32 [B+1] gives each slot's atoms.  Ladders may differ in atom count and in length R_g
+ * (2 .. NNHIP_REMD_MAX_REPLICAS).  Every per-slot and per-pair array has B entries; entry ladder_ptr[g] + k belongs to slot k, rank
+ * k or pair (k, k + 1) of ladder g, and the last per-pair entry of a ladder is unused.
+ * State (device arrays of the caller):  rank_of_slot, slot_of_rank int32 [B], relative to the ladder and inverse permutations of
+ * each other (rank = index into the ladder's temperatures; both the identity at the start);  vel fp32 [N][3];  sigma fp32 [N], the
+ * Langevin sigma nnhip_md_step reads;  n_attempt, n_accept int32 [B], per pair, accumulated.
+ * Per launch:  energy fp32 [B] (read only);  stream_id int32 [G], the bits of a uint32: the ladder's identity for the random
+ * stream, NOT its position in the batch;  dbeta fp32 [B] = fl32(1 / (k_B T_k) - 1 / (k_B T_{k+1}));  scale_up, scale_down fp32 [B]
+ * = fl32(sqrt(T_{k+1} / T_k)), fl32(sqrt(T_k / T_{k+1})) (all three formed in fp64 on the host and rounded once);  sigma_table fp32
+ * [n_rows][N]: row k holds every atom's sigma at rank k of its ladder (fixed atoms: 0 in every row);  attempt, the bits of a
+ * uint32, and seed, the bits of a uint64 (the header's vocabulary has signed scalars only).  Optional outputs (NULL: not written)
+ * delta_out, u_out fp32 [B] and accepted_out int32 [B], per pair.
+ *
+ * One launch for ladder g of R slots:
+ *   1. Pairs attempted: with p = attempt & 1, the pairs (k, k + 1) for k = p, p + 2, ... < R - 1.  They are disjoint: no two
+ *      decisions touch the same slot.
+ *   2. Pair k, with a = slot_of_rank[k] and b = slot_of_rank[k + 1]:  dE = E_a - E_b and delta = dbeta_k dE, one rounding each.
+ *   3. (w0, w1, w2, w3) = Philox4x32-10 with counter (attempt, stream_id[g], k, 0) and key (seed low word, seed high word);
+ *      u = float(w0 >> 8) 2^-24: exact in fp32, in [0, 1).
+ *   4. Accepted iff  delta >= 0 || u < expf(delta).  A NaN delta rejects, a tie (delta == 0) accepts.  n_attempt[k] += 1 and
+ *      n_accept[k] += accepted;  delta_out[k] = delta, u_out[k] = u, accepted_out[k] = 0 / 1.  The entries of pairs NOT attempted in
+ *      this launch (the other parity, the unused last entry) get 0 in all three.
+ *   5. Accepted:  rank_of_slot[a] = k + 1, rank_of_slot[b] = k, slot_of_rank[k] = b, slot_of_rank[k + 1] = a;  every vel component
+ *      of slot a is multiplied by scale_up_k and every one of slot b by scale_down_k, one rounded product each;  sigma[i] =
+ *      sigma_table[new rank][i] for the atoms of both slots: a copy, so sigma never drifts.  positions and forces are not arguments.
+ *   6. A slot that is not swapped keeps every bit of its vel, sigma and map entries.
+ * Skipped on the device: a ladder whose rank maps are not inverse permutations of each other (or whose slots differ in atom count
+ * in mol_ptr) gets delta_out = NaN and accepted_out = 0 in all its entries and nothing else of it is written (u_out neither); a
+ * ladder whose device offsets leave the arrays is not touched at all.
+ * NNHIP_E_INVALID, nothing launched: NULL mandatory pointers (everything but the three optional outputs), negative counts,
+ * ladder_ptr_host not running from 0 to n_mol (or a ladder leaving the batch on the way) or mol_ptr_host not from 0 to n_atoms, a
+ * ladder of fewer than 2 or more than NNHIP_REMD_MAX_REPLICAS slots, n_rows below the longest ladder, slots of one ladder with
+ * unequal atom counts.  n_ladders == 0 with n_mol == 0 is success without a launch.
+ * The energies enter one difference of two slots of one ladder: delta is resolved to one fp32 ulp of |E| times dbeta.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_REMD_MAX_REPLICAS 64
+int nnhip_remd_exchange(const float* energy, const int32_t* mol_ptr, const int32_t* mol_ptr_host, const int32_t* ladder_ptr,
+                        const int32_t* ladder_ptr_host, const int32_t* stream_id, const float* dbeta, const float* scale_up,
+                        const float* scale_down, const float* sigma_table, int32_t* rank_of_slot, int32_t* slot_of_rank, float* vel,
+                        float* sigma, int32_t* n_attempt, int32_t* n_accept, float* delta_out, float* u_out, int32_t* accepted_out,
+                        int32_t attempt, int64_t seed, int32_t n_ladders, int32_t n_mol, int32_t n_atoms, int32_t n_rows,
+                        void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

@@ -110,6 +110,53 @@ class Trajectory:
         return 2.0 * self.kinetic_energy / (3.0 * K_BOLTZMANN * self._counts.clamp(min=1).float())
 
 
+def _check_system(model, z, pos, cell, batch, masses, velocities, fixed, timestep, friction):
+    """the model, the batch and the integrator's numbers, refused without touching the device; returns (N, B, timestep, friction)"""
+    if getattr(model, 'training', False):
+        raise ValueError('Dynamics needs the model in eval mode: call model.eval()')
+    props = list(getattr(model, 'output_properties', []))
+    if 'energy' not in props or 'gradient_force' not in props:
+        raise ValueError(f"Dynamics needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
+    for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
+    N = pos.shape[0]
+    if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
+        raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
+    B = cell.shape[0]
+    if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
+        raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
+    if pos.dtype != torch.float32 or cell.dtype != torch.float32:
+        raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
+    if masses is not None and (not isinstance(masses, torch.Tensor) or masses.numel() != N):
+        raise ValueError(f'masses: a tensor of {N} values expected')
+    if velocities is not None and (not isinstance(velocities, torch.Tensor) or tuple(velocities.shape) != (N, 3)):
+        raise ValueError(f'velocities: a tensor [{N},3] expected')
+    if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
+        raise ValueError(f'fixed: a bool tensor [{N}] expected')
+    timestep, friction = float(timestep), float(friction)
+    if not (timestep > 0.0 and math.isfinite(timestep)):
+        raise ValueError(f'timestep: a finite value > 0 fs expected (got {timestep!r})')
+    if not (friction >= 0.0 and math.isfinite(friction)):
+        raise ValueError(f'friction: a finite value >= 0 per fs expected (got {friction!r})')
+    return N, B, timestep, friction
+
+
+def _check_devices(pos, generator, **tensors):
+    """everything lives on the device of pos, which is a ROCm device; returns it"""
+    if not pos.is_cuda:
+        raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
+    dev = pos.device
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.dim() > 0 and t.device != dev:
+            raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+    if generator is not None and torch.device(generator.device).type != dev.type:
+        raise ValueError(f'generator is on {generator.device}, pos on {dev}')
+    return dev
+
+
 class Dynamics:
     """B molecules advanced together on the device.
 
@@ -125,47 +172,12 @@ class Dynamics:
     def __init__(self, model, z, pos, cell, batch, masses=None, velocities=None, temperature=None, friction=0.0, timestep=0.5,
                  fixed=None, generator=None):
         # ---- everything that can be refused without touching the device
-        if getattr(model, 'training', False):
-            raise ValueError('Dynamics needs the model in eval mode: call model.eval()')
-        props = list(getattr(model, 'output_properties', []))
-        if 'energy' not in props or 'gradient_force' not in props:
-            raise ValueError(f"Dynamics needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
-        for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
-        if pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
-        N = pos.shape[0]
-        if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
-            raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
-        B = cell.shape[0]
-        if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
-            raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
-        if pos.dtype != torch.float32 or cell.dtype != torch.float32:
-            raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
-        if masses is not None and (not isinstance(masses, torch.Tensor) or masses.numel() != N):
-            raise ValueError(f'masses: a tensor of {N} values expected')
-        if velocities is not None and (not isinstance(velocities, torch.Tensor) or tuple(velocities.shape) != (N, 3)):
-            raise ValueError(f'velocities: a tensor [{N},3] expected')
-        if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
-            raise ValueError(f'fixed: a bool tensor [{N}] expected')
-        timestep, friction = float(timestep), float(friction)
-        if not (timestep > 0.0 and math.isfinite(timestep)):
-            raise ValueError(f'timestep: a finite value > 0 fs expected (got {timestep!r})')
-        if not (friction >= 0.0 and math.isfinite(friction)):
-            raise ValueError(f'friction: a finite value >= 0 per fs expected (got {friction!r})')
+        N, B, timestep, friction = _check_system(model, z, pos, cell, batch, masses, velocities, fixed, timestep, friction)
         _check_temperature(temperature, B)
         if friction > 0.0 and temperature is None:
             raise ValueError('friction > 0 (Langevin dynamics) needs a temperature')
-        if not pos.is_cuda:
-            raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
-        dev = pos.device
-        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('masses', masses), ('velocities', velocities), ('fixed', fixed),
-                        ('temperature', temperature)):
-            if isinstance(t, torch.Tensor) and t.dim() > 0 and t.device != dev:
-                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
-        if generator is not None and torch.device(generator.device).type != dev.type:
-            raise ValueError(f'generator is on {generator.device}, pos on {dev}')
+        dev = _check_devices(pos, generator, z=z, cell=cell, batch=batch, masses=masses, velocities=velocities, fixed=fixed,
+                             temperature=temperature)
         # ---- state
         self.model, self.z, self.cell, self.batch = model, z, cell, batch
         self.n_atoms, self.n_mol = N, B
@@ -254,6 +266,29 @@ class Dynamics:
         and its final step (record_every = 0: the final step only; n_steps = 0: the current state).  May be called again: the state
         between calls is (positions, velocities, forces, energies) at a full step, and run(a); run(b) leaves the same bits as
         run(a + b).  Langevin dynamics draws exactly one torch.randn((N, 3)) per step from the generator, in step order."""
+        n_steps, recorded = self._recorded_steps(n_steps, record_every)
+        with torch.no_grad():
+            self._ensure_state()
+            traj = self._new_trajectory(Trajectory, recorded)
+            r = 0
+            pending = False          # the second half kick of the previous step has not been launched yet
+            for k in range(1, n_steps + 1):
+                self._advance(pending)
+                pending = True
+                if k == recorded[r]:
+                    self._finish()
+                    pending = False
+                    self._store(traj, r)
+                    r += 1
+            if n_steps == 0:
+                self._store(traj, 0)
+            self.step_count += n_steps
+        return traj
+
+    # ---- the pieces of run (newtonnet_amd/remd.py puts its exchange attempts between them)
+    @staticmethod
+    def _recorded_steps(n_steps, record_every):
+        """(n_steps, the steps of a call that are recorded) of run's two arguments, refused without touching the device"""
         if int(n_steps) != n_steps or n_steps < 0:
             raise ValueError(f'n_steps: an integer >= 0 expected (got {n_steps!r})')
         if int(record_every) != record_every or record_every < 0:
@@ -262,38 +297,30 @@ class Dynamics:
         recorded = list(range(every, n_steps + 1, every)) if every else []
         if not recorded or recorded[-1] != n_steps:
             recorded.append(n_steps)
+        return n_steps, recorded
+
+    def _new_trajectory(self, cls, recorded):
         R, N, B, dev = len(recorded), self.n_atoms, self.n_mol, self._vel.device
-        with torch.no_grad():
-            self._ensure_state()
-            traj = Trajectory(torch.tensor([self.step_count + k for k in recorded], dtype=torch.int64, device=dev),
-                              torch.empty(R, N, 3, dtype=torch.float32, device=dev), torch.empty(R, N, 3, dtype=torch.float32, device=dev),
-                              torch.empty(R, B, dtype=torch.float32, device=dev), torch.empty(R, B, dtype=torch.float32, device=dev),
-                              self._counts)
-            r = 0
-            pending = False          # the second half kick of the previous step has not been launched yet
-            for k in range(1, n_steps + 1):
-                noise = None
-                if self._sigma is not None:
-                    noise = torch.randn((N, 3), generator=self.generator, device=dev, dtype=torch.float32)
-                other = 1 - self._cur
-                hip.md_step(self._pos[self._cur], self._vel, self._force, self._hk, self._dth, self._c1,
-                            (hip.MD_FINISH | hip.MD_BEGIN) if pending else hip.MD_BEGIN, pos_out=self._pos[other],
-                            sigma=self._sigma, noise=noise)
-                self._cur = other
-                self._evaluate()
-                pending = True
-                if k == recorded[r]:
-                    self._finish()
-                    pending = False
-                    traj.pos[r].copy_(self._pos[self._cur])
-                    traj.vel[r].copy_(self._vel)
-                    traj.potential_energy[r].copy_(self._energy)
-                    traj.kinetic_energy[r].copy_(self._ke)
-                    r += 1
-            if n_steps == 0:
-                traj.pos[0].copy_(self._pos[self._cur])
-                traj.vel[0].copy_(self._vel)
-                traj.potential_energy[0].copy_(self._energy)
-                traj.kinetic_energy[0].copy_(self._ke)
-            self.step_count += n_steps
-        return traj
+        return cls(torch.tensor([self.step_count + k for k in recorded], dtype=torch.int64, device=dev),
+                   torch.empty(R, N, 3, dtype=torch.float32, device=dev), torch.empty(R, N, 3, dtype=torch.float32, device=dev),
+                   torch.empty(R, B, dtype=torch.float32, device=dev), torch.empty(R, B, dtype=torch.float32, device=dev),
+                   self._counts)
+
+    def _advance(self, pending: bool):
+        """the noise of a step, the first half of it (with the second half kick of the step before, if that is still pending) and
+        the forces at the new positions"""
+        noise = None
+        if self._sigma is not None:
+            noise = torch.randn((self.n_atoms, 3), generator=self.generator, device=self._vel.device, dtype=torch.float32)
+        other = 1 - self._cur
+        hip.md_step(self._pos[self._cur], self._vel, self._force, self._hk, self._dth, self._c1,
+                    (hip.MD_FINISH | hip.MD_BEGIN) if pending else hip.MD_BEGIN, pos_out=self._pos[other],
+                    sigma=self._sigma, noise=noise)
+        self._cur = other
+        self._evaluate()
+
+    def _store(self, traj, r: int):
+        traj.pos[r].copy_(self._pos[self._cur])
+        traj.vel[r].copy_(self._vel)
+        traj.potential_energy[r].copy_(self._energy)
+        traj.kinetic_energy[r].copy_(self._ke)

@@ -730,6 +730,67 @@ def neb_step(pos_in: torch.Tensor, force: torch.Tensor, energy: torch.Tensor, fr
                                 _stream(dev)), 'nnhip_neb_step')
 
 
+REMD_MAX_REPLICAS = _K['NNHIP_REMD_MAX_REPLICAS']
+
+
+def remd_exchange(energy: torch.Tensor, mol_ptr: torch.Tensor, mol_ptr_host: torch.Tensor, ladder_ptr: torch.Tensor,
+                  ladder_ptr_host: torch.Tensor, stream_id: torch.Tensor, dbeta: torch.Tensor, scale_up: torch.Tensor,
+                  scale_down: torch.Tensor, sigma_table: torch.Tensor, rank_of_slot: torch.Tensor, slot_of_rank: torch.Tensor,
+                  vel: torch.Tensor, sigma: torch.Tensor, n_attempt: torch.Tensor, n_accept: torch.Tensor, attempt: int, seed: int,
+                  delta_out: Optional[torch.Tensor] = None, u_out: Optional[torch.Tensor] = None,
+                  accepted_out: Optional[torch.Tensor] = None):
+    """One launch of the replica-exchange attempt (nnhip_remd_exchange, csrc/remd.hip; the contract is in
+    include/newtonnet_hip.h) on the current stream, for the G ladders ladder_ptr (int32 [G+1], device; ladder_ptr_host and
+    mol_ptr_host: the same arrays on the host) delimits among the B molecules of mol_ptr (int32 [B+1]).  energy [B], stream_id
+    (int32 [G]), dbeta, scale_up, scale_down [B] and sigma_table [n_rows,N] are read; rank_of_slot, slot_of_rank, n_attempt,
+    n_accept (int32 [B]), vel [N,3] and sigma [N] are updated in place, delta_out, u_out (fp32 [B]) and accepted_out (int32 [B]) are
+    written when given: all of these must be contiguous tensors of exactly that type (a copy would take the result away).
+    attempt: the attempt number (its low bit is the parity), an int in 0 .. 2^32 - 1; seed: an int in 0 .. 2^64 - 1."""
+    for name, t in (('mol_ptr', mol_ptr), ('ladder_ptr', ladder_ptr), ('mol_ptr_host', mol_ptr_host),
+                    ('ladder_ptr_host', ladder_ptr_host)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
+            raise ValueError(f'{name}: contiguous int32 expected')
+    if ladder_ptr_host.device.type != 'cpu' or ladder_ptr_host.numel() != ladder_ptr.numel():
+        raise ValueError('ladder_ptr_host: the host copy of ladder_ptr expected')
+    if mol_ptr_host.device.type != 'cpu' or mol_ptr_host.numel() != mol_ptr.numel():
+        raise ValueError('mol_ptr_host: the host copy of mol_ptr expected')
+    if int(attempt) != attempt or not 0 <= attempt < 2 ** 32 or int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError(f'attempt: an integer in 0 .. 2^32 - 1 and seed: one in 0 .. 2^64 - 1 expected (got {attempt!r}, {seed!r})')
+    dev, B, G = mol_ptr.device, mol_ptr.numel() - 1, ladder_ptr.numel() - 1
+    if vel.dim() != 2 or vel.shape[1] != 3:
+        raise ValueError(f'vel: [N,3] expected (got {tuple(vel.shape)})')
+    N = vel.shape[0]
+    if sigma_table.dim() != 2 or sigma_table.shape[1] != N:
+        raise ValueError(f'sigma_table: [n_rows,{N}] expected (got {tuple(sigma_table.shape)})')
+    n_rows = sigma_table.shape[0]
+    for name, t, dtype, numel in (('rank_of_slot', rank_of_slot, torch.int32, B), ('slot_of_rank', slot_of_rank, torch.int32, B),
+                                  ('n_attempt', n_attempt, torch.int32, B), ('n_accept', n_accept, torch.int32, B),
+                                  ('vel', vel, torch.float32, 3 * N), ('sigma', sigma, torch.float32, N),
+                                  ('delta_out', delta_out, torch.float32, B), ('u_out', u_out, torch.float32, B),
+                                  ('accepted_out', accepted_out, torch.int32, B)):
+        if t is None and name.endswith('_out'):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
+    energy, dbeta, scale_up, scale_down, sigma_table = (_f32c(t, name) for name, t in (
+        ('energy', energy), ('dbeta', dbeta), ('scale_up', scale_up), ('scale_down', scale_down), ('sigma_table', sigma_table)))
+    if stream_id.dtype != torch.int32:
+        raise ValueError('stream_id: int32 expected (the bits of a uint32)')
+    stream_id = stream_id.contiguous()
+    for name, t, numel in (('energy', energy, B), ('dbeta', dbeta, B), ('scale_up', scale_up, B), ('scale_down', scale_down, B),
+                           ('stream_id', stream_id, G), ('ladder_ptr', ladder_ptr, G + 1), ('sigma_table', sigma_table, n_rows * N)):
+        if t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+    attempt, seed = int(attempt), int(seed)
+    # (the C ABI has signed scalars only: the same bits)
+    _check(lib().nnhip_remd_exchange(_ptr(energy), _ptr(mol_ptr), _ptr(mol_ptr_host), _ptr(ladder_ptr), _ptr(ladder_ptr_host),
+                                     _ptr(stream_id), _ptr(dbeta), _ptr(scale_up), _ptr(scale_down), _ptr(sigma_table),
+                                     _ptr(rank_of_slot), _ptr(slot_of_rank), _ptr(vel), _ptr(sigma), _ptr(n_attempt), _ptr(n_accept),
+                                     _ptr(delta_out), _ptr(u_out), _ptr(accepted_out),
+                                     attempt - 2 ** 32 if attempt >= 2 ** 31 else attempt, seed - 2 ** 64 if seed >= 2 ** 63 else seed,
+                                     G, B, N, n_rows, _stream(dev)), 'nnhip_remd_exchange')
+
+
 def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[e] = x[idx[e]] (idx int32)."""
     x = _f32c(x, 'x')

@@ -783,6 +783,18 @@ class NewtonNet(nn.Module):
         from newtonnet_amd import dynamics as _d
         return _d.Dynamics(self, z, pos, cell, batch, **kw)
 
+    def replica_exchange(self, z, pos, cell, batch, temperatures, exchange_every, friction, timestep=0.5, masses=None, fixed=None,
+                         generator=None, exchange_seed=0):
+        """Replica-exchange molecular dynamics (parallel tempering) on the device: a newtonnet_amd.remd.ReplicaExchange, a Dynamics
+        over G systems x R temperatures whose run(n_steps, record_every) also attempts, every exchange_every steps, a Metropolis
+        swap of the temperatures of neighbouring replicas in ONE launch (csrc/remd.hip), with no host read in the loop.  z, pos,
+        cell, batch describe the G systems; temperatures (K): [R] or [G, R], non-decreasing, 2 <= R <= 64; friction (1 / fs) > 0;
+        exchange_seed: the seed of the exchange decisions, separate from `generator` (initial velocities and Langevin noise).  Eval
+        mode only; needs the 'energy' and 'gradient_force' heads."""
+        from newtonnet_amd import remd as _x
+        return _x.ReplicaExchange(self, z, pos, cell, batch, temperatures, exchange_every, friction, timestep=timestep, masses=masses,
+                                  fixed=fixed, generator=generator, exchange_seed=exchange_seed)
+
     def relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
         """Relaxation of every molecule of the batch to a minimum on the device: a newtonnet_amd.relax.Relaxation whose
         run(max_steps, check_every, record_every) steps them together, one force evaluation and one L-BFGS launch (csrc/relax.hip)

@@ -223,6 +223,69 @@ class MLAseCalculator(_Base):
                 out[k] = out[k][:, 0]
         return out
 
+    def run_remd(self, atoms_or_list, temperatures, n_steps: int, exchange_every: int, friction: float, timestep: float = 0.5,
+                 record_every: int = 0, seed=None, exchange_seed: int = 0):
+        """n_steps of replica-exchange molecular dynamics (NewtonNet.replica_exchange) of one structure or a list of G equally
+        sized ones: each is replicated over the R `temperatures` (K; [R], or [G, R]: one ladder per structure), all G R replicas
+        advance together on the device (Langevin, friction in 1 / fs, > 0) and every exchange_every steps neighbouring temperatures
+        attempt a Metropolis swap (0: never).  Masses from atoms.get_masses() when the objects have it; initial velocities are
+        Maxwell-Boltzmann at each replica's temperature.  seed: of the device generator behind velocities and noise (None:
+        torch's global one); exchange_seed: of the exchange decisions.  Returns a dict of numpy arrays over the Rec recorded steps,
+        per SLOT (a continuous trajectory whose temperature changes): positions, velocities [Rec, G, R, n_atoms, 3], energy,
+        kinetic_energy [Rec, G, R], rank int32 and temperature [Rec, G, R], step [Rec]; per TEMPERATURE, gathered by rank:
+        positions_by_temperature, velocities_by_temperature, energy_by_temperature, kinetic_energy_by_temperature; the exchange log
+        exchange_step [A], delta, u, accepted [A, G, R-1]; and acceptance [G, R-1].  One structure drops the G axis.  The Atoms
+        objects are not modified."""
+        from newtonnet_amd import dynamics as _d
+        from newtonnet_amd import remd as _x
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('run_remd: at least one structure expected')
+        G, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('run_remd: frames of different sizes cannot share one array; use model.replica_exchange (packed per '
+                             'molecule)')
+        _d.Dynamics._recorded_steps(n_steps, record_every)
+        if not (float(timestep) > 0.0):
+            raise ValueError(f'timestep > 0 fs expected (got {timestep!r})')
+        T = _x.check_temperatures(temperatures, G)
+        _x.check_exchange_arguments(exchange_every, friction, exchange_seed)
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: make the calculator with device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        masses = gen = None
+        if all(hasattr(a, 'get_masses') for a in atoms):
+            masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
+                                  dtype=torch.float32, device=pos.device)
+        if seed is not None:
+            gen = torch.Generator(device=pos.device)
+            gen.manual_seed(int(seed))
+        rex = self.model.replica_exchange(z, pos.float(), cell.float(), batch, T, exchange_every, friction, timestep=timestep,
+                                          masses=masses, generator=gen, exchange_seed=exchange_seed)
+        traj = rex.run(int(n_steps), int(record_every))
+        Rec, R = traj.step.numel(), T.shape[1]
+        by_t = traj.by_temperature()
+        out = dict(positions=traj.pos.cpu().numpy().reshape(Rec, G, R, n_atoms, 3),
+                   velocities=traj.vel.cpu().numpy().reshape(Rec, G, R, n_atoms, 3),
+                   energy=traj.potential_energy.cpu().numpy().reshape(Rec, G, R),
+                   kinetic_energy=traj.kinetic_energy.cpu().numpy().reshape(Rec, G, R),
+                   rank=traj.rank.cpu().numpy().reshape(Rec, G, R),
+                   temperature=traj.temperature_of_slot.cpu().numpy().reshape(Rec, G, R),
+                   positions_by_temperature=by_t['pos'].cpu().numpy(), velocities_by_temperature=by_t['vel'].cpu().numpy(),
+                   energy_by_temperature=by_t['potential_energy'].cpu().numpy(),
+                   kinetic_energy_by_temperature=by_t['kinetic_energy'].cpu().numpy(),
+                   delta=traj.delta.cpu().numpy(), u=traj.u.cpu().numpy(), accepted=traj.accepted.cpu().numpy(),
+                   acceptance=rex.acceptance.cpu().numpy())
+        if G == 1:
+            for k in ('positions', 'velocities', 'energy', 'kinetic_energy', 'rank', 'temperature', 'positions_by_temperature',
+                      'velocities_by_temperature', 'energy_by_temperature', 'kinetic_energy_by_temperature'):
+                out[k] = out[k][:, 0]
+            for k in ('delta', 'u', 'accepted'):
+                out[k] = out[k][:, 0]
+            out['acceptance'] = out['acceptance'][0]
+        out['step'], out['exchange_step'] = traj.step.cpu().numpy(), traj.exchange_step.cpu().numpy()
+        return out
+
     def relax(self, atoms_or_list, fmax: float = 0.01, max_steps: int = 500, memory: int = 16, maxstep: float = 0.2,
               alpha: float = 70.0, check_every: int = 10, fixed=None):
         """Relax one structure or a list of equally sized ones to a minimum, all stepped together on the device
