@@ -1067,6 +1067,54 @@ int nnhip_remd_exchange(const float* energy, const int32_t* mol_ptr, const int32
                         void* stream);
 
 /* --------------------------------------------------------------------------
+ * Path-integral molecular dynamics on the device (csrc/pimd.hip): one launch advances every ring polymer of a batch by the second
+ * half kick of one step and / or the first half of the next, in ring-polymer normal-mode coordinates.  The scheme is BAOAB with
+ * the A step exact for the free ring polymer and the O step the PILE thermostat (Ceriotti, Parrinello, Markland and Manolopoulos
+ * 2010); the driver is newtonnet_amd/pimd.py, a step of it  model(beads) -> nnhip_pimd_step(finish | begin).
+ *
+ * Layout: system g owns the n_beads = P consecutive molecules g P .. g P + P - 1 of mol_ptr (int32 [n_mol + 1], on the device;
+ * mol_ptr_host: the same array in host memory, for the checks below), its SLOTS, all of one atom count n_g; n_mol = G P.  In force
+ * and pos_out (fp32 [N][3], the buffers of the model) slot s holds bead s; in the state arrays u, w (fp32 [N][3], mode positions
+ * and mode velocities, updated in place) slot k holds normal mode k.  Row r = mol_ptr[g P + k] + i is (slot k, atom i).
+ * Tables, all formed in fp64 on the host and rounded once -- the kernel evaluates no transcendental:
+ *   ctab fp32 [P][P], the orthonormal transform:  C[0][s] = 1 / sqrt(P);  C[k][s] = sqrt(2 / P) cos(2 pi s k / P) for 0 < k < P / 2;
+ *     C[P/2][s] = (-1)^s / sqrt(P) (P even);  C[k][s] = sqrt(2 / P) sin(2 pi s k / P) for k > P / 2.
+ *   mode_tab fp32 [n_mol][5], per (g, k), with omega_k = 2 omega_P sin(k pi / P) and h = dt / 2:
+ *     a = cos(omega_k h),  b = sin(omega_k h) / omega_k (dt / 2 for k = 0),  d = -omega_k sin(omega_k h),  c1 = exp(-gamma_k dt),
+ *     half_w2 = omega_k^2 / 2.
+ *   hk fp32 [N] = dt / (2 m_i);  mass fp32 [N] (with est_out only);  sigma fp32 [N] = sqrt((1 - c1^2) k_B P T_g / m_i), per row;
+ *   noise fp32 [N][3], standard normal, in mode space (sigma and noise: both or neither).
+ *
+ * Per row (mode k, atom i) and coordinate, every operation in fp32 and one rounding (tests/pimd_ref.py restates it in fp64):
+ *   f_k = C[k][0] F_0;  f_k = fma(C[k][s], F_s, f_k) for s = 1 .. P - 1 ascending           (the mode force; once per launch)
+ *   finish (NNHIP_PIMD_FINISH):  w = fma(hk, f_k, w);  est_out[r] = (kinetic, spring, virial, 0) when est_out != NULL:
+ *     kinetic = (0.5 m) fma(wz, wz, fma(wy, wy, wx wx)),  spring = (m half_w2) fma(uz, uz, fma(uy, uy, ux ux)),
+ *     virial = fma(uz, fz, fma(uy, fy, ux fx)) for k > 0 and 0 for k = 0
+ *   begin (NNHIP_PIMD_BEGIN):  w = fma(hk, f_k, w);  A: (u, w) <- (fma(b, w, a u), fma(d, u, a w)), both from the old pair;
+ *     O: w = fma(sigma, noise, c1 w), skipped entirely when noise == NULL;  A again;  u and w are stored;
+ *     x_s = C[0][s] u_0;  x_s = fma(C[k][s], u_k, x_s) for k = 1 .. P - 1 ascending  ->  pos_out, bead s
+ * With P = 1 (C = [1], a = 1, b = dth, d = 0) this is nnhip_md_step's chain, bit for bit.  finish alone writes neither u nor
+ * pos_out.  est_out fp32 [N][4] is reduced per slot with nnhip_segment_sum (width 4).
+ *
+ * One workgroup of NNHIP_PIMD_THREADS threads per (system, tile of atoms); a tile holds NNHIP_PIMD_THREADS / P atoms (rounded down).
+ * No float atomics, no communication between workgroups: a system's outputs are bitwise independent of the rest of the batch.
+ * A system whose DEVICE offsets leave the arrays is not touched.
+ * NNHIP_E_INVALID, nothing launched: flags outside 1 .. 3, negative counts, n_beads outside 1 .. NNHIP_PIMD_MAX_BEADS or not
+ * dividing n_mol, sigma without noise or noise without sigma, est_out without finish (or without mass), mol_ptr_host not running
+ * from 0 to n_atoms, slots of one system with unequal atom counts, NULL mandatory pointers (u, w, force, ctab, mode_tab, hk,
+ * mol_ptr, mol_ptr_host; pos_out with begin), pos_out overlapping pos_pending -- the positions the forward call still pending read
+ * (NULL: none is pending), for the reason given at nnhip_md_step.  n_atoms == 0 is success without a launch.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_PIMD_FINISH 1
+#define NNHIP_PIMD_BEGIN 2
+#define NNHIP_PIMD_MAX_BEADS 64
+#define NNHIP_PIMD_THREADS 256
+int nnhip_pimd_step(float* u, float* w, const float* force, const float* ctab, const float* mode_tab, const float* hk,
+                    const float* mass, const float* sigma, const float* noise, const int32_t* mol_ptr, const int32_t* mol_ptr_host,
+                    const float* pos_pending, int32_t flags, int32_t n_beads, int32_t n_mol, int32_t n_atoms, float* pos_out,
+                    float* est_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

@@ -791,6 +791,55 @@ def remd_exchange(energy: torch.Tensor, mol_ptr: torch.Tensor, mol_ptr_host: tor
                                      G, B, N, n_rows, _stream(dev)), 'nnhip_remd_exchange')
 
 
+PIMD_FINISH, PIMD_BEGIN = _K['NNHIP_PIMD_FINISH'], _K['NNHIP_PIMD_BEGIN']      # flags of nnhip_pimd_step
+PIMD_MAX_BEADS = _K['NNHIP_PIMD_MAX_BEADS']
+
+
+def pimd_tile_atoms(n_beads: int) -> int:
+    """atoms of one system a workgroup of nnhip_pimd_step handles: every (slot, atom) of the tile has a thread"""
+    return _K['NNHIP_PIMD_THREADS'] // int(n_beads)
+
+
+def pimd_step(u: torch.Tensor, w: torch.Tensor, force: torch.Tensor, ctab: torch.Tensor, mode_tab: torch.Tensor, hk: torch.Tensor,
+              mol_ptr: torch.Tensor, mol_ptr_host: torch.Tensor, n_beads: int, flags: int, pos_out: Optional[torch.Tensor] = None,
+              pos_pending: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None,
+              sigma: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, est_out: Optional[torch.Tensor] = None):
+    """One launch of the path-integral integrator (nnhip_pimd_step, csrc/pimd.hip; the contract is in include/newtonnet_hip.h) on
+    the current stream, for the G = B / n_beads ring polymers among the B molecules of mol_ptr (int32 [B+1]; mol_ptr_host: the same
+    array on the host).  PIMD_FINISH = the second half kick with the mode forces of `force` (and the estimator terms into
+    `est_out` [N,4]), PIMD_BEGIN = half kick, exact free-ring-polymer half step, the PILE step w = c1 w + sigma noise (only with
+    `noise`), half step, and the bead positions into `pos_out`.  `u`, `w` [N,3] (mode positions and velocities) are updated in
+    place and `pos_out`, `est_out` written: these must be contiguous float32 (a copy would take the result away).  ctab [P,P],
+    mode_tab [B,5], hk, mass, sigma [N], noise [N,3] are read.  `pos_out` may not overlap `pos_pending`, the positions the pending
+    forward call read."""
+    for name, t in (('mol_ptr', mol_ptr), ('mol_ptr_host', mol_ptr_host)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
+            raise ValueError(f'{name}: contiguous int32 expected')
+    if mol_ptr_host.device.type != 'cpu' or mol_ptr_host.numel() != mol_ptr.numel():
+        raise ValueError('mol_ptr_host: the host copy of mol_ptr expected')
+    if isinstance(n_beads, bool) or int(n_beads) != n_beads:
+        raise ValueError(f'n_beads: an integer expected (got {n_beads!r})')
+    P, B = int(n_beads), mol_ptr.numel() - 1
+    for name, t in (('u', u), ('w', w), ('pos_out', pos_out), ('est_out', est_out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
+    if u.dim() != 2 or u.shape[1] != 3:
+        raise ValueError(f'u: [N,3] expected (got {tuple(u.shape)})')
+    N, dev = u.shape[0], u.device
+    names = ('force', 'ctab', 'mode_tab', 'hk', 'mass', 'sigma', 'noise', 'pos_pending')
+    ins = dict(zip(names, (force, ctab, mode_tab, hk, mass, sigma, noise, pos_pending)))
+    ins = {name: None if t is None else _f32c(t, name) for name, t in ins.items()}
+    sizes = dict(force=3 * N, ctab=max(P, 0) ** 2, mode_tab=5 * B, hk=N, mass=N, sigma=N, noise=3 * N, pos_pending=3 * N)
+    for name, t, numel in [(k, ins[k], sizes[k]) for k in names] + [('w', w, 3 * N), ('pos_out', pos_out, 3 * N),
+                                                                     ('est_out', est_out, 4 * N), ('mol_ptr', mol_ptr, B + 1)]:
+        if t is not None and (t.numel() != numel or t.device != dev):
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+    _check(lib().nnhip_pimd_step(_ptr(u), _ptr(w), _ptr(ins['force']), _ptr(ins['ctab']), _ptr(ins['mode_tab']), _ptr(ins['hk']),
+                                 _ptr(ins['mass']), _ptr(ins['sigma']), _ptr(ins['noise']), _ptr(mol_ptr), _ptr(mol_ptr_host),
+                                 _ptr(ins['pos_pending']), int(flags), P, B, N, _ptr(pos_out), _ptr(est_out), _stream(dev)),
+           'nnhip_pimd_step')
+
+
 def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[e] = x[idx[e]] (idx int32)."""
     x = _f32c(x, 'x')

@@ -795,6 +795,19 @@ class NewtonNet(nn.Module):
         return _x.ReplicaExchange(self, z, pos, cell, batch, temperatures, exchange_every, friction, timestep=timestep, masses=masses,
                                   fixed=fixed, generator=generator, exchange_seed=exchange_seed)
 
+    def path_integral(self, z, pos, cell, batch, n_beads, temperature, timestep=0.25, centroid_friction=0.0, mode_friction=1.0,
+                      masses=None, generator=None, bead_positions=None, bead_velocities=None):
+        """Path-integral molecular dynamics on the device: a newtonnet_amd.pimd.PathIntegral, G ring polymers of n_beads beads whose
+        run(n_steps, record_every) makes one model call over all G n_beads beads and ONE launch (csrc/pimd.hip) per step -- the
+        normal-mode transform, the exact free-ring-polymer propagation, the PILE thermostat and the estimator terms -- with no host
+        read in the loop.  z, pos, cell, batch describe the G systems; n_beads: 1 .. 64; temperature (K): a number or [G], > 0;
+        centroid_friction (1 / fs) and mode_friction (dimensionless): both 0 = RPMD, centroid 0 = T-RPMD, both > 0 = PILE.
+        bead_positions, bead_velocities: Cartesian restarts.  Eval mode only; needs the 'energy' and 'gradient_force' heads."""
+        from newtonnet_amd import pimd as _p
+        return _p.PathIntegral(self, z, pos, cell, batch, n_beads, temperature, timestep=timestep,
+                               centroid_friction=centroid_friction, mode_friction=mode_friction, masses=masses, generator=generator,
+                               bead_positions=bead_positions, bead_velocities=bead_velocities)
+
     def relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
         """Relaxation of every molecule of the batch to a minimum on the device: a newtonnet_amd.relax.Relaxation whose
         run(max_steps, check_every, record_every) steps them together, one force evaluation and one L-BFGS launch (csrc/relax.hip)

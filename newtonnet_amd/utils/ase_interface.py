@@ -286,6 +286,60 @@ class MLAseCalculator(_Base):
         out['step'], out['exchange_step'] = traj.step.cpu().numpy(), traj.exchange_step.cpu().numpy()
         return out
 
+    def run_pimd(self, atoms_or_list, n_beads: int, temperature, n_steps: int, timestep: float = 0.25,
+                 centroid_friction: float = 0.0, mode_friction: float = 1.0, record_every: int = 0, seed=None):
+        """n_steps of path-integral molecular dynamics (NewtonNet.path_integral) of one structure or a list of G equally sized ones:
+        each becomes a ring polymer of n_beads beads starting coincident at the structure, all G n_beads beads advance together on
+        the device at `temperature` (K; a number or [G]).  centroid_friction (1 / fs) and mode_friction (dimensionless): both 0 =
+        RPMD, centroid 0 = thermostatted RPMD, both > 0 = PILE.  Masses from atoms.get_masses() when the objects have it.  seed: of
+        the device generator behind the initial velocities and the noise (None: torch's global one).  Returns a dict of numpy
+        arrays over the Rec recorded steps: positions, velocities, mode_positions, mode_velocities [Rec, G, P, n_atoms, 3], energy
+        [Rec, G, P], potential, kinetic_virial, kinetic_primitive, ring_polymer_energy [Rec, G], centroid [Rec, G, n_atoms, 3],
+        radius_of_gyration [Rec, G, n_atoms], step [Rec].  One structure drops the G axis.  The Atoms objects are not modified."""
+        from newtonnet_amd import dynamics as _d
+        from newtonnet_amd import pimd as _p
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('run_pimd: at least one structure expected')
+        G, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('run_pimd: frames of different sizes cannot share one array; use model.path_integral (packed per '
+                             'molecule)')
+        _d.Dynamics._recorded_steps(n_steps, record_every)
+        if not (float(timestep) > 0.0):
+            raise ValueError(f'timestep > 0 fs expected (got {timestep!r})')
+        P = _p.check_beads(n_beads)
+        _p.check_temperature(temperature, G)
+        _p.check_frictions(centroid_friction, mode_friction)
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: make the calculator with device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        masses = gen = None
+        if all(hasattr(a, 'get_masses') for a in atoms):
+            masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
+                                  dtype=torch.float32, device=pos.device)
+        if seed is not None:
+            gen = torch.Generator(device=pos.device)
+            gen.manual_seed(int(seed))
+        pi = self.model.path_integral(z, pos.float(), cell.float(), batch, P, temperature, timestep=timestep,
+                                      centroid_friction=centroid_friction, mode_friction=mode_friction, masses=masses, generator=gen)
+        traj = pi.run(int(n_steps), int(record_every))
+        Rec = traj.step.numel()
+        out = dict(positions=traj.pos.cpu().numpy().reshape(Rec, G, P, n_atoms, 3),
+                   velocities=traj.vel.cpu().numpy().reshape(Rec, G, P, n_atoms, 3),
+                   mode_positions=traj.mode_pos.cpu().numpy().reshape(Rec, G, P, n_atoms, 3),
+                   mode_velocities=traj.mode_vel.cpu().numpy().reshape(Rec, G, P, n_atoms, 3),
+                   energy=traj.potential_energy.cpu().numpy().reshape(Rec, G, P),
+                   potential=traj.potential.cpu().numpy(), kinetic_virial=traj.kinetic_virial.cpu().numpy(),
+                   kinetic_primitive=traj.kinetic_primitive.cpu().numpy(),
+                   ring_polymer_energy=traj.ring_polymer_energy.cpu().numpy(),
+                   centroid=traj.centroid.cpu().numpy().reshape(Rec, G, n_atoms, 3),
+                   radius_of_gyration=traj.radius_of_gyration.cpu().numpy().reshape(Rec, G, n_atoms))
+        if G == 1:
+            out = {k: v[:, 0] for k, v in out.items()}
+        out['step'] = traj.step.cpu().numpy()
+        return out
+
     def relax(self, atoms_or_list, fmax: float = 0.01, max_steps: int = 500, memory: int = 16, maxstep: float = 0.2,
               alpha: float = 70.0, check_every: int = 10, fixed=None):
         """Relax one structure or a list of equally sized ones to a minimum, all stepped together on the device

@@ -18,6 +18,11 @@ PATTERNS = [
     (r'box100k.*bench.*\.json$|bench_box100k\.json$', 'bench.py --workload box100k line (BASELINE configs[4], 100k-atom periodic box)'),
     (r'bench_mode_train.*\.json$', 'bench.py --mode train line (data-parallel training step, configs[3] per-rank batch)'),
     (r'train_large\.json$', 'large-batch (1024 aspirin conformers) training step: ms/step, weight-gradient launch'),
+    (r'^md_aspirin\.json$', 'tools/bench_md.py: ms per MD step, 1024 aspirins and one (Dynamics.run / bare model loop / torch-op integrator / calculator path)'),
+    (r'^relax_aspirin\.json$', 'tools/bench_relax.py: ms per relaxation step, 1024 aspirins, one aspirin and one 4096-atom periodic system (Relaxation.run / bare model loop / share of the launch), steps to fmax 0.01'),
+    (r'^neb_aspirin\.json$', 'tools/bench_neb.py: ms per nudged-elastic-band step, 128 bands x 8 aspirin images and one band of 8 (Band.run / bare model loop / share of the launch)'),
+    (r'^remd_aspirin\.json$', 'tools/bench_remd.py: ms per step of replica-exchange MD, 128 ladders x 8 aspirin replicas and one ladder of 8, an attempt every 10 steps (ReplicaExchange.run / Dynamics.run on the same batch / us per attempt; medians of three runs, all kept)'),
+    (r'^pimd_aspirin\.json$', 'tools/bench_pimd.py: ms per step of path-integral MD, 128 ring polymers x 8 aspirin beads and one ring polymer of 8 (PathIntegral.run / Dynamics.run on the same batch / Dynamics.run on the one molecule; medians of three runs, all kept)'),
     (r'bench.*\.json$', 'bench.py line, default command (config 2: 1024 aspirin conformers, 1 GPU)'),
     (r'bench_train\.txt$', 'tools/bench_train.py: training step times across batch shapes'),
     (r'box100k.*kernel_stats\.txt$', 'rocprofv3 --kernel-trace --stats summary of the 100k-atom box step'),
@@ -49,7 +54,14 @@ PATTERNS = [
 ]
 
 
+# records of the per-feature benchmark tools carry no tree of their own: they were taken on the change that added the kernel
+WITH_KERNEL = {'md_aspirin.json': 'md', 'relax_aspirin.json': 'relax', 'neb_aspirin.json': 'neb', 'remd_aspirin.json': 'remd',
+               'pimd_aspirin.json': 'pimd'}
+
+
 def tree_of(path):
+    if os.path.basename(path) in WITH_KERNEL:
+        return f'(added with csrc/{WITH_KERNEL[os.path.basename(path)]}.hip)'
     try:
         with open(path, errors='replace') as f:
             head = f.read(4096)
