@@ -1115,6 +1115,77 @@ int nnhip_pimd_step(float* u, float* w, const float* force, const float* ctab, c
                     float* est_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Bias potentials on collective variables, on the device (csrc/bias.hip): ONE launch on `stream` turns the model's forces into the
+ * forces of the biased potential for every molecule of a batch -- static harmonic restraints (umbrella windows) and a sum of
+ * Gaussian hills shared by the walkers of a group (multiple-walker metadynamics, Raiteri et al. 2006; well-tempered heights,
+ * Barducci, Bussi and Parrinello 2008) -- and, with NNHIP_BIAS_DEPOSIT, adds one hill per walker.  The driver is
+ * newtonnet_amd/metadynamics.py, a step of it  model(pos) -> nnhip_bias_step -> nnhip_md_step.
+ *
+ * Layout: group g owns the consecutive molecules group_ptr[g] .. group_ptr[g+1] - 1, its W_g WALKERS: copies of one system, all of
+ * one atom count (int32 [G+1], on the device; group_ptr_host and mol_ptr_host are the same arrays in host memory, for the checks
+ * below); mol_ptr int32 [B+1] gives each walker's atoms.  Groups may differ in atom count and in W_g >= 1.
+ * Tables, all formed in fp64 on the host and rounded once:
+ *   cv_def int32 [B][NNHIP_BIAS_MAX_CVS][5] = (kind, a, b, c, d): the variable's kind (0 = unused) and its atoms, LOCAL to the
+ *     molecule; entries beyond the kind's arity are ignored.  A group's walkers normally share their definitions.
+ *   restraint fp32 [B][NNHIP_BIAS_MAX_CVS][2] = (kappa, s0): U = sum_d kappa_d (s_d - s0_d)^2 / 2; kappa = 0: none.
+ *   hill_par fp32 [G][4] = (1 / sigma_0^2, 1 / sigma_1^2, w0, 1 / (k_B dT)): 1 / sigma_d^2 = 0 for an unused variable, the last
+ *     entry 0 for plain metadynamics.
+ *   hills fp32 [G][capacity][4], rows (c_0, c_1, height, 0), 16-byte aligned: rows 0 .. n_deposits W_g - 1 of group g are its hills.
+ * Collective variables, on the positions AS STORED (unwrapped; no minimum image is taken), every operation in fp32 and one rounding
+ * (tests/bias_ref.py restates the launch in fp64 with a bound):
+ *   NNHIP_BIAS_DISTANCE (i, j):   s = |x_j - x_i|
+ *   NNHIP_BIAS_ANGLE (i, j, k):   a = x_i - x_j, b = x_k - x_j, c = a x b;  s = atan2f(|c|, a.b) in [0, pi];
+ *                                 ds/dx_i = (a x c) / (|a|^2 |c|), ds/dx_k = (c x b) / (|b|^2 |c|), ds/dx_j = -(their sum)
+ *   NNHIP_BIAS_TORSION (i, j, k, l):  b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k, n1 = b1 x b2, n2 = b2 x b3;
+ *                                 s = atan2f(|b2| b1.n2, n1.n2) in (-pi, pi];  Blondel and Karplus 1996:  g_i = -|b2| n1 / |n1|^2,
+ *                                 g_l = |b2| n2 / |n2|^2,  with p = b1.b2 / |b2|^2, q = b3.b2 / |b2|^2 and t = q g_l - p g_i:
+ *                                 g_j = t - g_i,  g_k = -(t + g_l).  A DIFFERENCE of a torsion is wrapped: delta <- delta - P rint(
+ *                                 delta / P) with P = fl32(2 pi).
+ *   An unused variable has s = 0 and no gradient.  Where a gradient is undefined (|r| = 0, |a x b| = 0, |n1| = 0 or |n2| = 0, or any
+ *   row of it not finite) the variable contributes NO force and bit d of status_out[b] is set; its value still enters V and U.
+ * One launch for molecule b = walker j of group g, with H = n_deposits W_g:
+ *   1. delta_hd = s_d - c_hd (wrapped for a torsion);  a_hd = delta_hd / sigma_d^2;  e_h = a_h0 delta_h0 + a_h1 delta_h1;
+ *      t_h = height_h expf(-e_h / 2);  V = sum_{h < H} t_h,  G_d = sum_h t_h a_hd  (= -dV/ds_d).  Thread t adds the hills t, t + 256,
+ *      ... in ascending order; the partial sums go through a fixed tree (wave butterfly, then the four waves in order).
+ *   2. r_d = s_d - s0_d (wrapped for a torsion);  U = sum_d (kappa_d r_d) r_d / 2;  c_d = kappa_d r_d - G_d.
+ *   3. force_out[a] = force_in[a] - sum_d c_d ds_d/dx_a.  An atom in no variable, and any component whose bias part is exactly 0,
+ *      is a bitwise copy of force_in; a molecule without variables is a pure copy.
+ *   4. cv_out[b] = (s_0, s_1);  bias_out[b] = (V, U);  status_out[b] = the bits above.
+ *   5. With NNHIP_BIAS_DEPOSIT: hills[g][H + j] = (s_0, s_1, w0 expf(-V / (k_B dT)), 0), V the bias BEFORE any deposit of this
+ *      launch.  The rows written are exactly the rows no workgroup reads in this launch, and the count is a host integer: no
+ *      race, no counter on the device, no atomics, no host read.
+ * One workgroup of NNHIP_BIAS_THREADS threads per molecule, the molecules by a grid-stride loop; every thread forms the variables
+ * and their gradient rows itself (the same bits in every thread, no communication).  No float atomics: a group's outputs depend
+ * neither on the other groups of the batch nor on the group's place in it.
+ * State words no driver can leave behind -- a kind outside 0 .. 3, an atom index outside the molecule, hills that would leave the
+ * capacity by the DEVICE's group_ptr -- make the kernel copy that molecule's forces unchanged and set NNHIP_BIAS_STATUS_INVALID
+ * (cv_out and bias_out get 0, no hill is written); a molecule whose device offsets leave the arrays is not touched at all.
+ * NNHIP_E_INVALID, nothing launched: NULL mandatory pointers (everything but stream), force_out overlapping force_in or pos, hills
+ * not 16-byte aligned, negative counts, group_ptr_host not running from 0 to n_mol or mol_ptr_host not from 0 to n_atoms, an empty
+ * group, walkers of one group with unequal atom counts, n_deposits < 0, (n_deposits + (deposit ? 1 : 0)) W_g > capacity, unknown
+ * flag bits.  n_mol == 0 is success without a launch.
+ *
+ * nnhip_bias_eval: V of group `group` at n_points given points (fp32 [n_points][2]), through the same hill sum as step 1 (one
+ * workgroup per point), over the first n_hills rows; period0 / period1: the period of each coordinate (fl32(2 pi) for a torsion,
+ * 0 for none).  v_out fp32 [n_points].  Refused: NULL pointers, negative counts, group outside 0 .. n_groups - 1, n_hills > capacity,
+ * a negative or non-finite period.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_BIAS_MAX_CVS 2
+#define NNHIP_BIAS_DISTANCE 1
+#define NNHIP_BIAS_ANGLE 2
+#define NNHIP_BIAS_TORSION 3
+#define NNHIP_BIAS_DEPOSIT 1
+#define NNHIP_BIAS_THREADS 256
+#define NNHIP_BIAS_STATUS_INVALID 4
+int nnhip_bias_step(const float* pos, const float* force_in, const int32_t* mol_ptr, const int32_t* mol_ptr_host,
+                    const int32_t* group_ptr, const int32_t* group_ptr_host, const int32_t* cv_def, const float* restraint,
+                    const float* hill_par, float* hills, int32_t capacity, int32_t n_deposits, int32_t flags, int32_t n_groups,
+                    int32_t n_mol, int32_t n_atoms, float* force_out, float* cv_out, float* bias_out, int32_t* status_out,
+                    void* stream);
+int nnhip_bias_eval(const float* hills, const float* hill_par, const float* points, float period0, float period1, int32_t group,
+                    int32_t capacity, int32_t n_hills, int32_t n_points, int32_t n_groups, float* v_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Product form of the dense kernels.  1 (default): the 128x128 linears of the hot path (edge MLPs, node MLPs, equiv_update
  * and their adjoints / tangents, SiLU models) form each fp32 product from two scaled f16 pieces per operand on
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation (csrc/mlp128s.hip, node128s.hip); 0 (environment NNHIP_MLP_SPLIT=0,

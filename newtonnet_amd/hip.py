@@ -840,6 +840,88 @@ def pimd_step(u: torch.Tensor, w: torch.Tensor, force: torch.Tensor, ctab: torch
            'nnhip_pimd_step')
 
 
+BIAS_MAX_CVS, BIAS_THREADS = _K['NNHIP_BIAS_MAX_CVS'], _K['NNHIP_BIAS_THREADS']
+BIAS_DISTANCE, BIAS_ANGLE, BIAS_TORSION = _K['NNHIP_BIAS_DISTANCE'], _K['NNHIP_BIAS_ANGLE'], _K['NNHIP_BIAS_TORSION']   # kinds
+BIAS_DEPOSIT = _K['NNHIP_BIAS_DEPOSIT']                         # flag of nnhip_bias_step
+BIAS_STATUS_INVALID = _K['NNHIP_BIAS_STATUS_INVALID']           # status bit; bits 0 and 1: variable 0 / 1 has no gradient here
+
+
+def bias_step(pos: torch.Tensor, force_in: torch.Tensor, mol_ptr: torch.Tensor, mol_ptr_host: torch.Tensor, group_ptr: torch.Tensor,
+              group_ptr_host: torch.Tensor, cv_def: torch.Tensor, restraint: torch.Tensor, hill_par: torch.Tensor,
+              hills: torch.Tensor, n_deposits: int, flags: int, force_out: torch.Tensor, cv_out: torch.Tensor,
+              bias_out: torch.Tensor, status_out: torch.Tensor):
+    """One launch of the bias on collective variables (nnhip_bias_step, csrc/bias.hip; the contract is in
+    include/newtonnet_hip.h) on the current stream, for the G groups group_ptr (int32 [G+1], device; group_ptr_host and
+    mol_ptr_host: the same arrays on the host) delimits among the B molecules of mol_ptr (int32 [B+1]).  pos, force_in [N,3], cv_def
+    (int32 [B,2,5]), restraint [B,2,2] and hill_par [G,4] are read; hills [G,capacity,4] is read below row n_deposits W and, with
+    BIAS_DEPOSIT, written at the W rows from there; force_out [N,3], cv_out, bias_out [B,2] and status_out (int32 [B]) are
+    written: these must be contiguous tensors of exactly that type (a copy would take the result away).  force_out may overlap
+    neither force_in nor pos."""
+    for name, t in (('mol_ptr', mol_ptr), ('group_ptr', group_ptr), ('mol_ptr_host', mol_ptr_host), ('group_ptr_host', group_ptr_host)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
+            raise ValueError(f'{name}: contiguous int32 expected')
+    if group_ptr_host.device.type != 'cpu' or group_ptr_host.numel() != group_ptr.numel():
+        raise ValueError('group_ptr_host: the host copy of group_ptr expected')
+    if mol_ptr_host.device.type != 'cpu' or mol_ptr_host.numel() != mol_ptr.numel():
+        raise ValueError('mol_ptr_host: the host copy of mol_ptr expected')
+    if isinstance(n_deposits, bool) or int(n_deposits) != n_deposits or not 0 <= n_deposits < 2 ** 31:
+        raise ValueError(f'n_deposits: an integer in 0 .. 2^31 - 1 expected (got {n_deposits!r})')
+    if isinstance(flags, bool) or int(flags) != flags or not 0 <= flags < 2 ** 31:
+        raise ValueError(f'flags: an integer >= 0 expected (got {flags!r})')
+    dev, B, G = mol_ptr.device, mol_ptr.numel() - 1, group_ptr.numel() - 1
+    if not isinstance(force_out, torch.Tensor) or force_out.dim() != 2 or force_out.shape[1] != 3:
+        raise ValueError('force_out: a tensor [N,3] expected')
+    N = force_out.shape[0]
+    if not isinstance(hills, torch.Tensor) or hills.dim() != 3 or hills.shape[0] != G or hills.shape[2] != 4:
+        raise ValueError(f'hills: [{G},capacity,4] expected')
+    capacity = hills.shape[1]
+    for name, t, dtype, numel in (('hills', hills, torch.float32, G * capacity * 4), ('force_out', force_out, torch.float32, 3 * N),
+                                  ('cv_out', cv_out, torch.float32, 2 * B), ('bias_out', bias_out, torch.float32, 2 * B),
+                                  ('status_out', status_out, torch.int32, B)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
+    pos, force_in, restraint, hill_par = (_f32c(t, name) for name, t in (('pos', pos), ('force_in', force_in),
+                                                                         ('restraint', restraint), ('hill_par', hill_par)))
+    if cv_def.dtype != torch.int32:
+        raise ValueError('cv_def: int32 expected')
+    cv_def = cv_def.contiguous()
+    for name, t, numel in (('pos', pos, 3 * N), ('force_in', force_in, 3 * N), ('cv_def', cv_def, B * BIAS_MAX_CVS * 5),
+                           ('restraint', restraint, B * BIAS_MAX_CVS * 2), ('hill_par', hill_par, G * 4), ('group_ptr', group_ptr, G + 1)):
+        if t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+    _check(lib().nnhip_bias_step(_ptr(pos), _ptr(force_in), _ptr(mol_ptr), _ptr(mol_ptr_host), _ptr(group_ptr), _ptr(group_ptr_host),
+                                 _ptr(cv_def), _ptr(restraint), _ptr(hill_par), _ptr(hills), capacity, int(n_deposits), int(flags), G,
+                                 B, N, _ptr(force_out), _ptr(cv_out), _ptr(bias_out), _ptr(status_out), _stream(dev)),
+           'nnhip_bias_step')
+
+
+def bias_eval(hills: torch.Tensor, hill_par: torch.Tensor, group: int, n_hills: int, points: torch.Tensor, periods=(0.0, 0.0)):
+    """V of group `group` at points [M,2] over the first n_hills rows of its hill list (nnhip_bias_eval, csrc/bias.hip: the hill
+    sum of nnhip_bias_step, one workgroup per point); periods: the period of each coordinate as an fp32 value (0: none).
+    Returns fp32 [M]."""
+    if not isinstance(hills, torch.Tensor) or hills.dim() != 3 or hills.shape[2] != 4:
+        raise ValueError('hills: [G,capacity,4] expected')
+    G, capacity = hills.shape[0], hills.shape[1]
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 2:
+        raise ValueError('points: a tensor [M,2] expected')
+    for name, v in (('group', group), ('n_hills', n_hills)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f'{name}: an integer expected (got {v!r})')
+    if not 0 <= group < G or not 0 <= n_hills <= capacity:
+        raise ValueError(f'group in 0 .. {G - 1} and n_hills in 0 .. {capacity} expected (got {group}, {n_hills})')
+    hills, hill_par, points = _f32c(hills, 'hills'), _f32c(hill_par, 'hill_par'), _f32c(points, 'points')
+    dev = hills.device
+    if hill_par.numel() != 4 * G or hill_par.device != dev or points.device != dev:
+        raise ValueError(f'hill_par: {4 * G} values, and points, on {dev} expected')
+    p0, p1 = (float(p) for p in periods)
+    out = torch.empty(points.shape[0], dtype=torch.float32, device=dev)
+    if points.shape[0] == 0:
+        return out
+    _check(lib().nnhip_bias_eval(_ptr(hills), _ptr(hill_par), _ptr(points), p0, p1, int(group), capacity, int(n_hills),
+                                 points.shape[0], G, _ptr(out), _stream(dev)), 'nnhip_bias_eval')
+    return out
+
+
 def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[e] = x[idx[e]] (idx int32)."""
     x = _f32c(x, 'x')

@@ -808,6 +808,22 @@ class NewtonNet(nn.Module):
                                centroid_friction=centroid_friction, mode_friction=mode_friction, masses=masses, generator=generator,
                                bead_positions=bead_positions, bead_velocities=bead_velocities)
 
+    def metadynamics(self, z, pos, cell, batch, cvs, temperature, friction, hill_height, hill_width, pace, bias_factor=None,
+                     walkers=1, restraint_k=None, restraint_center=None, timestep=0.5, masses=None, fixed=None, generator=None,
+                     hill_capacity=1024):
+        """Multiple-walker (well-tempered) metadynamics and umbrella restraints on the device: a
+        newtonnet_amd.metadynamics.Metadynamics, a Dynamics over G systems x `walkers` walkers whose run(n_steps, record_every)
+        adds ONE launch per step (csrc/bias.hip) -- collective variables and their gradients, the sum over the hills a group's
+        walkers share, harmonic restraints, the chain rule into the forces and, every `pace` steps, one new hill per walker -- with
+        no host read in the loop.  cvs: 0 .. 2 of ('distance', i, j), ('angle', i, j, k), ('torsion', i, j, k, l) for all systems, or
+        one list per system; hill_height (eV), hill_width (per variable); bias_factor None = plain, > 1 = well-tempered; pace = 0
+        or hill_height = 0 leaves the restraints alone (umbrella sampling).  Eval mode only; needs the 'energy' and
+        'gradient_force' heads."""
+        from newtonnet_amd import metadynamics as _m
+        return _m.Metadynamics(self, z, pos, cell, batch, cvs, temperature, friction, hill_height, hill_width, pace,
+                               bias_factor=bias_factor, walkers=walkers, restraint_k=restraint_k, restraint_center=restraint_center,
+                               timestep=timestep, masses=masses, fixed=fixed, generator=generator, hill_capacity=hill_capacity)
+
     def relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
         """Relaxation of every molecule of the batch to a minimum on the device: a newtonnet_amd.relax.Relaxation whose
         run(max_steps, check_every, record_every) steps them together, one force evaluation and one L-BFGS launch (csrc/relax.hip)

@@ -23,6 +23,7 @@ PATTERNS = [
     (r'^neb_aspirin\.json$', 'tools/bench_neb.py: ms per nudged-elastic-band step, 128 bands x 8 aspirin images and one band of 8 (Band.run / bare model loop / share of the launch)'),
     (r'^remd_aspirin\.json$', 'tools/bench_remd.py: ms per step of replica-exchange MD, 128 ladders x 8 aspirin replicas and one ladder of 8, an attempt every 10 steps (ReplicaExchange.run / Dynamics.run on the same batch / us per attempt; medians of three runs, all kept)'),
     (r'^pimd_aspirin\.json$', 'tools/bench_pimd.py: ms per step of path-integral MD, 128 ring polymers x 8 aspirin beads and one ring polymer of 8 (PathIntegral.run / Dynamics.run on the same batch / Dynamics.run on the one molecule; medians of three runs, all kept)'),
+    (r'^metad_aspirin\.json$', 'tools/bench_metad.py: ms per step of biased MD on collective variables, 1024 aspirin walkers (1 group of 1024, 128 groups of 8) and one group of 8, with 0 / 1e4 / 1e5 hills per group (Metadynamics.run / Dynamics.run on the same batch; medians of three runs, all kept)'),
     (r'bench.*\.json$', 'bench.py line, default command (config 2: 1024 aspirin conformers, 1 GPU)'),
     (r'bench_train\.txt$', 'tools/bench_train.py: training step times across batch shapes'),
     (r'box100k.*kernel_stats\.txt$', 'rocprofv3 --kernel-trace --stats summary of the 100k-atom box step'),
@@ -56,7 +57,7 @@ PATTERNS = [
 
 # records of the per-feature benchmark tools carry no tree of their own: they were taken on the change that added the kernel
 WITH_KERNEL = {'md_aspirin.json': 'md', 'relax_aspirin.json': 'relax', 'neb_aspirin.json': 'neb', 'remd_aspirin.json': 'remd',
-               'pimd_aspirin.json': 'pimd'}
+               'pimd_aspirin.json': 'pimd', 'metad_aspirin.json': 'bias'}
 
 
 def tree_of(path):
