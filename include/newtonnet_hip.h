@@ -914,6 +914,73 @@ int nnhip_md_step(const float* pos_in, float* vel, const float* force, const flo
 int nnhip_md_kinetic(const float* ke, const int32_t* mol_ptr, int32_t n_mol, float* out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Molecular dynamics with bond-length constraints on the device (csrc/rattle.hip): nnhip_md_step's launch for molecules whose
+ * constrained distances |x_i - x_j| = d_c are kept by SHAKE / RATTLE.  Constrained BAOAB ("g-BAOAB", Leimkuhler & Matthews 2016,
+ * one RATTLE per half drift); c1 = 1 with sigma = noise = NULL is velocity-Verlet RATTLE in two half drifts.  All in fp32, every
+ * operation one rounding (tests/rattle_ref.py restates the chain in fp64 and emulates it in fp32).
+ *
+ * Tables (device, with host copies of the three offset tables; the caller keeps them equal):
+ *   mol_ptr      int32 [B+1]   atom offsets of the molecules
+ *   mol_col_ptr  int32 [B+1]   molecule b owns the colours mol_col_ptr[b] .. mol_col_ptr[b+1] - 1 (none: an unconstrained molecule)
+ *   col_ptr      int32 [K+1]   colour k owns the constraints col_ptr[k] .. col_ptr[k+1] - 1; K = n_col; C = col_ptr[K]
+ *   con_pair     int32 [C,2]   the two atoms of a constraint, counted from the first atom of its molecule (0 .. n_b - 1)
+ *   con_d2       fp32  [C]     d_c^2
+ * Constraints are thus sorted by molecule and, within one, by colour.  No two constraints of a colour may share an atom (the
+ * caller's colouring; the lanes of a wave take a colour's constraints side by side).  The offset tables are checked on their host
+ * copies; the kernel skips a constraint whose atoms lie outside its molecule (the molecule counts as failed) and never reads or
+ * writes outside the arrays whatever the device tables hold.
+ *
+ * One launch, for a molecule WITH constraints.  x_first is the INPUT position of its first atom, y = fl32(x - x_first) per
+ * coordinate, w = inv_mass (0 for a fixed atom, whose hk, sigma and velocity are 0 as well):
+ *   NNHIP_MD_FINISH:    v = fma(hk_i, F, v);  PROJECT v at y;  ke_out[i] = (0.5 mass_i)(vx vx + vy vy + vz vz) as nnhip_md_step
+ *   NNHIP_MD_BEGIN:     v = fma(hk_i, F, v);  PROJECT v at y;  DRIFT;  [v = fma(sigma_i, noise, c1 v);  PROJECT v at y]  DRIFT
+ *                       (the bracket is skipped when noise == NULL)
+ *     DRIFT:            r = y;  y = fma(dth, v, r);  D = 0;  SHAKE y along r;  v = fma(D, inv_dth, v);  PROJECT v at y
+ *                       D_i is the sum of the updates SHAKE applied to atom i (= y'' - y'), accumulated by the same fmas as y: the
+ *                       difference of the two positions would carry 2^-24 |y| / dth per update into the velocities
+ *   NNHIP_MDC_PROJECT:  r = y;  SHAKE y along r;  PROJECT v at y          (valid alone: imposes the constraints on a start state)
+ *   pos_out = fl32(x_first + y) with BEGIN or PROJECT -- but an atom with inv_mass = 0 gets pos_in bit for bit; vel in place.
+ * FINISH | BEGIN performs exactly the operations of FINISH followed by BEGIN with the same forces.
+ *   SHAKE, constraint (i, j, d2):  s = y_i - y_j;  q = r_i - r_j;  e = d2 - s.s;  applied iff |e| > tol d2:
+ *                                  g = e / ((2 (w_i + w_j)) (s.q));  y_i = fma(g w_i, q, y_i);  y_j = fma(-(g w_j), q, y_j);
+ *                                  D_i = fma(g w_i, q, D_i);  D_j = fma(-(g w_j), q, D_j)
+ *   PROJECT, constraint (i, j, d2): q = y_i - y_j;  p = q.(v_i - v_j);  applied iff |p| dth > tol d2:
+ *                                  g = p / ((w_i + w_j) d2);  v_i = fma(-(g w_i), q, v_i);  v_j = fma(g w_j, q, v_j)
+ *   (dot products: fma(az, bz, fma(ay, by, ax bx)).)  Both are Gauss-Seidel sweeps over the molecule's constraints in colour order;
+ *   a solve ends when a whole sweep applied no update, or after max_iter sweeps.  Breakdown guard: a SHAKE constraint with
+ *   s.q <= NNHIP_MDC_GUARD d2 (the bond turned by almost a right angle within half a step), and any constraint with w_i + w_j <= 0,
+ *   d2 <= 0, i == j or an atom outside its molecule, is SKIPPED -- nothing divides by a vanishing number: a failed solve may leave
+ *   a wrong geometry, never a non-finite store that finite inputs did not hold.
+ *   n_failed[b] (sticky, zeroed by the caller) is incremented ONCE per launch in which a solve of molecule b ended at max_iter with
+ *   its last sweep still updating, or skipped a constraint;  n_sweeps[b] = the largest sweep count of this launch's solves (the
+ *   closing sweep without an update counts; 0 for an unconstrained molecule).
+ * The result does not depend on which lane takes which constraint: bitwise repeatable, a molecule's outputs are independent of the
+ * rest of the batch and of its place in it.  The molecule-relative y makes convergence independent of where a molecule sits
+ * (unwrapped periodic positions drift far from the origin); what the STORED positions can show is tol plus the rounding of the
+ * stored coordinates.
+ * A molecule WITHOUT constraints takes nnhip_md_step's chain bit for bit (PROJECT: pos_out = pos_in, vel untouched).
+ *
+ * One wave64 per molecule, its y, r, v, D, w in LDS (13 floats per atom): a molecule with constraints has at most nnhip_md_constrained_max_atoms() =
+ * NNHIP_MDC_MAX_ATOMS atoms -- a kernel for batches of molecules, not for one large system.
+ * NNHIP_E_INVALID, nothing launched and nothing written: pos_out overlapping pos_in (the reason is given at nnhip_md_step), a
+ * constrained molecule above the bound, NULL mandatory pointers or tables, offset tables (host copies) that do not start at 0,
+ * decrease, or do not end at n_atoms / n_col, n_mol < 1 with n_atoms > 0, tol <= 0 (or NaN), max_iter < 1, flags other than FINISH,
+ * BEGIN, FINISH | BEGIN or PROJECT, sigma without noise or the reverse, ke_out without mass and FINISH.  force and hk may be NULL
+ * with PROJECT, pos_out with FINISH alone.  n_atoms == 0 is success without a launch.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_MDC_PROJECT 4
+#define NNHIP_MDC_MAX_ATOMS 256
+#define NNHIP_MDC_GUARD 0.1f
+int nnhip_md_constrained_max_atoms(void);
+int nnhip_md_step_constrained(const float* pos_in, float* vel, const float* force, const float* hk, const float* mass,
+                              const float* inv_mass, const float* sigma, const float* noise, float dth, float inv_dth, float c1,
+                              int32_t flags, int32_t n_atoms, const int32_t* mol_ptr, const int32_t* mol_ptr_host, int32_t n_mol,
+                              const int32_t* con_pair, const float* con_d2, const int32_t* mol_col_ptr,
+                              const int32_t* mol_col_ptr_host, const int32_t* col_ptr, const int32_t* col_ptr_host, int32_t n_col,
+                              float tol, int32_t max_iter, float* pos_out, float* ke_out, int32_t* n_failed, int32_t* n_sweeps,
+                              void* stream);
+
+/* --------------------------------------------------------------------------
  * Geometry relaxation on the device (csrc/relax.hip): ONE launch on `stream` moves every molecule of a batch by one L-BFGS step
  * from the forces just evaluated.  L-BFGS without line search in ASE's convention (fixed H0 = 1 / alpha, the longest atomic
  * displacement capped at maxstep); every molecule has its own history, one wave64 works on one molecule, every reduction is a

@@ -95,7 +95,10 @@ class Trajectory:
     potential_energy  fp32 [R,B]     the model's energy at pos
     kinetic_energy    fp32 [R,B]     sum of m v^2 / 2 per molecule
     total_energy      fp32 [R,B]     their sum;  temperature fp32 [R,B] = 2 KE / (3 n_b k_B)
+                                     (a run with C_b constrained bond lengths in molecule b: 2 KE / ((3 n_b - C_b) k_B))
     """
+
+    _dof = None          # fp32 [B] degrees of freedom 3 n_b - C_b of a constrained run (Dynamics sets it); None: 3 n_b
 
     def __init__(self, step, pos, vel, potential_energy, kinetic_energy, counts):
         self.step, self.pos, self.vel = step, pos, vel
@@ -107,6 +110,8 @@ class Trajectory:
 
     @property
     def temperature(self):
+        if self._dof is not None:
+            return 2.0 * self.kinetic_energy / (K_BOLTZMANN * self._dof.clamp(min=1).float())
         return 2.0 * self.kinetic_energy / (3.0 * K_BOLTZMANN * self._counts.clamp(min=1).float())
 
 
@@ -157,6 +162,31 @@ def _check_devices(pos, generator, **tensors):
     return dev
 
 
+def _check_constraint_arguments(constraints, tolerance, max_iter, dev):
+    """the form of the `constraints` argument (the pairs themselves are checked by constraints.prepare)"""
+    if constraints is None:
+        return
+    if not (float(tolerance) > 0.0 and math.isfinite(float(tolerance))):
+        raise ValueError(f'constraint_tolerance: a finite value > 0 expected (got {tolerance!r})')
+    if int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f'constraint_max_iter: an integer >= 1 expected (got {max_iter!r})')
+    if isinstance(constraints, str):
+        if constraints != 'h-bonds':
+            raise ValueError(f"constraints: (pairs, lengths), 'h-bonds' or None expected (got {constraints!r})")
+        return
+    if not isinstance(constraints, (tuple, list)) or len(constraints) != 2:
+        raise ValueError(f"constraints: (pairs, lengths), 'h-bonds' or None expected (got {type(constraints).__name__})")
+    pairs, lengths = constraints
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError('constraints: pairs, an int64 tensor [C,2] of atom indices, expected')
+    if lengths is not None and (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.float32
+                                or tuple(lengths.shape) != (pairs.shape[0],)):
+        raise ValueError(f'constraints: lengths, a float32 tensor [{pairs.shape[0]}] or None, expected')
+    for name, t in (('pairs', pairs), ('lengths', lengths)):
+        if t is not None and t.device.type != 'cpu' and t.device != dev:
+            raise ValueError(f'constraints: {name} is on {t.device}, pos on {dev}')
+
+
 class Dynamics:
     """B molecules advanced together on the device.
 
@@ -167,10 +197,21 @@ class Dynamics:
     unit (None: Maxwell-Boltzmann at `temperature` when one is given, else zero).  fixed: bool [N], atoms that never move.
     generator: a generator of the device for the initial velocities and the noise (None: torch's global one).
 
+    constraints: None, or bond lengths kept by SHAKE / RATTLE inside the step's one launch (nnhip_md_step_constrained,
+    csrc/rattle.hip; constrained BAOAB): (pairs int64 [C,2] of global atom indices, lengths fp32 [C] in
+    Angstrom or None = the present distances), on the host or on the device of pos, or the string 'h-bonds' (hydrogen_constraints).
+    Construction imposes the lengths on the initial positions and makes the initial velocities tangent (for a Maxwell-Boltzmann
+    draw that gives the constrained distribution), and raises ValueError when that fails.  constraint_tolerance: relative, on
+    d^2 (| |r|^2 - d^2 | <= tol d^2 in the solver's molecule-relative fp32 coordinates); constraint_max_iter: sweeps per solve.
+    A molecule with constraints has at most hip.MDC_MAX_ATOMS atoms.  Distances are taken on the positions as stored (no minimum
+    image): a constrained bond must not straddle a periodic boundary in the input.
+
     Periodic molecules: positions stay unwrapped; the model's neighbor list takes the minimum image of every pair itself."""
 
+    _con = _dof = None       # no constraints (a subclass that builds its own state never sets them)
+
     def __init__(self, model, z, pos, cell, batch, masses=None, velocities=None, temperature=None, friction=0.0, timestep=0.5,
-                 fixed=None, generator=None):
+                 fixed=None, generator=None, constraints=None, constraint_tolerance=1e-5, constraint_max_iter=150):
         # ---- everything that can be refused without touching the device
         N, B, timestep, friction = _check_system(model, z, pos, cell, batch, masses, velocities, fixed, timestep, friction)
         _check_temperature(temperature, B)
@@ -178,6 +219,7 @@ class Dynamics:
             raise ValueError('friction > 0 (Langevin dynamics) needs a temperature')
         dev = _check_devices(pos, generator, z=z, cell=cell, batch=batch, masses=masses, velocities=velocities, fixed=fixed,
                              temperature=temperature)
+        _check_constraint_arguments(constraints, constraint_tolerance, constraint_max_iter, dev)
         # ---- state
         self.model, self.z, self.cell, self.batch = model, z, cell, batch
         self.n_atoms, self.n_mol = N, B
@@ -213,6 +255,63 @@ class Dynamics:
             self._ke_atom = torch.zeros(N, dtype=torch.float32, device=dev)
             self._ke = torch.zeros(B, dtype=torch.float32, device=dev)
             self._force = self._energy = None
+            self._con = self._dof = None
+            if constraints is not None:
+                self._init_constraints(constraints, float(constraint_tolerance), int(constraint_max_iter), free)
+
+    def _init_constraints(self, constraints, tol, max_iter, free):
+        """check, colour and upload the constraints, then impose them on the initial state with one NNHIP_MDC_PROJECT launch"""
+        from newtonnet_amd import constraints as _c
+        dev, N, B = self._vel.device, self.n_atoms, self.n_mol
+        pos0 = self._pos[0]
+        if isinstance(constraints, str):
+            pairs, lengths = _c.hydrogen_constraints(self.z, pos0, self.batch)[0], None       # (the present distances, in fp64)
+        else:
+            pairs, lengths = constraints
+        prep = _c.prepare(pairs.detach().cpu().numpy(), None if lengths is None else lengths.detach().cpu().numpy(),
+                          self.batch.detach().cpu().numpy(), B, None if free is None else (~free).cpu().numpy(),
+                          max_atoms=hip.MDC_MAX_ATOMS)
+        if lengths is None:
+            x = pos0.cpu().double().numpy()
+            d2 = ((x[prep.pairs[:, 0]] - x[prep.pairs[:, 1]]) ** 2).sum(1)
+        else:
+            d2 = lengths.detach().cpu().double().numpy()[prep.order] ** 2
+        self._con = _c.device_tables(prep, d2.astype(np.float32), self._mol_ptr)
+        self._con_tol, self._con_max_iter = tol, max_iter
+        self.constraint_pairs = torch.from_numpy(prep.pairs).to(dev)                  # (sorted by molecule and colour)
+        self.constraint_lengths = torch.from_numpy(np.sqrt(d2).astype(np.float32)).to(dev)
+        w = 1.0 / self.masses.double()
+        self._inv_mass = (w if free is None else w * free).float().contiguous()
+        self._inv_dth = float(np.float32(1.0 / self._dth))
+        self._dof = (3 * self._counts - torch.from_numpy(prep.per_mol).to(dev)).float()
+        self._n_failed = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._n_sweeps = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._constrained_step(hip.MDC_PROJECT, pos_out=self._pos[1])
+        self._cur = 1
+        failed = self._n_failed.cpu()
+        if bool(failed.any()):
+            raise ValueError(f'constraints: the initial positions could not be brought onto the constraints within {max_iter} sweeps '
+                             f'(molecules {torch.nonzero(failed).reshape(-1).tolist()[:8]}): are the lengths far from the geometry?')
+
+    def _constrained_step(self, flags, pos_out=None, force=None, noise=None, ke_out=None):
+        hip.md_step_constrained(self._pos[self._cur], self._vel, force, self._hk, self._inv_mass, self._dth, self._inv_dth, self._c1,
+                                flags, self._con, self._con_tol, self._con_max_iter, self._n_failed, self._n_sweeps,
+                                pos_out=pos_out, mass=self.masses, sigma=None if noise is None else self._sigma, noise=noise,
+                                ke_out=ke_out)
+
+    @property
+    def constraint_failures(self):
+        """int32 [B]: the launches in which a constraint solve of the molecule did not converge or met the breakdown guard"""
+        if self._con is None:
+            raise AttributeError('this Dynamics has no constraints')
+        return self._n_failed.clone()
+
+    @property
+    def constraint_sweeps(self):
+        """int32 [B]: the largest sweep count among the solves of the last launch"""
+        if self._con is None:
+            raise AttributeError('this Dynamics has no constraints')
+        return self._n_sweeps.clone()
 
     # ------------------------------------------------------------------------------------------
     def _evaluate(self):
@@ -224,8 +323,11 @@ class Dynamics:
 
     def _finish(self):
         """the second half kick with the current forces, and the kinetic energies of the full-step velocities"""
-        hip.md_step(None, self._vel, self._force, self._hk, self._dth, self._c1, hip.MD_FINISH, mass=self.masses,
-                    ke_out=self._ke_atom)
+        if self._con is not None:
+            self._constrained_step(hip.MD_FINISH, force=self._force, ke_out=self._ke_atom)
+        else:
+            hip.md_step(None, self._vel, self._force, self._hk, self._dth, self._c1, hip.MD_FINISH, mass=self.masses,
+                        ke_out=self._ke_atom)
         hip.md_kinetic(self._ke_atom, self._mol_ptr, out=self._ke)
 
     def _ensure_state(self):
@@ -233,8 +335,11 @@ class Dynamics:
             with torch.no_grad():
                 self._evaluate()
                 # (kinetic energies of the initial velocities from the kernel that computes every later one: a kick with zero forces)
-                hip.md_step(None, self._vel, torch.zeros_like(self._force), self._hk, self._dth, self._c1, hip.MD_FINISH,
-                            mass=self.masses, ke_out=self._ke_atom)
+                if self._con is not None:
+                    self._constrained_step(hip.MD_FINISH, force=torch.zeros_like(self._force), ke_out=self._ke_atom)
+                else:
+                    hip.md_step(None, self._vel, torch.zeros_like(self._force), self._hk, self._dth, self._c1, hip.MD_FINISH,
+                                mass=self.masses, ke_out=self._ke_atom)
                 hip.md_kinetic(self._ke_atom, self._mol_ptr, out=self._ke)
 
     @property
@@ -301,10 +406,13 @@ class Dynamics:
 
     def _new_trajectory(self, cls, recorded):
         R, N, B, dev = len(recorded), self.n_atoms, self.n_mol, self._vel.device
-        return cls(torch.tensor([self.step_count + k for k in recorded], dtype=torch.int64, device=dev),
+        traj = cls(torch.tensor([self.step_count + k for k in recorded], dtype=torch.int64, device=dev),
                    torch.empty(R, N, 3, dtype=torch.float32, device=dev), torch.empty(R, N, 3, dtype=torch.float32, device=dev),
                    torch.empty(R, B, dtype=torch.float32, device=dev), torch.empty(R, B, dtype=torch.float32, device=dev),
                    self._counts)
+        if self._dof is not None:
+            traj._dof = self._dof
+        return traj
 
     def _advance(self, pending: bool):
         """the noise of a step, the first half of it (with the second half kick of the step before, if that is still pending) and
@@ -313,9 +421,12 @@ class Dynamics:
         if self._sigma is not None:
             noise = torch.randn((self.n_atoms, 3), generator=self.generator, device=self._vel.device, dtype=torch.float32)
         other = 1 - self._cur
-        hip.md_step(self._pos[self._cur], self._vel, self._force, self._hk, self._dth, self._c1,
-                    (hip.MD_FINISH | hip.MD_BEGIN) if pending else hip.MD_BEGIN, pos_out=self._pos[other],
-                    sigma=self._sigma, noise=noise)
+        flags = (hip.MD_FINISH | hip.MD_BEGIN) if pending else hip.MD_BEGIN
+        if self._con is not None:
+            self._constrained_step(flags, pos_out=self._pos[other], force=self._force, noise=noise)
+        else:
+            hip.md_step(self._pos[self._cur], self._vel, self._force, self._hk, self._dth, self._c1, flags,
+                        pos_out=self._pos[other], sigma=self._sigma, noise=noise)
         self._cur = other
         self._evaluate()
 

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -631,6 +631,75 @@ def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tens
         return out.zero_()
     _check(lib().nnhip_md_kinetic(_ptr(ke), _ptr(mol_ptr), B, _ptr(out), _stream(ke.device)), 'nnhip_md_kinetic')
     return out
+
+
+MDC_PROJECT, MDC_MAX_ATOMS = _K['NNHIP_MDC_PROJECT'], _K['NNHIP_MDC_MAX_ATOMS']      # of nnhip_md_step_constrained
+
+
+class ConstraintTables(NamedTuple):
+    """The constraint tables of nnhip_md_step_constrained (the layout is in include/newtonnet_hip.h): int32 offset tables on the
+    device with their host copies, con_pair int32 [C,2] (atoms counted within their molecule) and con_d2 fp32 [C] on the device."""
+    mol_ptr: torch.Tensor
+    mol_ptr_host: torch.Tensor
+    mol_col_ptr: torch.Tensor
+    mol_col_ptr_host: torch.Tensor
+    col_ptr: torch.Tensor
+    col_ptr_host: torch.Tensor
+    con_pair: torch.Tensor
+    con_d2: torch.Tensor
+
+
+def md_constrained_max_atoms() -> int:
+    """the largest molecule with constraints nnhip_md_step_constrained takes"""
+    return int(lib().nnhip_md_constrained_max_atoms())
+
+
+def md_step_constrained(pos_in: torch.Tensor, vel: torch.Tensor, force: Optional[torch.Tensor], hk: Optional[torch.Tensor],
+                        inv_mass: torch.Tensor, dth: float, inv_dth: float, c1: float, flags: int, tables: ConstraintTables,
+                        tol: float, max_iter: int, n_failed: torch.Tensor, n_sweeps: torch.Tensor,
+                        pos_out: Optional[torch.Tensor] = None, mass: Optional[torch.Tensor] = None,
+                        sigma: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                        ke_out: Optional[torch.Tensor] = None):
+    """One launch of the constrained integrator (nnhip_md_step_constrained, csrc/rattle.hip; the contract is in
+    include/newtonnet_hip.h) on the current stream: md_step's flags MD_FINISH and MD_BEGIN with SHAKE / RATTLE on the constraints
+    of `tables`, or MDC_PROJECT alone (the constraints imposed on pos_in and vel).  pos_in is always read.  `vel` is updated in
+    place, `pos_out`, `ke_out` are written and `n_failed`, `n_sweeps` (int32 [B]) updated: all of these must be contiguous tensors
+    of exactly that type (a copy would take the result away); `pos_out` may not overlap `pos_in`."""
+    for name, t in (('vel', vel), ('pos_out', pos_out), ('ke_out', ke_out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
+    N, dev = vel.shape[0], vel.device
+    ins = [None if t is None else _f32c(t, name) for name, t in (('pos_in', pos_in), ('force', force), ('hk', hk), ('mass', mass),
+                                                                 ('inv_mass', inv_mass), ('sigma', sigma), ('noise', noise))]
+    for name, t, numel in (('pos_in', ins[0], 3 * N), ('force', ins[1], 3 * N), ('hk', ins[2], N), ('mass', ins[3], N),
+                           ('inv_mass', ins[4], N), ('sigma', ins[5], N), ('noise', ins[6], 3 * N), ('pos_out', pos_out, 3 * N),
+                           ('ke_out', ke_out, N), ('vel', vel, 3 * N)):
+        if t is not None and (t.numel() != numel or t.device != dev):
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+    for name in ('mol_ptr', 'mol_col_ptr', 'col_ptr'):
+        d, h = getattr(tables, name), getattr(tables, name + '_host')
+        for label, t, where in ((name, d, dev.type), (name + '_host', h, 'cpu')):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1 \
+                    or t.device.type != where:
+                raise ValueError(f'{label}: a contiguous int32 tensor on {where} expected')
+        if d.numel() != h.numel():
+            raise ValueError(f'{name}_host: the host copy of {name} expected')
+    B, K = tables.mol_ptr.numel() - 1, tables.col_ptr.numel() - 1
+    if tables.mol_col_ptr.numel() != B + 1:
+        raise ValueError(f'mol_col_ptr: int32 [{B + 1}] expected')
+    C_ = int(tables.col_ptr_host[K])
+    pair, d2 = tables.con_pair, tables.con_d2
+    if (pair.dtype != torch.int32 or not pair.is_contiguous() or pair.device != dev or d2.dtype != torch.float32
+            or not d2.is_contiguous() or d2.device != dev or pair.numel() < 2 * C_ or d2.numel() < C_):
+        raise ValueError(f'con_pair: contiguous int32 [{C_},2] and con_d2: contiguous float32 [{C_}] on {dev} expected')
+    for name, t in (('n_failed', n_failed), ('n_sweeps', n_sweeps)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B or t.device != dev:
+            raise ValueError(f'{name}: a contiguous int32 tensor of {B} values on {dev} expected (it is written in place)')
+    _check(lib().nnhip_md_step_constrained(
+        _ptr(ins[0]), _ptr(vel), _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]), _ptr(ins[5]), _ptr(ins[6]), float(dth),
+        float(inv_dth), float(c1), int(flags), N, _ptr(tables.mol_ptr), _ptr(tables.mol_ptr_host), B, _ptr(pair), _ptr(d2),
+        _ptr(tables.mol_col_ptr), _ptr(tables.mol_col_ptr_host), _ptr(tables.col_ptr), _ptr(tables.col_ptr_host), K, float(tol),
+        int(max_iter), _ptr(pos_out), _ptr(ke_out), _ptr(n_failed), _ptr(n_sweeps), _stream(dev)), 'nnhip_md_step_constrained')
 
 
 LBFGS_CHECK_ONLY = _K['NNHIP_LBFGS_CHECK_ONLY']             # flag of nnhip_lbfgs_step

@@ -778,7 +778,9 @@ class NewtonNet(nn.Module):
         """Molecular dynamics of every molecule of the batch on the device: a newtonnet_amd.dynamics.Dynamics whose run(n_steps,
         record_every) advances them together, one force evaluation and one integrator launch (csrc/md.hip) per step.  Keywords:
         masses, velocities, temperature (K, a number or one per molecule), friction (1 / fs; 0 = microcanonical velocity Verlet,
-        > 0 = BAOAB Langevin), timestep (fs), fixed, generator.  Eval mode only; needs the 'energy' and 'gradient_force' heads.
+        > 0 = BAOAB Langevin), timestep (fs), fixed, generator, constraints ('h-bonds' or (pairs, lengths): bond lengths kept by
+        SHAKE / RATTLE inside the step's launch, csrc/rattle.hip), constraint_tolerance, constraint_max_iter.  Eval mode only;
+        needs the 'energy' and 'gradient_force' heads.
         The reference leaves dynamics to an outside driver, one structure and one calculator call per step."""
         from newtonnet_amd import dynamics as _d
         return _d.Dynamics(self, z, pos, cell, batch, **kw)

@@ -169,7 +169,8 @@ class MLAseCalculator(_Base):
         return out.pos.cpu().numpy().reshape(int(n_samples), len(atoms), 3)
 
     def run_md(self, atoms_or_list, n_steps: int, timestep: float = 0.5, temperature=None, friction: float = 0.0,
-               record_every: int = 0, seed=None):
+               record_every: int = 0, seed=None, constraints=None, constraint_tolerance: float = 1e-5,
+               constraint_max_iter: int = 150):
         """n_steps of molecular dynamics of one structure or a list of equally sized ones, all advanced together on the device
         (NewtonNet.dynamics): timestep in fs, friction in 1 / fs (0: microcanonical; > 0: Langevin at `temperature`, K).  Masses
         from atoms.get_masses() when the objects have it, else standard atomic weights; initial velocities from
@@ -177,7 +178,11 @@ class MLAseCalculator(_Base):
         `temperature`, or zero without one.  seed: of the device generator behind velocities and noise (None: torch's global one).
         Returns a dict of numpy arrays over the R recorded steps (record_every, 2 record_every, ... and the last; 0: the last
         only): positions and velocities [R, n_frames, n_atoms, 3], energy and kinetic_energy [R, n_frames], step [R]; one
-        structure drops the frame axis.  The Atoms objects are not modified."""
+        structure drops the frame axis.  The Atoms objects are not modified.
+        constraints: None, 'h-bonds' (every X-H bond length kept at its present value) or (pairs [C,2], lengths [C] or None) with
+        atom indices within ONE frame (arrays, lists or tensors on any device), applied to every frame; constraint_tolerance and
+        constraint_max_iter as for Dynamics, which has the details.  The dict then has constraint_failures (int32 [n_frames], the
+        launches in which a frame's constraint solve failed: 0 for a sound run; one structure drops the frame axis here too)."""
         from newtonnet_amd import dynamics as _d
         atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
         if not atoms:
@@ -210,17 +215,34 @@ class MLAseCalculator(_Base):
             gen.manual_seed(int(seed))
         if isinstance(temperature, (list, tuple, np.ndarray)):
             temperature = torch.tensor(np.asarray(temperature, dtype=np.float64), dtype=torch.float32, device=pos.device)
+        kw = {}
+        if constraints is not None:
+            if not isinstance(constraints, str):
+                pairs, lengths = constraints
+                pairs, lengths = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t for t in (pairs, lengths))
+                pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+                if pairs.size and (pairs.min() < 0 or pairs.max() >= n_atoms):
+                    raise ValueError(f'constraints: atom indices within one frame (0 .. {n_atoms - 1}) expected')
+                pairs = (pairs[None, :, :] + n_atoms * np.arange(n_frames)[:, None, None]).reshape(-1, 2)
+                if lengths is not None:
+                    lengths = torch.from_numpy(np.tile(np.asarray(lengths, dtype=np.float32).reshape(-1), n_frames))
+                constraints = (torch.from_numpy(pairs), lengths)
+            kw = dict(constraints=constraints, constraint_tolerance=constraint_tolerance, constraint_max_iter=constraint_max_iter)
         dyn = self.model.dynamics(z, pos.float(), cell.float(), batch, masses=masses, velocities=velocities, temperature=temperature,
-                                  friction=friction, timestep=timestep, generator=gen)
+                                  friction=friction, timestep=timestep, generator=gen, **kw)
         traj = dyn.run(int(n_steps), int(record_every))
         R = traj.step.numel()
         out = dict(positions=traj.pos.cpu().numpy().reshape(R, n_frames, n_atoms, 3),
                    velocities=traj.vel.cpu().numpy().reshape(R, n_frames, n_atoms, 3),
                    energy=traj.potential_energy.cpu().numpy(), kinetic_energy=traj.kinetic_energy.cpu().numpy(),
                    step=traj.step.cpu().numpy())
+        if constraints is not None:
+            out['constraint_failures'] = dyn.constraint_failures.cpu().numpy()
         if n_frames == 1:
             for k in ('positions', 'velocities', 'energy', 'kinetic_energy'):
                 out[k] = out[k][:, 0]
+            if 'constraint_failures' in out:
+                out['constraint_failures'] = out['constraint_failures'][0]
         return out
 
     def run_remd(self, atoms_or_list, temperatures, n_steps: int, exchange_every: int, friction: float, timestep: float = 0.5,
