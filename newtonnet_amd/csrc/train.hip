@@ -1302,9 +1302,11 @@ clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __re
     for (int k = 0; k < OPT_BLOCKS; ++k) tot += (double)part[k];
     const float norm = (float)sqrt(tot);
     s_clip = max_norm > 0.f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
-    const float t = state[0];
-    s_c1 = lr / (1.0f - powf(b1, t));
-    s_c2 = 1.0f / sqrtf(1.0f - powf(b2, t));
+    // the bias corrections in fp64 (torch forms them in Python floats): 1 - beta2^t cancels at small t -- beta2 = 0.999, t = 2
+    // leaves 2e-3, and the rounding of powf alone then put 1e-5 relative into every step (measured 3e-6; one thread per workgroup)
+    const double t = (double)state[0];
+    s_c1 = (float)((double)lr / (1.0 - pow((double)b1, t)));
+    s_c2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
     if (blockIdx.x == 0) state[1] = norm;
   }
   __syncthreads();
