@@ -1290,6 +1290,59 @@ int nnhip_edge_index_unpermute(const int32_t* row_ptr_p, const int32_t* col_p, c
                                int32_t n_atoms, int32_t n_edges, int64_t* edge_index, int32_t* scratch, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Constant-pressure molecular dynamics on the device (csrc/npt.hip): isotropic stochastic cell rescaling (Bernetti & Bussi, J. Chem.
+ * Phys. 153, 114107 (2020)) as a first-order (Euler) step S for eps = ln V inside nnhip_md_step's BAOAB step:
+ *   B(F_k) [full-step v, KE] B(F_k) S A O A,   then the model at the new positions with the new cell.
+ * TWO launches on `stream` between two force evaluations: nnhip_npt_barostat forms every system's scale factor, nnhip_npt_step is
+ * nnhip_md_step with S applied.  All in fp32; every line below is ONE rounding to nearest (an fma rounds once) unless it says
+ * otherwise (tests/npt_ref.py restates both chains in fp64):
+ *
+ * nnhip_npt_barostat: one 256-thread workgroup per system b = 0 .. n_mol - 1, atoms mol_ptr[b] .. mol_ptr[b+1] - 1 (int32 [n_mol+1],
+ * clamped to [0, n_atoms]).  Thread t takes the atoms t, t + 256, ... of the system in that order:
+ *     v'   = fma(hk_i, F_ik, v_ik)          the pending second half kick;  force == NULL: none is pending, v' = v (no rounding).
+ *                                           v' is NOT stored: nnhip_npt_step's finish forms the same bits
+ *     s    = vx' vx';  s = fma(vy', vy', s);  s = fma(vz', vz', s);  ke_i = (0.5 mass_i) s     nnhip_md_step's ke_out chain
+ *     acc  = acc + ke_i                                                                        (acc = 0 at the start)
+ *   The 256 partial sums meet in a fixed LDS tree: for d = 128, 64, ..., 1 thread t < d adds the partial of t + d to its own.  No
+ *   float atomics: K_b is bitwise repeatable for any system size, 0 (K = 0) and > 256 included.  Then one thread, with c = cell_in[b]
+ *   (row-major [3][3]) and W = virial[b] (= -dE/d strain at the current geometry):
+ *     m0   = fma(c11, c22, -(c12 c21));  m1 = fma(c10, c22, -(c12 c20));  m2 = fma(c10, c21, -(c11 c20))     (each product one rounding)
+ *     V    = fma(c02, m2, fma(-c01, m1, c00 m0))                                               = det(cell)
+ *     P    = fma(2, K, (W00 + W11) + W22) / (3 V)                                              two sums, the fma, 3 V, the quotient
+ *     deps = fma(-a_b, P0_b - P, sqrt(s2_b / V) noise_b)                                       with noise: quotient, root, product, fma
+ *     deps = (-a_b) (P0_b - P)                                                                 noise == NULL (s2 == NULL too)
+ *            a_b == 0 with noise == NULL: system b is not coupled, deps = +0 whatever P is (a cell of zeros included)
+ *     e    = deps fl32(1/3);  mu = expf(e);  inv_mu = expf(-e);  cell_out[b] = mu c            (nine products)
+ *   a_b = beta_T dt / tau_p (per pressure unit), P0_b the target pressure, s2_b = 2 k_B T_b beta_T dt / tau_p (energy), noise_b ~
+ *   N(0,1); pressures in energy / length^3.  Written: cell_out [n_mol][3][3], mu, inv_mu, and the records ke (= K), pressure (= P),
+ *   volume (= V), deps, all [n_mol].  expf(+-0) = 1 exactly, and a product with 1.0f is exact: a_b = 0 without noise gives
+ *   mu = inv_mu = 1.0f and cell_out[b] == cell_in[b] bit for bit.
+ *   Roundings that are NOT half an ulp: expf, 2 ulp taken (0.836 ulp measured on an MI355X over 2^22 arguments, tools/probes/
+ *   math_ulp_probe.hip; |e| < 1 here); the root, 2 ulp taken (gfx950 has no correctly rounded fp32 root:
+ *   0.916 ulp measured, same probe).  The quotients are correctly rounded (0.5 ulp measured, same probe).
+ *   cell_out may NOT overlap cell_in (NNHIP_E_INVALID, nothing is launched), for the reason given at nnhip_md_step: the deferred
+ *   forward call queued on cell_in may have to be repeated from it.  NULL vel, mass, mol_ptr, cell_in, virial, a, p0 or any output,
+ *   force without hk, or s2 and noise not both given / both NULL: NNHIP_E_INVALID.  n_mol == 0: success, nothing is launched.
+ *
+ * nnhip_npt_step: nnhip_md_step's launch shape, flags and chain with S between the begin kick and the first half drift; b =
+ * mol_of_atom[i] (int32 [N], read with BEGIN only):
+ *   finish (NNHIP_MD_FINISH):  v = fma(hk_i, F_ik, v);  ke_out[i] as nnhip_md_step                       [only when ke_out != NULL]
+ *   begin  (NNHIP_MD_BEGIN):   v = fma(hk_i, F_ik, v);  x = mu_b pos_in;  v = inv_mu_b v;  x = fma(dth, v, x);
+ *                              v = fma(sigma_i, noise_ik, c1 v) [skipped when noise == NULL];  pos_out = fma(dth, v, x)
+ *   With every mu = inv_mu = 1 these are nnhip_md_step's bits (a product with 1.0f is exact).  Same aliasing rule (pos_out may NOT
+ *   overlap pos_in), same NULL rules (plus mu, inv_mu [n_mol] and mol_of_atom with BEGIN), sigma and noise both given or both NULL,
+ *   ke_out needs FINISH and mass, n_atoms == 0: success without a launch.  An atom whose mol_of_atom lies outside [0, n_mol) is
+ *   left untouched by a BEGIN launch (no table is read outside its bounds).
+ * ------------------------------------------------------------------------ */
+int nnhip_npt_barostat(const float* vel, const float* force, const float* hk, const float* mass, const int32_t* mol_ptr,
+                       int32_t n_mol, int32_t n_atoms, const float* cell_in, const float* virial, const float* a, const float* p0,
+                       const float* s2, const float* noise, float* cell_out, float* mu, float* inv_mu, float* ke, float* pressure,
+                       float* volume, float* deps, void* stream);
+int nnhip_npt_step(const float* pos_in, float* vel, const float* force, const float* hk, const float* mass, const float* sigma,
+                   const float* noise, const float* mu, const float* inv_mu, const int32_t* mol_of_atom, int32_t n_mol, float dth,
+                   float c1, int32_t flags, int32_t n_atoms, float* pos_out, float* ke_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Timing hook for bench.py: wraps the kernels of one nnhip_energy_forces call
  * in HIP events on `stream` and accumulates per-kernel-class milliseconds.
  * classes: 0 = edge kernels (message/force fwd+adjoint), 1 = all dense MFMA kernels, 2 = everything else,

@@ -633,6 +633,81 @@ def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tens
     return out
 
 
+def _written(dev, **tensors):
+    """tensors a kernel writes in place: contiguous float32 on `dev` (a copy would take the result away)"""
+    for name, (t, numel) in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
+        if t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+
+
+def _read(dev, **tensors):
+    """tensors a kernel reads: float32 (made contiguous) with the stated number of values on `dev`; None stays None"""
+    out = []
+    for name, (t, numel) in tensors.items():
+        if t is not None:
+            t = _f32c(t, name)
+            if t.numel() != numel or t.device != dev:
+                raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+        out.append(t)
+    return out
+
+
+def npt_barostat(vel: torch.Tensor, mass: torch.Tensor, mol_ptr: torch.Tensor, cell_in: torch.Tensor, virial: torch.Tensor,
+                 a: torch.Tensor, p0: torch.Tensor, cell_out: torch.Tensor, mu: torch.Tensor, inv_mu: torch.Tensor,
+                 ke: torch.Tensor, pressure: torch.Tensor, volume: torch.Tensor, deps: torch.Tensor,
+                 force: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, s2: Optional[torch.Tensor] = None,
+                 noise: Optional[torch.Tensor] = None):
+    """One launch of the barostat of constant-pressure dynamics (nnhip_npt_barostat, csrc/npt.hip; the chain is written out in
+    include/newtonnet_hip.h) on the current stream: per system the kinetic energy of the full-step velocities (`vel` with the
+    pending half kick hk x force, or `vel` itself without `force`), V = det(cell_in), P = (2 K + tr virial) / (3 V), the step
+    deps = -a (p0 - P) + sqrt(s2 / V) noise of ln V and mu = exp(deps / 3).  Writes cell_out = mu cell_in [B,3,3], mu, inv_mu and
+    the records ke, pressure, volume, deps [B]: all contiguous float32; `cell_out` may not overlap `cell_in`.  mol_ptr int32 [B+1]."""
+    if mol_ptr.dtype != torch.int32 or not mol_ptr.is_contiguous() or mol_ptr.numel() < 1:
+        raise ValueError('mol_ptr: contiguous int32 [B+1] expected')
+    B, N, dev = mol_ptr.numel() - 1, vel.shape[0], vel.device
+    if mol_ptr.device != dev:
+        raise ValueError(f'mol_ptr is on {mol_ptr.device}, vel on {dev}')
+    _written(dev, cell_out=(cell_out, 9 * B), mu=(mu, B), inv_mu=(inv_mu, B), ke=(ke, B), pressure=(pressure, B),
+             volume=(volume, B), deps=(deps, B))
+    vel, force, hk, mass, cell_in, virial, a, p0, s2, noise = _read(
+        dev, vel=(vel, 3 * N), force=(force, 3 * N), hk=(hk, N), mass=(mass, N), cell_in=(cell_in, 9 * B), virial=(virial, 9 * B),
+        a=(a, B), p0=(p0, B), s2=(s2, B), noise=(noise, B))
+    _check(lib().nnhip_npt_barostat(_ptr(vel), _ptr(force), _ptr(hk), _ptr(mass), _ptr(mol_ptr), B, N, _ptr(cell_in), _ptr(virial),
+                                    _ptr(a), _ptr(p0), _ptr(s2), _ptr(noise), _ptr(cell_out), _ptr(mu), _ptr(inv_mu), _ptr(ke),
+                                    _ptr(pressure), _ptr(volume), _ptr(deps), _stream(dev)), 'nnhip_npt_barostat')
+
+
+def npt_step(pos_in: Optional[torch.Tensor], vel: torch.Tensor, force: torch.Tensor, hk: torch.Tensor, dth: float, c1: float,
+             flags: int, mu: Optional[torch.Tensor] = None, inv_mu: Optional[torch.Tensor] = None,
+             mol_of_atom: Optional[torch.Tensor] = None, pos_out: Optional[torch.Tensor] = None,
+             mass: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+             ke_out: Optional[torch.Tensor] = None):
+    """One launch of the constant-pressure integrator (nnhip_npt_step, csrc/npt.hip) on the current stream: md_step's flags and
+    chain with the rescale  x = mu_b x, v = inv_mu_b v  of the atom's system b = mol_of_atom[i] (int32 [N]) between the MD_BEGIN kick
+    and the first half drift.  mu, inv_mu: float32 [B] as nnhip_npt_barostat wrote them.  `vel` is updated in place and `pos_out`
+    written: both contiguous float32; `pos_out` may not overlap `pos_in`."""
+    N, dev = vel.shape[0], vel.device
+    _written(dev, vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), ke_out=(ke_out, N))
+    n_mol = 0
+    if mu is not None or inv_mu is not None:
+        if mu is None or inv_mu is None or mu.numel() != inv_mu.numel():
+            raise ValueError('mu and inv_mu: two float32 tensors [B] expected')
+        n_mol = mu.numel()
+    if mol_of_atom is not None and (mol_of_atom.dtype != torch.int32 or not mol_of_atom.is_contiguous() or mol_of_atom.numel() != N
+                                    or mol_of_atom.device != dev):
+        raise ValueError(f'mol_of_atom: contiguous int32 [{N}] on {dev} expected')
+    pos_in, force, hk, mass, sigma, noise, mu, inv_mu = _read(
+        dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), hk=(hk, N), mass=(mass, N), sigma=(sigma, N), noise=(noise, 3 * N),
+        mu=(mu, n_mol), inv_mu=(inv_mu, n_mol))
+    _check(lib().nnhip_npt_step(_ptr(pos_in), _ptr(vel), _ptr(force), _ptr(hk), _ptr(mass), _ptr(sigma), _ptr(noise), _ptr(mu),
+                                _ptr(inv_mu), _ptr(mol_of_atom), n_mol, float(dth), float(c1), int(flags), N, _ptr(pos_out),
+                                _ptr(ke_out), _stream(dev)), 'nnhip_npt_step')
+
+
 MDC_PROJECT, MDC_MAX_ATOMS = _K['NNHIP_MDC_PROJECT'], _K['NNHIP_MDC_MAX_ATOMS']      # of nnhip_md_step_constrained
 
 

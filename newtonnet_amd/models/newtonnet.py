@@ -785,6 +785,17 @@ class NewtonNet(nn.Module):
         from newtonnet_amd import dynamics as _d
         return _d.Dynamics(self, z, pos, cell, batch, **kw)
 
+    def constant_pressure(self, z, pos, cell, batch, pressure, temperature, **kw):
+        """Constant-pressure (NPT) molecular dynamics of every periodic system of the batch on the device: a
+        newtonnet_amd.npt.ConstantPressure, a Dynamics whose cell follows isotropic stochastic cell rescaling (Bernetti & Bussi
+        2020), two launches per step beside the model's (csrc/npt.hip) and no host read in the loop.  pressure (bar) and temperature
+        (K): a number or one per system.  Keywords: compressibility (1 / bar, 4.5e-5), barostat_time (fs, 1000), friction (1 / fs),
+        timestep (fs), masses, velocities, generator.  run(n_steps, record_every) returns an NPTTrajectory (Trajectory's fields and
+        cell, volume, pressure, density).  Eval mode only; needs the 'energy' and 'gradient_force' heads and a 'virial' or 'stress'
+        head; every system needs det(cell) > 0."""
+        from newtonnet_amd import npt as _n
+        return _n.ConstantPressure(self, z, pos, cell, batch, pressure, temperature, **kw)
+
     def replica_exchange(self, z, pos, cell, batch, temperatures, exchange_every, friction, timestep=0.5, masses=None, fixed=None,
                          generator=None, exchange_seed=0):
         """Replica-exchange molecular dynamics (parallel tempering) on the device: a newtonnet_amd.remd.ReplicaExchange, a Dynamics

@@ -245,6 +245,61 @@ class MLAseCalculator(_Base):
                 out['constraint_failures'] = out['constraint_failures'][0]
         return out
 
+    def run_npt(self, atoms_or_list, n_steps: int, pressure, temperature, timestep: float = 0.5, friction: float = 0.0,
+                compressibility: float = 4.5e-5, barostat_time: float = 1000.0, record_every: int = 0, seed=None):
+        """n_steps of constant-pressure molecular dynamics of one periodic structure or a list of equally sized ones, all advanced
+        together on the device (NewtonNet.constant_pressure: isotropic stochastic cell rescaling inside BAOAB).  pressure in bar
+        and temperature in K (a number, or one value per structure), compressibility in 1 / bar, barostat_time and timestep in
+        fs, friction in 1 / fs.  Masses, initial velocities and seed as in run_md.  The calculator's model needs a virial or
+        stress head (properties with 'stress').  Returns run_md's dict and cell [R, n_frames, 3, 3], volume (Angstrom^3),
+        pressure (bar: the internal pressure of the recorded state) and density (g / cm^3) [R, n_frames]; one structure drops
+        the frame axis.  The Atoms objects are not modified."""
+        from newtonnet_amd import dynamics as _d
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('run_npt: at least one structure expected')
+        n_frames, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('run_npt: frames of different sizes cannot share one array; use model.constant_pressure (packed per '
+                             'system)')
+        if int(n_steps) != n_steps or n_steps < 0:
+            raise ValueError(f'n_steps: an integer >= 0 expected (got {n_steps!r})')
+        if int(record_every) != record_every or record_every < 0:
+            raise ValueError(f'record_every: an integer >= 0 expected (got {record_every!r})')
+        if temperature is None:
+            raise ValueError('run_npt needs a temperature')
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd dynamics run on an MI355X (ROCm) device only: make the calculator with device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        masses = velocities = gen = None
+        if all(hasattr(a, 'get_masses') for a in atoms):
+            masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
+                                  dtype=torch.float32, device=pos.device)
+        if all(hasattr(a, 'get_momenta') for a in atoms):
+            p = np.concatenate([np.asarray(a.get_momenta(), dtype=np.float64).reshape(-1, 3) for a in atoms])
+            m = masses.cpu().double().numpy() if masses is not None else _d.table_masses(z.cpu()).double().numpy()
+            velocities = torch.tensor(p / m[:, None], dtype=torch.float32, device=pos.device)
+        if seed is not None:
+            gen = torch.Generator(device=pos.device)
+            gen.manual_seed(int(seed))
+        per_frame = [torch.tensor(np.asarray(v, dtype=np.float64), dtype=torch.float32, device=pos.device)
+                     if isinstance(v, (list, tuple, np.ndarray)) else v for v in (pressure, temperature)]
+        dyn = self.model.constant_pressure(z, pos.float(), cell.float(), batch, per_frame[0], per_frame[1], masses=masses,
+                                           velocities=velocities, friction=friction, timestep=timestep,
+                                           compressibility=compressibility, barostat_time=barostat_time, generator=gen)
+        traj = dyn.run(int(n_steps), int(record_every))
+        R = traj.step.numel()
+        out = dict(positions=traj.pos.cpu().numpy().reshape(R, n_frames, n_atoms, 3),
+                   velocities=traj.vel.cpu().numpy().reshape(R, n_frames, n_atoms, 3),
+                   energy=traj.potential_energy.cpu().numpy(), kinetic_energy=traj.kinetic_energy.cpu().numpy(),
+                   cell=traj.cell.cpu().numpy(), volume=traj.volume.cpu().numpy(), pressure=traj.pressure.cpu().numpy(),
+                   density=traj.density.cpu().numpy(), step=traj.step.cpu().numpy())
+        if n_frames == 1:
+            for k in out:
+                if k != 'step':
+                    out[k] = out[k][:, 0]
+        return out
+
     def run_remd(self, atoms_or_list, temperatures, n_steps: int, exchange_every: int, friction: float, timestep: float = 0.5,
                  record_every: int = 0, seed=None, exchange_seed: int = 0):
         """n_steps of replica-exchange molecular dynamics (NewtonNet.replica_exchange) of one structure or a list of G equally
