@@ -304,8 +304,6 @@ bias_eval_kernel(EvalArgs g) {
   }
 }
 
-inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
-
 }  // namespace
 
 extern "C" int nnhip_bias_step(const float* pos, const float* force_in, const int32_t* mol_ptr, const int32_t* mol_ptr_host,

@@ -43,6 +43,9 @@ void nnhip_set_error(const char* fmt, ...);
   } while (0)
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
+// do a [n] and b [n] share an element (an output that may not alias an input, overlapping views included)
+inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
+
 // ---- timers (host) ---------------------------------------------------------
 enum { TC_EDGE = 0, TC_LIN = 1, TC_OTHER = 2, TC_EDGE_FWD_MSG = 3, TC_EDGE_FWD_FORCE = 4, TC_EDGE_BWD_FORCE = 5,
        TC_EDGE_BWD_MSG = 6, TC_GRAPH = 7, TC_MLP = 8, TC_LIN1 = 9, TC_WGRAD = 10, TC_MLP_ONEPASS = 11, TC_MOL_FWD = 12, TC_MOL_BWD = 13 };

@@ -335,8 +335,6 @@ neb_step_kernel(NebArgs g) {
   }
 }
 
-inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
-
 }  // namespace
 
 extern "C" int nnhip_neb_step(const float* pos_in, const float* force, const float* energy, const uint8_t* free_mask,

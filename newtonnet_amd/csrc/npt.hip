@@ -1,13 +1,14 @@
 // Constant-pressure molecular dynamics on the device (gfx950, fp32): isotropic stochastic cell rescaling (Bernetti & Bussi 2020) as a
 // first-order step for eps = ln V inside the BAOAB step of csrc/md.hip.  A step of the driver (newtonnet_amd/npt.py) is
 //   model(pos, cell) -> npt_barostat -> npt_step(finish | begin):   B(F_k) [full-step v, KE] B(F_k) S A O A
-// Two launches.  Every operation in fp32, every multiply-add an explicit __fmaf_rn, every lone product, sum, quotient and root an
-// explicit __f*_rn, so that the rounding chain does not depend on the compiler's contraction (tests/npt_ref.py restates both kernels
-// in fp64 with one 2^-24 per operation and 2 ulp for expf).
+// Two launches: the barostat below, and nnhip_npt_step, which is md_step_kernel<true> of csrc/md.hip (the BAOAB chain with the
+// rescale S; the chain is written once, in csrc/md_chain.h).  Every operation in fp32, every multiply-add an explicit __fmaf_rn,
+// every lone product, sum, quotient and root an explicit __f*_rn, so that the rounding chain does not depend on the compiler's
+// contraction (tests/npt_ref.py restates both kernels in fp64 with one 2^-24 per operation and 2 ulp for expf).
 //
 // npt_barostat: one 256-thread workgroup per system b.  Thread t takes the atoms t, t + 256, ... of the system in that order:
-//     v' = fma(hk_i, F_ik, v)             (v' = v when force == NULL: no kick is pending; v' is NOT stored)
-//     ke_i = (0.5 m_i) * fma(vz', vz', fma(vy', vy', vx' * vx'))                  nnhip_md_step's ke_out chain
+//     v' = md_chain::half_kick             (v' = v when force == NULL: no kick is pending; v' is NOT stored)
+//     ke_i = md_chain::kinetic(v')         nnhip_md_step's ke_out, from the same text
 //     acc = acc + ke_i
 //   the 256 partial sums meet in a fixed LDS tree (t < d adds the partial of t + d, d = 128, 64, ..., 1); then thread 0:
 //     V     = fma(c02, m2, fma(-c01, m1, c00 * m0)),  m0 = fma(c11, c22, -(c12 * c21)), m1 = fma(c10, c22, -(c12 * c20)),
@@ -17,18 +18,11 @@
 //             (a_b == 0 without noise: system b is not coupled, deps = +0 whatever P is)
 //     e     = deps * fl32(1/3);  mu = expf(e);  inv_mu = expf(-e);  cell_out = mu * cell_in  (nine products)
 //   The kernel moves 28-40 bytes per atom: nothing here is tuned.
-//
-// npt_step: md_step_kernel with S between the begin kick and the first half drift:
-//     finish:  v = fma(hk_i, F_ik, v);  ke_i as above (only when ke_out != NULL)
-//     begin:   v = fma(hk_i, F_ik, v);  x = mu_b * x_in;  v = inv_mu_b * v;  x = fma(dth, v, x);  v = fma(sigma_i, xi_ik, c1 * v);
-//              x_out = fma(dth, v, x)                                                  b = mol_of_atom[i]
-//   A product with 1.0f is exact: with every mu = inv_mu = 1 these are nnhip_md_step's bits.
-#include "common.h"
+#include "md_chain.h"
 
 namespace {
 
 constexpr int NPT_THREADS = 256;
-constexpr int NPT_MAX_BLOCKS = 2048;
 constexpr float NPT_THIRD = 0.3333333432674407958984375f;        // fl32(1/3) = 0x3eaaaaab
 
 struct BaroArgs {
@@ -55,7 +49,7 @@ struct BaroArgs {
 
 __global__ void __launch_bounds__(NPT_THREADS)
 npt_barostat_kernel(BaroArgs g) {
-#pragma clang fp contract(off)       // (acc + ke_i below is a product followed by a sum: plain operators, which stay two roundings here)
+#pragma clang fp contract(off)       // (acc + ke_i below is a product followed by a plain sum, which stays two roundings here)
   __shared__ float part[NPT_THREADS];
   const int b = blockIdx.x, t = threadIdx.x;
   const int a0 = max(g.mol_ptr[b], 0), a1 = min(g.mol_ptr[b + 1], g.n_atoms);       // (never outside the per-atom arrays)
@@ -63,13 +57,8 @@ npt_barostat_kernel(BaroArgs g) {
   for (int i = a0 + t; i < a1; i += NPT_THREADS) {
     const size_t o = 3 * (size_t)i;
     float v[3] = {g.vel[o], g.vel[o + 1], g.vel[o + 2]};
-    if (g.force) {
-      const float hk = g.hk[i];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] = __fmaf_rn(hk, g.force[o + k], v[k]);
-    }
-    const float s = __fmaf_rn(v[2], v[2], __fmaf_rn(v[1], v[1], __fmul_rn(v[0], v[0])));
-    const float ke_i = (0.5f * g.mass[i]) * s;
+    if (g.force) md_chain::half_kick(v, g.hk[i], g.force + o);
+    const float ke_i = md_chain::kinetic(v, g.mass[i]);
     acc = acc + ke_i;
   }
   part[t] = acc;
@@ -109,64 +98,6 @@ npt_barostat_kernel(BaroArgs g) {
   g.volume[b] = V;
   g.deps[b] = de;
 }
-
-struct NptArgs {
-  const float* pos_in;
-  float* vel;
-  const float* force;
-  const float* hk;
-  const float* mass;
-  const float* sigma;
-  const float* noise;
-  const float* mu;
-  const float* inv_mu;
-  const int* mol_of_atom;
-  float* pos_out;
-  float* ke_out;
-  float dth, c1;
-  int flags, n_atoms, n_mol;
-};
-
-__global__ void __launch_bounds__(NPT_THREADS)
-npt_step_kernel(NptArgs g) {
-  const bool finish = g.flags & NNHIP_MD_FINISH, begin = g.flags & NNHIP_MD_BEGIN;
-  for (int i = blockIdx.x * NPT_THREADS + threadIdx.x; i < g.n_atoms; i += gridDim.x * NPT_THREADS) {
-    const size_t o = 3 * (size_t)i;
-    int b = 0;
-    if (begin) {
-      b = g.mol_of_atom[i];
-      if ((unsigned)b >= (unsigned)g.n_mol) continue;       // (an index outside the tables: the atom is left alone, nothing is read)
-    }
-    const float hk = g.hk[i];
-    float v[3] = {g.vel[o], g.vel[o + 1], g.vel[o + 2]};
-    const float f[3] = {g.force[o], g.force[o + 1], g.force[o + 2]};
-    if (finish) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] = __fmaf_rn(hk, f[k], v[k]);
-      if (g.ke_out) {
-        const float s = __fmaf_rn(v[2], v[2], __fmaf_rn(v[1], v[1], __fmul_rn(v[0], v[0])));
-        g.ke_out[i] = __fmul_rn(__fmul_rn(0.5f, g.mass[i]), s);
-      }
-    }
-    if (begin) {
-      const float mu = g.mu[b], inv_mu = g.inv_mu[b];
-      const float sigma = g.noise ? g.sigma[i] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        v[k] = __fmaf_rn(hk, f[k], v[k]);
-        float x = __fmul_rn(mu, g.pos_in[o + k]);
-        v[k] = __fmul_rn(inv_mu, v[k]);
-        x = __fmaf_rn(g.dth, v[k], x);
-        if (g.noise) v[k] = __fmaf_rn(sigma, g.noise[o + k], __fmul_rn(g.c1, v[k]));
-        g.pos_out[o + k] = __fmaf_rn(g.dth, v[k], x);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) g.vel[o + k] = v[k];
-  }
-}
-
-inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
 
 }  // namespace
 
@@ -214,56 +145,6 @@ extern "C" int nnhip_npt_barostat(const float* vel, const float* force, const fl
   g.deps = deps;
   g.n_atoms = n_atoms;
   npt_barostat_kernel<<<n_mol, NPT_THREADS, 0, (hipStream_t)stream>>>(g);
-  LAUNCH_CHECK();
-  return NNHIP_OK;
-}
-
-extern "C" int nnhip_npt_step(const float* pos_in, float* vel, const float* force, const float* hk, const float* mass,
-                              const float* sigma, const float* noise, const float* mu, const float* inv_mu,
-                              const int32_t* mol_of_atom, int32_t n_mol, float dth, float c1, int32_t flags, int32_t n_atoms,
-                              float* pos_out, float* ke_out, void* stream) {
-  if (n_atoms < 0 || n_mol < 0 || flags < 1 || flags > (NNHIP_MD_FINISH | NNHIP_MD_BEGIN)) {
-    nnhip_set_error("nnhip_npt_step: bad arguments (n_atoms %d, n_mol %d, flags %d: bit 0 = finish, bit 1 = begin)", n_atoms, n_mol,
-                    flags);
-    return NNHIP_E_INVALID;
-  }
-  if ((sigma == nullptr) != (noise == nullptr)) {
-    nnhip_set_error("nnhip_npt_step: sigma and noise come together (both given or both null)");
-    return NNHIP_E_INVALID;
-  }
-  if (n_atoms == 0) return NNHIP_OK;
-  const bool begin = flags & NNHIP_MD_BEGIN;
-  if (!vel || !force || !hk || (begin && (!pos_in || !pos_out || !mu || !inv_mu || !mol_of_atom)) ||
-      (ke_out && (!mass || !(flags & NNHIP_MD_FINISH)))) {
-    nnhip_set_error("nnhip_npt_step: bad arguments (vel, force and hk always; pos_in, pos_out, mu, inv_mu and mol_of_atom with begin; "
-                    "ke_out needs mass and finish)");
-    return NNHIP_E_INVALID;
-  }
-  if (begin && overlap(pos_in, pos_out, 3 * (size_t)n_atoms)) {
-    nnhip_set_error("nnhip_npt_step: pos_out may not alias pos_in (a forward call that has to be repeated reads pos_in again)");
-    return NNHIP_E_INVALID;
-  }
-  NptArgs g;
-  g.pos_in = pos_in;
-  g.vel = vel;
-  g.force = force;
-  g.hk = hk;
-  g.mass = mass;
-  g.sigma = sigma;
-  g.noise = noise;
-  g.mu = mu;
-  g.inv_mu = inv_mu;
-  g.mol_of_atom = mol_of_atom;
-  g.pos_out = pos_out;
-  g.ke_out = ke_out;
-  g.dth = dth;
-  g.c1 = c1;
-  g.flags = flags;
-  g.n_atoms = n_atoms;
-  g.n_mol = n_mol;
-  int blocks = (n_atoms + NPT_THREADS - 1) / NPT_THREADS;
-  blocks = blocks > NPT_MAX_BLOCKS ? NPT_MAX_BLOCKS : blocks;
-  npt_step_kernel<<<blocks, NPT_THREADS, 0, (hipStream_t)stream>>>(g);
   LAUNCH_CHECK();
   return NNHIP_OK;
 }

@@ -9,7 +9,7 @@
 // per operation):
 //   f_k = C[k][0] F_0;  f_k = fma(C[k][s], F_s, f_k)  s = 1 .. P-1 ascending              the mode force, once per launch
 //   finish:  w = fma(hk, f_k, w)
-//            est[row] = ((0.5 m) fma(wz,wz,fma(wy,wy,wx wx)),  (m half_w2) fma(uz,uz,fma(uy,uy,ux ux)),
+//            est[row] = (md_chain::kinetic(w, m),               (m half_w2) fma(uz,uz,fma(uy,uy,ux ux)),
 //                        k > 0 ? fma(uz,fz,fma(uy,fy,ux fx)) : 0,  0)                     only when est_out != NULL
 //   begin:   w = fma(hk, f_k, w)
 //            A:  u' = fma(b, w, a u);  w' = fma(d, u, a w)                                 both from the old u, w
@@ -25,7 +25,7 @@
 // after a barrier thread (s, atom) does the back-transform.  Every barrier is reached by all threads: a system or a tile that is
 // skipped skips the work, never the barrier.  No float atomics, no communication between workgroups: a system's outputs depend on
 // nothing else in the batch.
-#include "common.h"
+#include "md_chain.h"
 
 namespace {
 
@@ -97,11 +97,10 @@ pimd_step_kernel(PimdArgs g) {
           for (int c = 0; c < 3; ++c) ww[c] = __fmaf_rn(hk, f[c], ww[c]);
           if (g.est_out) {
             const float m = g.mass[row];
-            const float kin = __fmaf_rn(ww[2], ww[2], __fmaf_rn(ww[1], ww[1], __fmul_rn(ww[0], ww[0])));
             const float spr = __fmaf_rn(uu[2], uu[2], __fmaf_rn(uu[1], uu[1], __fmul_rn(uu[0], uu[0])));
             const float vir = k > 0 ? __fmaf_rn(uu[2], f[2], __fmaf_rn(uu[1], f[1], __fmul_rn(uu[0], f[0]))) : 0.f;
             float* e = g.est_out + 4 * row;
-            e[0] = __fmul_rn(__fmul_rn(0.5f, m), kin);
+            e[0] = md_chain::kinetic(ww, m);
             e[1] = __fmul_rn(__fmul_rn(m, mt[4]), spr);
             e[2] = vir;
             e[3] = 0.f;
@@ -146,8 +145,6 @@ pimd_step_kernel(PimdArgs g) {
     }
   }
 }
-
-inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
 
 }  // namespace
 

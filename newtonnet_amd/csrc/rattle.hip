@@ -3,10 +3,10 @@
 //
 // The scheme is constrained BAOAB ("g-BAOAB", Leimkuhler & Matthews 2016, one RATTLE per half drift); with c1 = 1 and no noise it
 // is velocity-Verlet RATTLE in two half drifts.  For one molecule, in this order (include/newtonnet_hip.h spells the contract out,
-// tests/rattle_ref.py restates the chain in fp64 and emulates it in fp32):
-//   finish (flag bit 0):  v = fma(hk_i, F, v);  PROJECT v at y;  ke_i = (0.5 m_i) |v_i|^2        (ke only when ke_out != NULL)
-//   begin  (flag bit 1):  v = fma(hk_i, F, v);  PROJECT v at y;  DRIFT;  [v = fma(sigma_i, xi, c1 v);  PROJECT v at y]  DRIFT
-//                         (the bracket only with noise)
+// tests/rattle_ref.py restates the chain in fp64 and emulates it in fp32; half_kick, kinetic and o_step are nnhip_md_step's, from
+// csrc/md_chain.h):
+//   finish (flag bit 0):  half_kick;  PROJECT v at y;  ke_i = kinetic                            (ke only when ke_out != NULL)
+//   begin  (flag bit 1):  half_kick;  PROJECT v at y;  DRIFT;  [o_step;  PROJECT v at y]  DRIFT   (the bracket only with noise)
 //   DRIFT:                r = y;  y = fma(dth, v, r);  D = 0;  SHAKE y with the directions r, every update also added into D;
 //                         v = fma(D, inv_dth, v);  PROJECT v at y
 //                         (D = y'' - y' is the SUM of the applied updates, not the difference of the two positions: the difference
@@ -36,9 +36,10 @@
 // other's atoms.  Lanes of one wave exchange data through LDS only: its LDS instructions execute in program order, so what is
 // needed between a colour and the next (and between an atom-wise and a constraint-wise pass) is that the COMPILER keeps the
 // order and re-reads LDS -- a wavefront-scope release/acquire fence pair around a wave barrier (wave_sync).  No workgroup barrier:
-// the four waves of a workgroup share nothing.  A molecule without constraints takes nnhip_md_step's chain, bit for bit, without
-// LDS or relative coordinates.  This kernel is for batches of molecules, not for one large system: a molecule is one wave's work.
-#include "common.h"
+// the four waves of a workgroup share nothing.  A molecule without constraints takes nnhip_md_step's chain (the same functions of
+// csrc/md_chain.h, one atom per lane), bit for bit, without LDS or relative coordinates.  This kernel is for batches of molecules,
+// not for one large system: a molecule is one wave's work.
+#include "md_chain.h"
 
 namespace {
 
@@ -193,22 +194,12 @@ __device__ void unconstrained(const RattleArgs& g, int a0, int a1, int lane) {
     float v[3] = {g.vel[o], g.vel[o + 1], g.vel[o + 2]};
     const float f[3] = {g.force[o], g.force[o + 1], g.force[o + 2]};
     if (finish) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] = __fmaf_rn(hk, f[k], v[k]);
-      if (g.ke_out) {
-        const float s = __fmaf_rn(v[2], v[2], __fmaf_rn(v[1], v[1], __fmul_rn(v[0], v[0])));
-        g.ke_out[i] = __fmul_rn(__fmul_rn(0.5f, g.mass[i]), s);
-      }
+      md_chain::half_kick(v, hk, f);
+      if (g.ke_out) g.ke_out[i] = md_chain::kinetic(v, g.mass[i]);
     }
     if (begin) {
       const float sigma = g.noise ? g.sigma[i] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        v[k] = __fmaf_rn(hk, f[k], v[k]);
-        float x = __fmaf_rn(g.dth, v[k], g.pos_in[o + k]);
-        if (g.noise) v[k] = __fmaf_rn(sigma, g.noise[o + k], __fmul_rn(g.c1, v[k]));
-        g.pos_out[o + k] = __fmaf_rn(g.dth, v[k], x);
-      }
+      md_chain::begin<false>(v, hk, f, g.pos_in + o, g.pos_out + o, g.dth, sigma, g.noise ? g.noise + o : nullptr, g.c1, 1.f, 1.f);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) g.vel[o + k] = v[k];
@@ -279,38 +270,21 @@ md_step_constrained_kernel(RattleArgs g) {
       sweeps = imax(sweeps, project(g, y, v, w, n, k0, k1, lane, fail));
     }
     if (finish) {
-      for (int i = lane; i < n; i += 64) {
-        const size_t o = 3 * (size_t)(a0 + i);
-        const float hk = g.hk[a0 + i];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[3 * i + k] = __fmaf_rn(hk, g.force[o + k], v[3 * i + k]);
-      }
+      for (int i = lane; i < n; i += 64) md_chain::half_kick(v + 3 * i, g.hk[a0 + i], g.force + 3 * (size_t)(a0 + i));
       wave_sync();
       sweeps = imax(sweeps, project(g, y, v, w, n, k0, k1, lane, fail));
       if (g.ke_out) {
-        for (int i = lane; i < n; i += 64) {
-          const float s = __fmaf_rn(v[3 * i + 2], v[3 * i + 2], __fmaf_rn(v[3 * i + 1], v[3 * i + 1], __fmul_rn(v[3 * i], v[3 * i])));
-          g.ke_out[a0 + i] = __fmul_rn(__fmul_rn(0.5f, g.mass[a0 + i]), s);
-        }
+        for (int i = lane; i < n; i += 64) g.ke_out[a0 + i] = md_chain::kinetic(v + 3 * i, g.mass[a0 + i]);
       }
     }
     if (begin) {
-      for (int i = lane; i < n; i += 64) {
-        const size_t o = 3 * (size_t)(a0 + i);
-        const float hk = g.hk[a0 + i];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[3 * i + k] = __fmaf_rn(hk, g.force[o + k], v[3 * i + k]);
-      }
+      for (int i = lane; i < n; i += 64) md_chain::half_kick(v + 3 * i, g.hk[a0 + i], g.force + 3 * (size_t)(a0 + i));
       wave_sync();
       sweeps = imax(sweeps, project(g, y, v, w, n, k0, k1, lane, fail));
       for (int half = 0; half < 2; ++half) {
         if (half == 1 && g.noise) {
-          for (int i = lane; i < n; i += 64) {
-            const size_t o = 3 * (size_t)(a0 + i);
-            const float sigma = g.sigma[a0 + i];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) v[3 * i + k] = __fmaf_rn(sigma, g.noise[o + k], __fmul_rn(g.c1, v[3 * i + k]));
-          }
+          for (int i = lane; i < n; i += 64)
+            md_chain::o_step(v + 3 * i, g.sigma[a0 + i], g.noise + 3 * (size_t)(a0 + i), g.c1);
           wave_sync();
           sweeps = imax(sweeps, project(g, y, v, w, n, k0, k1, lane, fail));
         }
@@ -348,8 +322,6 @@ md_step_constrained_kernel(RattleArgs g) {
     }
   }
 }
-
-inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
 
 // a [n + 1] offset table: starts at 0, never decreases, ends at `last`
 inline bool offsets_ok(const int32_t* p, int n, int last) {

@@ -292,8 +292,6 @@ lbfgs_step_kernel(RelaxArgs g) {
   }
 }
 
-inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }
-
 }  // namespace
 
 extern "C" int nnhip_lbfgs_step(const float* pos_in, const float* force, const uint8_t* free_mask, const int32_t* mol_ptr,

@@ -591,6 +591,44 @@ def segment_sum(x: torch.Tensor, row_ptr: torch.Tensor, n_rows: int) -> torch.Te
     return out
 
 
+def _written(dev, optional=(), **tensors):
+    """tensors a kernel writes in place, name=(tensor, numel) or (tensor, numel, dtype), float32 unless stated: contiguous, of
+    exactly that dtype, on `dev` (a copy would take the result away); None only under the names in `optional`"""
+    for name, (t, numel, *dtype) in tensors.items():
+        if t is None and name in optional:
+            continue
+        dtype = dtype[0] if dtype else torch.float32
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f'{name}: a contiguous {str(dtype)[6:]} tensor expected (it is written in place)')
+        if t.numel() != numel or t.device != dev:
+            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+
+
+def _read(dev, **tensors):
+    """tensors a kernel reads: float32 (made contiguous) with the stated number of values on `dev`; None stays None"""
+    out = []
+    for name, (t, numel) in tensors.items():
+        if t is not None:
+            t = _f32c(t, name)
+            if t.numel() != numel or t.device != dev:
+                raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+        out.append(t)
+    return out
+
+
+def _offsets(name, t, dev=None, host=False) -> int:
+    """an int32 offset table [n+1]: contiguous, at least one value, on `dev` when one is given; `host`, unless False: its copy on
+    the CPU, of the same length.  Returns n."""
+    for label, x in ((name, t),) if host is False else ((name, t), (name + '_host', host)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or not x.is_contiguous() or x.numel() < 1:
+            raise ValueError(f'{label}: a contiguous int32 tensor [n+1] expected')
+    if dev is not None and t.device != dev:
+        raise ValueError(f'{name}: on {dev} expected (it is on {t.device})')
+    if host is not False and (host.device.type != 'cpu' or host.numel() != t.numel()):
+        raise ValueError(f'{name}_host: the host copy of {name} expected')
+    return t.numel() - 1
+
+
 MD_FINISH, MD_BEGIN = _K['NNHIP_MD_FINISH'], _K['NNHIP_MD_BEGIN']      # flags of nnhip_md_step
 
 
@@ -601,20 +639,12 @@ def md_step(pos_in: Optional[torch.Tensor], vel: torch.Tensor, force: torch.Tens
     `force` (and the per-atom kinetic energies into `ke_out`), MD_BEGIN = half kick, half drift, the exact Ornstein-Uhlenbeck
     step v = c1 v + sigma noise (only with `noise`), half drift.  `vel` is updated in place and `pos_out` written: both must be
     contiguous float32 (a copy would take the result away); `pos_out` may not overlap `pos_in`."""
-    for name, t in (('vel', vel), ('pos_out', pos_out), ('ke_out', ke_out)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
-    N = vel.shape[0]
-    ins = [None if t is None else _f32c(t, name) for name, t in (('pos_in', pos_in), ('force', force), ('hk', hk), ('mass', mass),
-                                                                 ('sigma', sigma), ('noise', noise))]
-    for name, t, numel in (('pos_in', ins[0], 3 * N), ('force', ins[1], 3 * N), ('hk', ins[2], N), ('mass', ins[3], N),
-                           ('sigma', ins[4], N), ('noise', ins[5], 3 * N), ('pos_out', pos_out, 3 * N), ('ke_out', ke_out, N),
-                           ('vel', vel, 3 * N)):
-        if t is not None and (t.numel() != numel or t.device != vel.device):
-            raise ValueError(f'{name}: {numel} values on {vel.device} expected (got {t.numel()} on {t.device})')
-    _check(lib().nnhip_md_step(_ptr(ins[0]), _ptr(vel), _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]), _ptr(ins[5]),
-                               float(dth), float(c1), int(flags), N, _ptr(pos_out), _ptr(ke_out), _stream(vel.device)),
-           'nnhip_md_step')
+    N, dev = vel.shape[0], vel.device
+    _written(dev, optional=('pos_out', 'ke_out'), vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), ke_out=(ke_out, N))
+    pos_in, force, hk, mass, sigma, noise = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), hk=(hk, N), mass=(mass, N),
+                                                  sigma=(sigma, N), noise=(noise, 3 * N))
+    _check(lib().nnhip_md_step(_ptr(pos_in), _ptr(vel), _ptr(force), _ptr(hk), _ptr(mass), _ptr(sigma), _ptr(noise), float(dth),
+                               float(c1), int(flags), N, _ptr(pos_out), _ptr(ke_out), _stream(dev)), 'nnhip_md_step')
 
 
 def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -633,29 +663,6 @@ def md_kinetic(ke: torch.Tensor, mol_ptr: torch.Tensor, out: Optional[torch.Tens
     return out
 
 
-def _written(dev, **tensors):
-    """tensors a kernel writes in place: contiguous float32 on `dev` (a copy would take the result away)"""
-    for name, (t, numel) in tensors.items():
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
-        if t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
-
-
-def _read(dev, **tensors):
-    """tensors a kernel reads: float32 (made contiguous) with the stated number of values on `dev`; None stays None"""
-    out = []
-    for name, (t, numel) in tensors.items():
-        if t is not None:
-            t = _f32c(t, name)
-            if t.numel() != numel or t.device != dev:
-                raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
-        out.append(t)
-    return out
-
-
 def npt_barostat(vel: torch.Tensor, mass: torch.Tensor, mol_ptr: torch.Tensor, cell_in: torch.Tensor, virial: torch.Tensor,
                  a: torch.Tensor, p0: torch.Tensor, cell_out: torch.Tensor, mu: torch.Tensor, inv_mu: torch.Tensor,
                  ke: torch.Tensor, pressure: torch.Tensor, volume: torch.Tensor, deps: torch.Tensor,
@@ -666,11 +673,8 @@ def npt_barostat(vel: torch.Tensor, mass: torch.Tensor, mol_ptr: torch.Tensor, c
     pending half kick hk x force, or `vel` itself without `force`), V = det(cell_in), P = (2 K + tr virial) / (3 V), the step
     deps = -a (p0 - P) + sqrt(s2 / V) noise of ln V and mu = exp(deps / 3).  Writes cell_out = mu cell_in [B,3,3], mu, inv_mu and
     the records ke, pressure, volume, deps [B]: all contiguous float32; `cell_out` may not overlap `cell_in`.  mol_ptr int32 [B+1]."""
-    if mol_ptr.dtype != torch.int32 or not mol_ptr.is_contiguous() or mol_ptr.numel() < 1:
-        raise ValueError('mol_ptr: contiguous int32 [B+1] expected')
-    B, N, dev = mol_ptr.numel() - 1, vel.shape[0], vel.device
-    if mol_ptr.device != dev:
-        raise ValueError(f'mol_ptr is on {mol_ptr.device}, vel on {dev}')
+    N, dev = vel.shape[0], vel.device
+    B = _offsets('mol_ptr', mol_ptr, dev)
     _written(dev, cell_out=(cell_out, 9 * B), mu=(mu, B), inv_mu=(inv_mu, B), ke=(ke, B), pressure=(pressure, B),
              volume=(volume, B), deps=(deps, B))
     vel, force, hk, mass, cell_in, virial, a, p0, s2, noise = _read(
@@ -686,12 +690,12 @@ def npt_step(pos_in: Optional[torch.Tensor], vel: torch.Tensor, force: torch.Ten
              mol_of_atom: Optional[torch.Tensor] = None, pos_out: Optional[torch.Tensor] = None,
              mass: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
              ke_out: Optional[torch.Tensor] = None):
-    """One launch of the constant-pressure integrator (nnhip_npt_step, csrc/npt.hip) on the current stream: md_step's flags and
+    """One launch of the constant-pressure integrator (nnhip_npt_step, csrc/md.hip) on the current stream: md_step's flags and
     chain with the rescale  x = mu_b x, v = inv_mu_b v  of the atom's system b = mol_of_atom[i] (int32 [N]) between the MD_BEGIN kick
     and the first half drift.  mu, inv_mu: float32 [B] as nnhip_npt_barostat wrote them.  `vel` is updated in place and `pos_out`
     written: both contiguous float32; `pos_out` may not overlap `pos_in`."""
     N, dev = vel.shape[0], vel.device
-    _written(dev, vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), ke_out=(ke_out, N))
+    _written(dev, optional=('pos_out', 'ke_out'), vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), ke_out=(ke_out, N))
     n_mol = 0
     if mu is not None or inv_mu is not None:
         if mu is None or inv_mu is None or mu.numel() != inv_mu.numel():
@@ -740,38 +744,23 @@ def md_step_constrained(pos_in: torch.Tensor, vel: torch.Tensor, force: Optional
     of `tables`, or MDC_PROJECT alone (the constraints imposed on pos_in and vel).  pos_in is always read.  `vel` is updated in
     place, `pos_out`, `ke_out` are written and `n_failed`, `n_sweeps` (int32 [B]) updated: all of these must be contiguous tensors
     of exactly that type (a copy would take the result away); `pos_out` may not overlap `pos_in`."""
-    for name, t in (('vel', vel), ('pos_out', pos_out), ('ke_out', ke_out)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
     N, dev = vel.shape[0], vel.device
-    ins = [None if t is None else _f32c(t, name) for name, t in (('pos_in', pos_in), ('force', force), ('hk', hk), ('mass', mass),
-                                                                 ('inv_mass', inv_mass), ('sigma', sigma), ('noise', noise))]
-    for name, t, numel in (('pos_in', ins[0], 3 * N), ('force', ins[1], 3 * N), ('hk', ins[2], N), ('mass', ins[3], N),
-                           ('inv_mass', ins[4], N), ('sigma', ins[5], N), ('noise', ins[6], 3 * N), ('pos_out', pos_out, 3 * N),
-                           ('ke_out', ke_out, N), ('vel', vel, 3 * N)):
-        if t is not None and (t.numel() != numel or t.device != dev):
-            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
-    for name in ('mol_ptr', 'mol_col_ptr', 'col_ptr'):
-        d, h = getattr(tables, name), getattr(tables, name + '_host')
-        for label, t, where in ((name, d, dev.type), (name + '_host', h, 'cpu')):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1 \
-                    or t.device.type != where:
-                raise ValueError(f'{label}: a contiguous int32 tensor on {where} expected')
-        if d.numel() != h.numel():
-            raise ValueError(f'{name}_host: the host copy of {name} expected')
-    B, K = tables.mol_ptr.numel() - 1, tables.col_ptr.numel() - 1
-    if tables.mol_col_ptr.numel() != B + 1:
+    B = _offsets('mol_ptr', tables.mol_ptr, dev, tables.mol_ptr_host)
+    if _offsets('mol_col_ptr', tables.mol_col_ptr, dev, tables.mol_col_ptr_host) != B:
         raise ValueError(f'mol_col_ptr: int32 [{B + 1}] expected')
+    K = _offsets('col_ptr', tables.col_ptr, dev, tables.col_ptr_host)
     C_ = int(tables.col_ptr_host[K])
     pair, d2 = tables.con_pair, tables.con_d2
     if (pair.dtype != torch.int32 or not pair.is_contiguous() or pair.device != dev or d2.dtype != torch.float32
             or not d2.is_contiguous() or d2.device != dev or pair.numel() < 2 * C_ or d2.numel() < C_):
         raise ValueError(f'con_pair: contiguous int32 [{C_},2] and con_d2: contiguous float32 [{C_}] on {dev} expected')
-    for name, t in (('n_failed', n_failed), ('n_sweeps', n_sweeps)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B or t.device != dev:
-            raise ValueError(f'{name}: a contiguous int32 tensor of {B} values on {dev} expected (it is written in place)')
+    _written(dev, optional=('pos_out', 'ke_out'), vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), ke_out=(ke_out, N),
+             n_failed=(n_failed, B, torch.int32), n_sweeps=(n_sweeps, B, torch.int32))
+    pos_in, force, hk, mass, inv_mass, sigma, noise = _read(
+        dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), hk=(hk, N), mass=(mass, N), inv_mass=(inv_mass, N), sigma=(sigma, N),
+        noise=(noise, 3 * N))
     _check(lib().nnhip_md_step_constrained(
-        _ptr(ins[0]), _ptr(vel), _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]), _ptr(ins[5]), _ptr(ins[6]), float(dth),
+        _ptr(pos_in), _ptr(vel), _ptr(force), _ptr(hk), _ptr(mass), _ptr(inv_mass), _ptr(sigma), _ptr(noise), float(dth),
         float(inv_dth), float(c1), int(flags), N, _ptr(tables.mol_ptr), _ptr(tables.mol_ptr_host), B, _ptr(pair), _ptr(d2),
         _ptr(tables.mol_col_ptr), _ptr(tables.mol_col_ptr_host), _ptr(tables.col_ptr), _ptr(tables.col_ptr_host), K, float(tol),
         int(max_iter), _ptr(pos_out), _ptr(ke_out), _ptr(n_failed), _ptr(n_sweeps), _stream(dev)), 'nnhip_md_step_constrained')
@@ -792,30 +781,18 @@ def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.T
     [B,memory]; f_prev fp32 [N,3]) is updated in place, pos_out [N,3] and fmax_out [B] are written: all of these must be contiguous
     tensors of exactly that type (a copy would take the result away).  work: fp32 [N,3] scratch, needed when N > 64.  pos_out may
     not overlap pos_in."""
-    if mol_ptr.dtype != torch.int32 or not mol_ptr.is_contiguous() or mol_ptr.numel() < 1:
-        raise ValueError('mol_ptr: contiguous int32 [B+1] expected')
-    dev, B, m = mol_ptr.device, mol_ptr.numel() - 1, int(memory)
+    B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
     if pos_out.dim() != 2 or pos_out.shape[1] != 3:
         raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
-    N = pos_out.shape[0]
-    for name, t, dtype, numel in (('converged', converged, torch.int32, B), ('n_steps', n_steps, torch.int32, B),
-                                  ('n_pairs', n_pairs, torch.int32, B), ('head', head, torch.int32, B),
-                                  ('S', S, torch.float32, m * N * 3), ('Y', Y, torch.float32, m * N * 3),
-                                  ('rho', rho, torch.float32, B * m), ('f_prev', f_prev, torch.float32, 3 * N),
-                                  ('work', work, torch.float32, 3 * N), ('pos_out', pos_out, torch.float32, 3 * N),
-                                  ('fmax_out', fmax_out, torch.float32, B)):
-        if t is None and name == 'work':
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != max(numel, 0) or t.device != dev:
-            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
-    pos_in, force = _f32c(pos_in, 'pos_in'), _f32c(force, 'force')
+    N, rows = pos_out.shape[0], max(m, 0)
+    _written(dev, optional=('work',), converged=(converged, B, i32), n_steps=(n_steps, B, i32), n_pairs=(n_pairs, B, i32),
+             head=(head, B, i32), S=(S, rows * N * 3), Y=(Y, rows * N * 3), rho=(rho, B * rows), f_prev=(f_prev, 3 * N),
+             work=(work, 3 * N), pos_out=(pos_out, 3 * N), fmax_out=(fmax_out, B))
     if free is not None:
         if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
             raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
         free = free.contiguous()
-    for name, t in (('pos_in', pos_in), ('force', force)):
-        if t.numel() != 3 * N or t.device != dev:
-            raise ValueError(f'{name}: {3 * N} values on {dev} expected (got {t.numel()} on {t.device})')
+    pos_in, force = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N))
     _check(lib().nnhip_lbfgs_step(_ptr(pos_in), _ptr(force), _ptr(free), _ptr(mol_ptr), B, N, m, float(tol2), float(alpha),
                                   float(maxstep), int(flags), _ptr(converged), _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S),
                                   _ptr(Y), _ptr(rho), _ptr(f_prev), _ptr(work), _ptr(pos_out), _ptr(fmax_out), _stream(dev)),
@@ -840,31 +817,19 @@ def neb_step(pos_in: torch.Tensor, force: torch.Tensor, energy: torch.Tensor, fr
     [K]; dt, a fp32 [K]; vel fp32 [N,3]) is updated in place, pos_out, neb_force_out, tangent_out [N,3], fmax_out [K] and saddle_out
     (int32 [K]) are written: all of these must be contiguous tensors of exactly that type (a copy would take the result away).
     pos_out may not overlap pos_in."""
-    for name, t in (('mol_ptr', mol_ptr), ('band_ptr', band_ptr), ('band_ptr_host', band_ptr_host)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
-            raise ValueError(f'{name}: contiguous int32 expected')
-    if band_ptr_host.device.type != 'cpu' or band_ptr_host.numel() != band_ptr.numel():
-        raise ValueError('band_ptr_host: the host copy of band_ptr expected')
-    dev, B, K = mol_ptr.device, mol_ptr.numel() - 1, band_ptr.numel() - 1
+    B, dev, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, torch.int32
+    K = _offsets('band_ptr', band_ptr, dev, band_ptr_host)
     if pos_out.dim() != 2 or pos_out.shape[1] != 3:
         raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
     N = pos_out.shape[0]
-    for name, t, dtype, numel in (('converged', converged, torch.int32, K), ('climbing', climbing, torch.int32, K),
-                                  ('n_steps', n_steps, torch.int32, K), ('n_pos', n_pos, torch.int32, K),
-                                  ('dt', dt, torch.float32, K), ('a', a, torch.float32, K), ('vel', vel, torch.float32, 3 * N),
-                                  ('pos_out', pos_out, torch.float32, 3 * N), ('neb_force_out', neb_force_out, torch.float32, 3 * N),
-                                  ('tangent_out', tangent_out, torch.float32, 3 * N), ('fmax_out', fmax_out, torch.float32, K),
-                                  ('saddle_out', saddle_out, torch.int32, K)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
-    pos_in, force, energy = _f32c(pos_in, 'pos_in'), _f32c(force, 'force'), _f32c(energy, 'energy')
+    _written(dev, converged=(converged, K, i32), climbing=(climbing, K, i32), n_steps=(n_steps, K, i32), n_pos=(n_pos, K, i32),
+             dt=(dt, K), a=(a, K), vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), neb_force_out=(neb_force_out, 3 * N),
+             tangent_out=(tangent_out, 3 * N), fmax_out=(fmax_out, K), saddle_out=(saddle_out, K, i32))
     if free is not None:
         if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
             raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
         free = free.contiguous()
-    for name, t, numel in (('pos_in', pos_in, 3 * N), ('force', force, 3 * N), ('energy', energy, B), ('band_ptr', band_ptr, K + 1)):
-        if t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
+    pos_in, force, energy = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), energy=(energy, B))
     dt0, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep = fire
     _check(lib().nnhip_neb_step(_ptr(pos_in), _ptr(force), _ptr(energy), _ptr(free), _ptr(mol_ptr), _ptr(band_ptr),
                                 _ptr(band_ptr_host), K, B, N, float(spring), float(tol2), float(climb2), float(dt0), float(dt_max),
@@ -890,41 +855,25 @@ def remd_exchange(energy: torch.Tensor, mol_ptr: torch.Tensor, mol_ptr_host: tor
     n_accept (int32 [B]), vel [N,3] and sigma [N] are updated in place, delta_out, u_out (fp32 [B]) and accepted_out (int32 [B]) are
     written when given: all of these must be contiguous tensors of exactly that type (a copy would take the result away).
     attempt: the attempt number (its low bit is the parity), an int in 0 .. 2^32 - 1; seed: an int in 0 .. 2^64 - 1."""
-    for name, t in (('mol_ptr', mol_ptr), ('ladder_ptr', ladder_ptr), ('mol_ptr_host', mol_ptr_host),
-                    ('ladder_ptr_host', ladder_ptr_host)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
-            raise ValueError(f'{name}: contiguous int32 expected')
-    if ladder_ptr_host.device.type != 'cpu' or ladder_ptr_host.numel() != ladder_ptr.numel():
-        raise ValueError('ladder_ptr_host: the host copy of ladder_ptr expected')
-    if mol_ptr_host.device.type != 'cpu' or mol_ptr_host.numel() != mol_ptr.numel():
-        raise ValueError('mol_ptr_host: the host copy of mol_ptr expected')
+    B, dev, i32 = _offsets('mol_ptr', mol_ptr, host=mol_ptr_host), mol_ptr.device, torch.int32
+    G = _offsets('ladder_ptr', ladder_ptr, dev, ladder_ptr_host)
     if int(attempt) != attempt or not 0 <= attempt < 2 ** 32 or int(seed) != seed or not 0 <= seed < 2 ** 64:
         raise ValueError(f'attempt: an integer in 0 .. 2^32 - 1 and seed: one in 0 .. 2^64 - 1 expected (got {attempt!r}, {seed!r})')
-    dev, B, G = mol_ptr.device, mol_ptr.numel() - 1, ladder_ptr.numel() - 1
     if vel.dim() != 2 or vel.shape[1] != 3:
         raise ValueError(f'vel: [N,3] expected (got {tuple(vel.shape)})')
     N = vel.shape[0]
     if sigma_table.dim() != 2 or sigma_table.shape[1] != N:
         raise ValueError(f'sigma_table: [n_rows,{N}] expected (got {tuple(sigma_table.shape)})')
     n_rows = sigma_table.shape[0]
-    for name, t, dtype, numel in (('rank_of_slot', rank_of_slot, torch.int32, B), ('slot_of_rank', slot_of_rank, torch.int32, B),
-                                  ('n_attempt', n_attempt, torch.int32, B), ('n_accept', n_accept, torch.int32, B),
-                                  ('vel', vel, torch.float32, 3 * N), ('sigma', sigma, torch.float32, N),
-                                  ('delta_out', delta_out, torch.float32, B), ('u_out', u_out, torch.float32, B),
-                                  ('accepted_out', accepted_out, torch.int32, B)):
-        if t is None and name.endswith('_out'):
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
-    energy, dbeta, scale_up, scale_down, sigma_table = (_f32c(t, name) for name, t in (
-        ('energy', energy), ('dbeta', dbeta), ('scale_up', scale_up), ('scale_down', scale_down), ('sigma_table', sigma_table)))
-    if stream_id.dtype != torch.int32:
-        raise ValueError('stream_id: int32 expected (the bits of a uint32)')
+    _written(dev, optional=('delta_out', 'u_out', 'accepted_out'), rank_of_slot=(rank_of_slot, B, i32),
+             slot_of_rank=(slot_of_rank, B, i32), n_attempt=(n_attempt, B, i32), n_accept=(n_accept, B, i32), vel=(vel, 3 * N),
+             sigma=(sigma, N), delta_out=(delta_out, B), u_out=(u_out, B), accepted_out=(accepted_out, B, i32))
+    energy, dbeta, scale_up, scale_down, sigma_table = _read(
+        dev, energy=(energy, B), dbeta=(dbeta, B), scale_up=(scale_up, B), scale_down=(scale_down, B),
+        sigma_table=(sigma_table, n_rows * N))
+    if stream_id.dtype != torch.int32 or stream_id.numel() != G or stream_id.device != dev:
+        raise ValueError(f'stream_id: int32 (the bits of a uint32), {G} values on {dev} expected')
     stream_id = stream_id.contiguous()
-    for name, t, numel in (('energy', energy, B), ('dbeta', dbeta, B), ('scale_up', scale_up, B), ('scale_down', scale_down, B),
-                           ('stream_id', stream_id, G), ('ladder_ptr', ladder_ptr, G + 1), ('sigma_table', sigma_table, n_rows * N)):
-        if t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
     attempt, seed = int(attempt), int(seed)
     # (the C ABI has signed scalars only: the same bits)
     _check(lib().nnhip_remd_exchange(_ptr(energy), _ptr(mol_ptr), _ptr(mol_ptr_host), _ptr(ladder_ptr), _ptr(ladder_ptr_host),
@@ -956,32 +905,19 @@ def pimd_step(u: torch.Tensor, w: torch.Tensor, force: torch.Tensor, ctab: torch
     place and `pos_out`, `est_out` written: these must be contiguous float32 (a copy would take the result away).  ctab [P,P],
     mode_tab [B,5], hk, mass, sigma [N], noise [N,3] are read.  `pos_out` may not overlap `pos_pending`, the positions the pending
     forward call read."""
-    for name, t in (('mol_ptr', mol_ptr), ('mol_ptr_host', mol_ptr_host)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
-            raise ValueError(f'{name}: contiguous int32 expected')
-    if mol_ptr_host.device.type != 'cpu' or mol_ptr_host.numel() != mol_ptr.numel():
-        raise ValueError('mol_ptr_host: the host copy of mol_ptr expected')
     if isinstance(n_beads, bool) or int(n_beads) != n_beads:
         raise ValueError(f'n_beads: an integer expected (got {n_beads!r})')
-    P, B = int(n_beads), mol_ptr.numel() - 1
-    for name, t in (('u', u), ('w', w), ('pos_out', pos_out), ('est_out', est_out)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f'{name}: a contiguous float32 tensor expected (it is written in place)')
     if u.dim() != 2 or u.shape[1] != 3:
         raise ValueError(f'u: [N,3] expected (got {tuple(u.shape)})')
-    N, dev = u.shape[0], u.device
-    names = ('force', 'ctab', 'mode_tab', 'hk', 'mass', 'sigma', 'noise', 'pos_pending')
-    ins = dict(zip(names, (force, ctab, mode_tab, hk, mass, sigma, noise, pos_pending)))
-    ins = {name: None if t is None else _f32c(t, name) for name, t in ins.items()}
-    sizes = dict(force=3 * N, ctab=max(P, 0) ** 2, mode_tab=5 * B, hk=N, mass=N, sigma=N, noise=3 * N, pos_pending=3 * N)
-    for name, t, numel in [(k, ins[k], sizes[k]) for k in names] + [('w', w, 3 * N), ('pos_out', pos_out, 3 * N),
-                                                                     ('est_out', est_out, 4 * N), ('mol_ptr', mol_ptr, B + 1)]:
-        if t is not None and (t.numel() != numel or t.device != dev):
-            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
-    _check(lib().nnhip_pimd_step(_ptr(u), _ptr(w), _ptr(ins['force']), _ptr(ins['ctab']), _ptr(ins['mode_tab']), _ptr(ins['hk']),
-                                 _ptr(ins['mass']), _ptr(ins['sigma']), _ptr(ins['noise']), _ptr(mol_ptr), _ptr(mol_ptr_host),
-                                 _ptr(ins['pos_pending']), int(flags), P, B, N, _ptr(pos_out), _ptr(est_out), _stream(dev)),
-           'nnhip_pimd_step')
+    P, N, dev = int(n_beads), u.shape[0], u.device
+    B = _offsets('mol_ptr', mol_ptr, dev, mol_ptr_host)
+    _written(dev, optional=('pos_out', 'est_out'), u=(u, 3 * N), w=(w, 3 * N), pos_out=(pos_out, 3 * N), est_out=(est_out, 4 * N))
+    force, ctab, mode_tab, hk, mass, sigma, noise, pos_pending = _read(
+        dev, force=(force, 3 * N), ctab=(ctab, max(P, 0) ** 2), mode_tab=(mode_tab, 5 * B), hk=(hk, N), mass=(mass, N),
+        sigma=(sigma, N), noise=(noise, 3 * N), pos_pending=(pos_pending, 3 * N))
+    _check(lib().nnhip_pimd_step(_ptr(u), _ptr(w), _ptr(force), _ptr(ctab), _ptr(mode_tab), _ptr(hk), _ptr(mass), _ptr(sigma),
+                                 _ptr(noise), _ptr(mol_ptr), _ptr(mol_ptr_host), _ptr(pos_pending), int(flags), P, B, N,
+                                 _ptr(pos_out), _ptr(est_out), _stream(dev)), 'nnhip_pimd_step')
 
 
 BIAS_MAX_CVS, BIAS_THREADS = _K['NNHIP_BIAS_MAX_CVS'], _K['NNHIP_BIAS_THREADS']
@@ -1001,38 +937,25 @@ def bias_step(pos: torch.Tensor, force_in: torch.Tensor, mol_ptr: torch.Tensor, 
     BIAS_DEPOSIT, written at the W rows from there; force_out [N,3], cv_out, bias_out [B,2] and status_out (int32 [B]) are
     written: these must be contiguous tensors of exactly that type (a copy would take the result away).  force_out may overlap
     neither force_in nor pos."""
-    for name, t in (('mol_ptr', mol_ptr), ('group_ptr', group_ptr), ('mol_ptr_host', mol_ptr_host), ('group_ptr_host', group_ptr_host)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < 1:
-            raise ValueError(f'{name}: contiguous int32 expected')
-    if group_ptr_host.device.type != 'cpu' or group_ptr_host.numel() != group_ptr.numel():
-        raise ValueError('group_ptr_host: the host copy of group_ptr expected')
-    if mol_ptr_host.device.type != 'cpu' or mol_ptr_host.numel() != mol_ptr.numel():
-        raise ValueError('mol_ptr_host: the host copy of mol_ptr expected')
+    B, dev = _offsets('mol_ptr', mol_ptr, host=mol_ptr_host), mol_ptr.device
+    G = _offsets('group_ptr', group_ptr, dev, group_ptr_host)
     if isinstance(n_deposits, bool) or int(n_deposits) != n_deposits or not 0 <= n_deposits < 2 ** 31:
         raise ValueError(f'n_deposits: an integer in 0 .. 2^31 - 1 expected (got {n_deposits!r})')
     if isinstance(flags, bool) or int(flags) != flags or not 0 <= flags < 2 ** 31:
         raise ValueError(f'flags: an integer >= 0 expected (got {flags!r})')
-    dev, B, G = mol_ptr.device, mol_ptr.numel() - 1, group_ptr.numel() - 1
     if not isinstance(force_out, torch.Tensor) or force_out.dim() != 2 or force_out.shape[1] != 3:
         raise ValueError('force_out: a tensor [N,3] expected')
     N = force_out.shape[0]
     if not isinstance(hills, torch.Tensor) or hills.dim() != 3 or hills.shape[0] != G or hills.shape[2] != 4:
         raise ValueError(f'hills: [{G},capacity,4] expected')
     capacity = hills.shape[1]
-    for name, t, dtype, numel in (('hills', hills, torch.float32, G * capacity * 4), ('force_out', force_out, torch.float32, 3 * N),
-                                  ('cv_out', cv_out, torch.float32, 2 * B), ('bias_out', bias_out, torch.float32, 2 * B),
-                                  ('status_out', status_out, torch.int32, B)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: a contiguous {dtype} tensor of {numel} values on {dev} expected (it is written in place)')
-    pos, force_in, restraint, hill_par = (_f32c(t, name) for name, t in (('pos', pos), ('force_in', force_in),
-                                                                         ('restraint', restraint), ('hill_par', hill_par)))
-    if cv_def.dtype != torch.int32:
-        raise ValueError('cv_def: int32 expected')
+    _written(dev, hills=(hills, G * capacity * 4), force_out=(force_out, 3 * N), cv_out=(cv_out, 2 * B), bias_out=(bias_out, 2 * B),
+             status_out=(status_out, B, torch.int32))
+    pos, force_in, restraint, hill_par = _read(dev, pos=(pos, 3 * N), force_in=(force_in, 3 * N),
+                                               restraint=(restraint, B * BIAS_MAX_CVS * 2), hill_par=(hill_par, G * 4))
+    if cv_def.dtype != torch.int32 or cv_def.numel() != B * BIAS_MAX_CVS * 5 or cv_def.device != dev:
+        raise ValueError(f'cv_def: int32, {B * BIAS_MAX_CVS * 5} values on {dev} expected')
     cv_def = cv_def.contiguous()
-    for name, t, numel in (('pos', pos, 3 * N), ('force_in', force_in, 3 * N), ('cv_def', cv_def, B * BIAS_MAX_CVS * 5),
-                           ('restraint', restraint, B * BIAS_MAX_CVS * 2), ('hill_par', hill_par, G * 4), ('group_ptr', group_ptr, G + 1)):
-        if t.numel() != numel or t.device != dev:
-            raise ValueError(f'{name}: {numel} values on {dev} expected (got {t.numel()} on {t.device})')
     _check(lib().nnhip_bias_step(_ptr(pos), _ptr(force_in), _ptr(mol_ptr), _ptr(mol_ptr_host), _ptr(group_ptr), _ptr(group_ptr_host),
                                  _ptr(cv_def), _ptr(restraint), _ptr(hill_par), _ptr(hills), capacity, int(n_deposits), int(flags), G,
                                  B, N, _ptr(force_out), _ptr(cv_out), _ptr(bias_out), _ptr(status_out), _stream(dev)),

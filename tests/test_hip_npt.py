@@ -106,6 +106,28 @@ def test_barostat_against_fp64_on_the_same_inputs(triclinic, with_force, with_no
             assert torch.equal(off[k], got[k])
 
 
+@pytest.mark.parametrize('with_force', [False, True])
+def test_barostat_kinetic_energy_is_the_step_kernels(with_force):
+    """Five systems of one atom each: the barostat's tree sum is 0 + ke_i plus zeros, exact, so ke[b] must carry the bits of
+    nnhip_md_step's ke_out[b] on the same vel, hk, force and mass (no pending force = a zero force in md_step: fma(hk, 0, v) = v)."""
+    from newtonnet_amd import hip
+    rng = np.random.default_rng(77)
+    f32, B = np.float32, 5
+    m = np.array([1.008, 12.011, 14.007, 15.999, 32.06], dtype=f32)
+    v = (rng.standard_normal((B, 3)) * np.sqrt(K_B * 300.0 / m.astype(np.float64))[:, None]).astype(f32)
+    d = dict(ptr=np.arange(B + 1, dtype=np.int32), m=m, v=v, F=rng.uniform(-5, 5, (B, 3)).astype(f32),
+             hk=(0.5 * DT / m.astype(np.float64)).astype(f32), cell=np.tile(np.diag([10.0, 11.0, 12.0]).astype(f32), (B, 1, 1)),
+             W=rng.normal(0, 4.0, (B, 3, 3)).astype(f32), a=np.full(B, 0.2, dtype=f32), p0=np.zeros(B, dtype=f32),
+             s2=np.zeros(B, dtype=f32), xi=np.zeros(B, dtype=f32))
+    t = {k: torch.from_numpy(x).cuda() for k, x in d.items()}
+    ke = _launch_barostat(t, with_force, False)['ke']
+    vel, ke_out = t['v'].clone(), torch.full((B,), 777.0, device='cuda')
+    hip.md_step(None, vel, t['F'] if with_force else torch.zeros_like(t['F']), t['hk'], 0.5 * DT, 1.0, hip.MD_FINISH, mass=t['m'],
+                ke_out=ke_out)
+    assert torch.equal(vel, t['v']) != with_force and torch.all(ke_out > 0)            # the kick was applied iff a force is pending
+    assert torch.equal(ke.view(torch.int32), ke_out.view(torch.int32)), f'ke {ke.tolist()} is not md_step ke_out {ke_out.tolist()}'
+
+
 # ---- 2. the step kernel against fp64, and against md_step's bits ---------------------------------------------------------------
 
 def _step_inputs(N, seed, n_mol=5):

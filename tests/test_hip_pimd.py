@@ -112,6 +112,35 @@ def test_pimd_step_against_fp64_on_the_same_inputs(P, flags, with_noise):
     assert max(worst.values()) <= 1.0
 
 
+@pytest.mark.parametrize('with_noise', [False, True])
+@pytest.mark.parametrize('flags', [pr.FINISH, pr.BEGIN, pr.FINISH | pr.BEGIN])
+@pytest.mark.parametrize('N', [1, 257])
+def test_one_bead_gives_md_step_bits(N, flags, with_noise):
+    """csrc/pimd.hip's head comment: with P = 1 (C = [1], a = 1, b = dth, d = 0) the chain is md_step_kernel's.  The products with 1
+    and fma(0, u, w) are exact, so u plays pos_in and every output carries nnhip_md_step's bits."""
+    from newtonnet_amd import hip
+    assert (pr.FINISH, pr.BEGIN) == (hip.MD_FINISH, hip.MD_BEGIN)
+    d = _synthetic(1, [N], 700 + N)
+    dth, c1 = np.float32(0.5 * 0.25 * 0.0982269), np.float32(np.exp(-0.01))
+    d['C'] = np.ones((1, 1), dtype=np.float32)
+    d['tab'] = np.array([[1.0, dth, 0.0, c1, 0.0]], dtype=np.float32)
+    t, pos_out, est_out = _launch(d, 1, flags, with_noise)
+    m = {k: torch.from_numpy(d[k]).cuda() for k in ('u', 'w', 'F', 'xi', 'm', 'hk', 'sigma')}
+    md_pos, md_ke = torch.full((N, 3), 777.0, device='cuda'), torch.full((N,), 777.0, device='cuda')
+    begin, finish = bool(flags & pr.BEGIN), bool(flags & pr.FINISH)
+    hip.md_step(m['u'] if begin else None, m['w'], m['F'], m['hk'], float(dth), float(c1), flags, pos_out=md_pos if begin else None,
+                mass=m['m'], sigma=m['sigma'] if with_noise else None, noise=m['xi'] if with_noise else None,
+                ke_out=md_ke if finish else None)
+
+    def same(name, got, want):
+        assert torch.equal(got.contiguous().view(torch.int32), want.view(torch.int32)), f'{name}: not the bits of nnhip_md_step'
+    same('w', t['w'], m['w'])
+    same('pos_out', pos_out, md_pos)                              # (both still the sentinel without begin)
+    same('u', t['u'], md_pos if begin else m['u'])
+    same('est_out[:, 0]', est_out[:, 0], md_ke)                   # (both still the sentinel without finish)
+    assert not torch.equal(m['w'], torch.from_numpy(d['w']).cuda())
+
+
 # ---- 2. what a launch may not touch ---------------------------------------------------------------------------------------------
 
 def test_what_a_launch_may_not_touch_and_refusals():
