@@ -1027,6 +1027,59 @@ int nnhip_lbfgs_step(const float* pos_in, const float* force, const uint8_t* fre
                      float* pos_out, float* fmax_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Intrinsic-reaction-coordinate following on the device (csrc/irc.hip): ONE launch on `stream` moves every path of a batch by one
+ * step of the damped velocity Verlet scheme (after Hratchian and Schlegel, J. Phys. Chem. A 106, 165 (2002)) from the forces just
+ * evaluated.  The path is a trajectory whose speed is reset to the constant v0 after every step: with a = c F / m
+ * (c = NNHIP_IRC_ACCEL: eV / (Angstrom amu) in Angstrom / fs^2, the square of dynamics.FS) it moves along M^-1 F, steepest descent in
+ * mass-weighted coordinates, on one gradient per step.  One wave64 works on one molecule, every reduction is a lane-local sum / max
+ * in atom order and a fixed butterfly: no float atomics, a molecule's outputs are bitwise independent of the rest of the batch and
+ * of its place in it.  All arithmetic in fp32, every operation one rounding (tests/irc_ref.py restates it); the square roots and
+ * the cube root are taken as good to 2 ulp.
+ *
+ * State of molecule b (device arrays of the caller):
+ *   status[b] (sticky: 0 running, 1 minimum reached, 2 turned), armed[b] (sticky), n_steps[b]      int32 [B] each
+ *   dt[b] (fs, inside [dt_min, dt_max]), dt_prev[b], arc[b] (amu^1/2 Angstrom)                     fp32 [B] each
+ *   vel (Angstrom / fs; the caller's start velocity of norm v0 before the first step), x_prev, v_prev, a_prev      fp32 [N][3] each
+ * Per launch: pos_in = x_n, force = F_n [N,3]; free_mask uint8 [N] (0 = fixed atom) or NULL (all free); masses fp32 [N] (amu);
+ * mol_ptr int32 [B+1] atom offsets; v0 (Angstrom / fs); delta0 (Angstrom, the error target); dt_min, dt_max (fs); tol2 =
+ * fl32(fmax^2); flags; outputs pos_out = x_{n+1} [N,3] and fmax_out [B].  A fixed atom is in no sum and never moves; |.| is the
+ * Euclidean norm over the molecule's free atoms.
+ *
+ * One launch for molecule b:
+ *   1. f_i = F_i for free atoms and exactly 0 for fixed ones.  fmax2 = max_i |f_i|^2;  fmax_out[b] = sqrt(fmax2).  armed[b] is set
+ *      when fmax2 >= tol2 (only while status[b] == 0: a stopped molecule keeps every bit).
+ *   2. Stop tests, never with NNHIP_IRC_CHECK_ONLY and never for status[b] != 0:  when n_steps >= 1 and P = sum_i f_i.vel_i < 0
+ *      (vel: the damped velocity the previous launch stored -- the last step passed the minimum along the path): status = 2;
+ *      otherwise, when armed[b] and fmax2 < tol2: status = 1.  (The force AT a saddle is below the threshold too: it counts only
+ *      once the path has left that region.)
+ *   3. Frozen when status[b] != 0 (before or now), when the molecule has no atoms, or with NNHIP_IRC_CHECK_ONLY:  pos_out = pos_in
+ *      bitwise and no other state word is touched.
+ *   4. Otherwise  a_n = (c f) / m,  and when n_steps >= 1:  v = fma(0.5 (a_prev + a_n), dt_prev, vel), then v = v (v0 / |v|) -- but
+ *      with |v| == 0 nothing divides and v = vel as stored.  n_steps == 0:  v = vel.
+ *   5. x_{n+1} = fma(a_n, (0.5 dt) dt, fma(v, dt, x_n)).
+ *   6. arc[b] += sqrt(sum_i m_i |x_{n+1,i} - x_{n,i}|^2), the differences in fp32 on the stored values (a lane adds an atom by
+ *      fma(m_i, |d_i|^2, acc)).
+ *   7. When n_steps >= 1, with T = dt_prev + dt:  x' = fma(a_prev, (0.5 T) T, fma(v_prev, T, x_prev)),  Delta = |x_{n+1} - x'|,
+ *      dt_next = dt cbrt(delta0 / Delta) clamped into [dt / 2, 2 dt] and then into [dt_min, dt_max].  Delta == 0 or n_steps == 0:
+ *      dt_next = dt.
+ *   8. x_prev = x_n, v_prev = vel = v, a_prev = a_n, dt_prev = dt, dt = dt_next, n_steps += 1.
+ * pos_out may NOT overlap pos_in (NNHIP_E_INVALID, nothing is launched), for the reason given at nnhip_md_step.  NULL mandatory
+ * pointers, unknown flag bits, v0, delta0 or dt_min that are not finite and > 0, dt_max < dt_min (or not finite) and tol2 < 0 are
+ * refused likewise.  n_mol == 0 is success without a launch.  A molecule whose state words are impossible (status outside 0 .. 2,
+ * n_steps < 0, dt outside [dt_min, dt_max] or NaN, atom offsets outside 0 .. n_atoms) is not touched and gets fmax_out = NaN; so
+ * does a molecule with a free atom whose mass is not finite and > 0 -- the masses live on the device, where a launch function that
+ * may not wait for it cannot read them; the driver refuses such masses when it is made.
+ * Forces are taken as finite: a NaN component is passed over by the max in fmax2 (fmaxf returns its other operand)
+ * and goes into the positions of its molecule, and of no other; the model's own input checks are the guard.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_IRC_CHECK_ONLY 1
+#define NNHIP_IRC_ACCEL 0.00964853322f
+int nnhip_irc_step(const float* pos_in, const float* force, const uint8_t* free_mask, const float* masses, const int32_t* mol_ptr,
+                   int32_t n_mol, int32_t n_atoms, float v0, float delta0, float dt_min, float dt_max, float tol2, int32_t flags,
+                   int32_t* status, int32_t* armed, int32_t* n_steps, float* dt, float* dt_prev, float* arc, float* vel,
+                   float* x_prev, float* v_prev, float* a_prev, float* pos_out, float* fmax_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Nudged elastic band on the device (csrc/neb.hip): ONE launch on `stream` moves every band of a batch by one FIRE step on its NEB
  * forces, from the forces and energies just evaluated.  Improved tangent (Henkelman and Jonsson 2000), one spring constant,
  * climbing image (Henkelman, Uberuaga and Jonsson 2000), FIRE as ase.optimize.FIRE states it (mass 1, one step length per band).

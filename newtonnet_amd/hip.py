@@ -839,6 +839,38 @@ def neb_step(pos_in: torch.Tensor, force: torch.Tensor, energy: torch.Tensor, fr
                                 _stream(dev)), 'nnhip_neb_step')
 
 
+IRC_CHECK_ONLY = _K['NNHIP_IRC_CHECK_ONLY']                 # flag of nnhip_irc_step
+IRC_ACCEL = 0.00964853322        # eV / (Angstrom amu) in Angstrom / fs^2: NNHIP_IRC_ACCEL (include/newtonnet_hip.h), dynamics.FS^2
+
+
+def irc_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.Tensor], masses: torch.Tensor, mol_ptr: torch.Tensor,
+             v0: float, delta0: float, dt_min: float, dt_max: float, tol2: float, flags: int, status: torch.Tensor,
+             armed: torch.Tensor, n_steps: torch.Tensor, dt: torch.Tensor, dt_prev: torch.Tensor, arc: torch.Tensor,
+             vel: torch.Tensor, x_prev: torch.Tensor, v_prev: torch.Tensor, a_prev: torch.Tensor, pos_out: torch.Tensor,
+             fmax_out: torch.Tensor):
+    """One launch of the reaction-path step (nnhip_irc_step, csrc/irc.hip; the contract is in include/newtonnet_hip.h) on the
+    current stream, for the B molecules mol_ptr (int32 [B+1]) delimits.  pos_in, force [N,3] and masses [N] are read; free: bool /
+    uint8 [N] (False = fixed atom) or None; the state (status, armed, n_steps int32 [B]; dt, dt_prev, arc fp32 [B]; vel, x_prev,
+    v_prev, a_prev fp32 [N,3]) is updated in place, pos_out [N,3] and fmax_out [B] are written: all of these must be contiguous
+    tensors of exactly that type (a copy would take the result away).  pos_out may not overlap pos_in."""
+    B, dev, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, torch.int32
+    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
+        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
+    N = pos_out.shape[0]
+    _written(dev, status=(status, B, i32), armed=(armed, B, i32), n_steps=(n_steps, B, i32), dt=(dt, B), dt_prev=(dt_prev, B),
+             arc=(arc, B), vel=(vel, 3 * N), x_prev=(x_prev, 3 * N), v_prev=(v_prev, 3 * N), a_prev=(a_prev, 3 * N),
+             pos_out=(pos_out, 3 * N), fmax_out=(fmax_out, B))
+    if free is not None:
+        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
+            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
+        free = free.contiguous()
+    pos_in, force, masses = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), masses=(masses, N))
+    _check(lib().nnhip_irc_step(_ptr(pos_in), _ptr(force), _ptr(free), _ptr(masses), _ptr(mol_ptr), B, N, float(v0), float(delta0),
+                                float(dt_min), float(dt_max), float(tol2), int(flags), _ptr(status), _ptr(armed), _ptr(n_steps),
+                                _ptr(dt), _ptr(dt_prev), _ptr(arc), _ptr(vel), _ptr(x_prev), _ptr(v_prev), _ptr(a_prev),
+                                _ptr(pos_out), _ptr(fmax_out), _stream(dev)), 'nnhip_irc_step')
+
+
 REMD_MAX_REPLICAS = _K['NNHIP_REMD_MAX_REPLICAS']
 
 

@@ -861,6 +861,21 @@ class NewtonNet(nn.Module):
         return _n.Band(self, z, pos, cell, batch, n_images, spring=spring, fmax=fmax, climb=climb, climb_below=climb_below,
                        fixed=fixed, dt=dt, dt_max=dt_max, maxstep=maxstep)
 
+    def reaction_path(self, z, pos, cell, batch, direction=None, masses=None, both=True, speed=0.02, error_target=1.5e-3,
+                      timestep=0.25, timestep_min=0.01, timestep_max=2.0, initial_displacement=0.1, fmax=0.01, fixed=None):
+        """Intrinsic-reaction-coordinate following from the saddles `pos` of every molecule of the batch on the device: a
+        newtonnet_amd.irc.ReactionPath whose run(max_steps, check_every, record_every) steps every path together, one force
+        evaluation and one launch (csrc/irc.hip) per step.  Damped velocity Verlet (Hratchian & Schlegel 2002): the paths move at
+        the constant `speed` (Angstrom / fs) along M^-1 F, each with its own time step (fs) steered by `error_target` (Angstrom).
+        direction: fp32 [N,3] Cartesian, or None for each molecule's lowest normal mode (normal_modes is called; a molecule without
+        an imaginary mode is refused); both=True follows both branches (path 2b forward, 2b + 1 backward).  A path starts
+        initial_displacement (amu^1/2 Angstrom) from its saddle and stops below fmax (eV / Angstrom) or where the force turns
+        against it.  fixed: bool [N], atoms that never move.  Eval mode only; needs the 'energy' and 'gradient_force' heads."""
+        from newtonnet_amd import irc as _i
+        return _i.ReactionPath(self, z, pos, cell, batch, direction=direction, masses=masses, both=both, speed=speed,
+                               error_target=error_target, timestep=timestep, timestep_min=timestep_min, timestep_max=timestep_max,
+                               initial_displacement=initial_displacement, fmax=fmax, fixed=fixed)
+
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated
         (trainer.py:301-313): newtonnet_amd/train_fused.py, no torch autograd graph inside the step."""

@@ -560,6 +560,70 @@ class MLAseCalculator(_Base):
             out = {k: v[0] for k, v in out.items()}
         return out
 
+    def irc(self, atoms_or_list, direction=None, max_steps: int = 1000, speed: float = 0.02, error_target: float = 1.5e-3,
+            timestep: float = 0.25, timestep_min: float = 0.01, timestep_max: float = 2.0, initial_displacement: float = 0.1,
+            fmax: float = 0.01, check_every: int = 10, record_every: int = 1, fixed=None):
+        """Follow the intrinsic reaction coordinate from one saddle geometry or a list of equally sized ones down both sides, all
+        paths stepped together on the device (NewtonNet.reaction_path: damped velocity Verlet, one force evaluation and one launch
+        per step), until every path has stopped or max_steps steps have been taken.  direction: array [n_atoms, 3] (one structure)
+        or [n_frames, n_atoms, 3], or None for the lowest normal mode of every structure (a structure without an imaginary mode
+        is refused).  fixed: bool array [n_atoms], the same atoms held in every structure.  Returns a dict; per structure
+        `images` is the stitched path as a list of copies of its Atoms -- the backward branch reversed, the saddle, the forward
+        branch, every record_every-th step (0: the end points alone) -- with info['energy'] (eV) and info['arc_length']
+        (amu^1/2 Angstrom, negative on the backward branch) set; `arc`, `energy` [K] and `positions` [K, n_atoms, 3] hold the same
+        as numpy arrays; status, n_steps, fmax, arc_length [n_frames, 2] describe the forward and the backward branch.  One
+        structure drops the frame axis.  The Atoms objects passed in are not modified."""
+        import copy
+        from newtonnet_amd import irc as _i
+        from newtonnet_amd import relax as _r
+        single = _is_single(atoms_or_list)
+        atoms = [atoms_or_list] if single else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('irc: at least one structure expected')
+        n_frames, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('irc: frames of different sizes cannot share one array; use model.reaction_path (packed per molecule)')
+        _i.check_arguments(speed, error_target, timestep, timestep_min, timestep_max, initial_displacement, fmax)
+        _r.check_run_arguments(max_steps, check_every, record_every)
+        if fixed is not None:
+            fixed = np.asarray(fixed)
+            if fixed.dtype != np.bool_ or fixed.shape != (n_atoms,):
+                raise ValueError(f'fixed: a bool array [{n_atoms}] expected')
+        if direction is not None:
+            direction = np.asarray(direction, dtype=np.float32)
+            if direction.shape not in ((n_frames, n_atoms, 3),) + (((n_atoms, 3),) if n_frames == 1 else ()):
+                raise ValueError(f'direction: an array [{n_frames}, {n_atoms}, 3] expected (got {direction.shape})')
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd reaction paths run on an MI355X (ROCm) device only: make the calculator with '
+                               'device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        held = None if fixed is None else torch.from_numpy(np.tile(fixed, n_frames)).to(pos.device)
+        along = None if direction is None else torch.from_numpy(direction.reshape(-1, 3).copy()).to(pos.device)
+        path = self.model.reaction_path(z, pos.float(), cell.float(), batch, direction=along, both=True, speed=speed,
+                                        error_target=error_target, timestep=timestep, timestep_min=timestep_min,
+                                        timestep_max=timestep_max, initial_displacement=initial_displacement, fmax=fmax, fixed=held)
+        res = path.run(int(max_steps), int(check_every), int(record_every))
+        out = dict(images=[], arc=[], energy=[], positions=[])
+        for b, a in enumerate(atoms):
+            arc, energy, xyz = (t.cpu().numpy() for t in res.profile(b))
+            images = []
+            for k in range(len(arc)):
+                image = copy.deepcopy(a)
+                if hasattr(image, 'set_positions'):
+                    image.set_positions(xyz[k].astype(np.float64))
+                else:
+                    image.positions = xyz[k].astype(np.float64)
+                if not isinstance(getattr(image, 'info', None), dict):
+                    image.info = {}
+                image.info['energy'], image.info['arc_length'] = float(energy[k]), float(arc[k])
+                images.append(image)
+            out['images'].append(images), out['arc'].append(arc), out['energy'].append(energy), out['positions'].append(xyz)
+        for k, t in (('status', res.status), ('n_steps', res.n_steps), ('fmax', res.fmax), ('arc_length', res.arc_length)):
+            out[k] = t.cpu().numpy().reshape(n_frames, 2)
+        if single:
+            out = {k: v[0] for k, v in out.items()}
+        return out
+
     # ------------------------------------------------------------------ MD-loop latency path (SURVEY 8f rank 2)
     def _calculate_md(self, atoms):
         """One structure per call, called thousands of times by an MD driver (simulate.py:21-30): keep everything that does
