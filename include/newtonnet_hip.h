@@ -1080,6 +1080,101 @@ int nnhip_irc_step(const float* pos_in, const float* force, const uint8_t* free_
                    float* x_prev, float* v_prev, float* a_prev, float* pos_out, float* fmax_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Dimer-method saddle search on the device (csrc/dimer.hip): ONE launch on `stream` advances the dimer of every molecule of a batch
+ * by one move, from the forces just evaluated at each molecule's PROBE geometry.  Min-mode following after Henkelman and Jonsson
+ * (1999) with the one-evaluation rotations of Heyden, Bell and Keil (2005) and Kaestner and Sherwood (2008): conjugate-gradient
+ * rotation directions, the rotated endpoint's force interpolated, an L-BFGS translation (nnhip_lbfgs_step's recursion, one text:
+ * csrc/lbfgs_chain.h).  A molecule's probe is its dimer's centre (phase 0), the endpoint centre + delta N (phase 1) or a trial
+ * endpoint (phase 2), so a step of a batch is always one force evaluation of B geometries and the centre's force F0 is never
+ * evaluated twice.  One wave64 works on one molecule, every reduction is a lane-local sum / max in atom order and a fixed
+ * butterfly: no float atomics, a molecule's outputs are bitwise independent of the rest of the batch and of its place in it.  All
+ * arithmetic in fp32, every operation one rounding, and only sums, products, quotients and square roots: no atan, sin or cos
+ * (tests/dimer_ref.py restates the chain).
+ *
+ * State of molecule b (device arrays of the caller, zero before the first launch except the row MODE):
+ *   istate  int32 [NNHIP_DIMER_N_INT][B]: rows STATUS (0 running, 1 converged, sticky), PHASE (0 centre, 1 endpoint, 2 trial), STEPS
+ *           (translations), EVALS, ROT (rotations of this cycle), ROT_TOTAL, PAIRS, HEAD (the L-BFGS ring, as nnhip_lbfgs_step),
+ *           PENDING (1: slot HEAD and F_PREV hold the pending pair of a translation made with C < 0)
+ *   fstate  fp32 [NNHIP_DIMER_N_FLOAT][B]: rows CURVATURE C (eV / Angstrom^2), SLOPE b1, C2 and S2 (cosine and sine of twice the trial
+ *           angle), DNORM (the norm of the rotation direction before it was normalised)
+ *   vstate  fp32 [NNHIP_DIMER_N_VEC][N][3]: rows CENTER, MODE (N: a unit vector per molecule, zero on fixed atoms -- the caller's
+ *           start direction), F0, F1 (forces at the centre and at the endpoint), THETA (the unit rotation direction), THETA_ROT
+ *           (THETA carried into the rotated plane), G_OLD, X_PREV (the centre before the last translation), F_PREV
+ *   S, Y    fp32 [m][N][3], rho fp32 [B][m]: the translation's L-BFGS history, laid out as nnhip_lbfgs_step's
+ * Per launch: pos_in [N,3] the probes, force [N,3] and energy [B] (may be NULL) the model's results there; free_mask uint8 [N]
+ * (0 = fixed atom) or NULL; mol_ptr int32 [B+1]; delta (Angstrom, the dimer's half length); rot_tol = tan(2 x the rotation
+ * tolerance); max_rotations; tol2 = fl32(fmax^2); alpha, maxstep as nnhip_lbfgs_step; work [N,3] scratch when n_atoms > 64; outputs
+ * pos_out [N,3] (the next probes), fmax_out [B] and energy_out [B] (may be NULL): the largest force norm and the energy at the
+ * centre, written by every launch whose probe IS the centre (phase 0) and by no other.  A fixed atom has f = 0, reads as 0 in
+ * every state vector, is in no sum and never moves.  sum(a, b) is the sum of a_i . b_i over the molecule's atoms.
+ *
+ * One launch for molecule b.  Frozen when STATUS != 0, when the molecule has no atoms, or with NNHIP_DIMER_CHECK_ONLY: pos_out =
+ * pos_in bitwise and no state word is touched.  Otherwise EVALS += 1 and, by PHASE:
+ *   0  F0 = f (the first launch also sets CENTER = pos_in).  When STEPS >= 1, max_i |f_i|^2 < tol2 and C < 0: STATUS = 1, pos_out =
+ *      pos_in.  Otherwise pos_out = CENTER + delta N, PHASE = 1, ROT = 0.
+ *   1  F1 = f; then ASSESS.
+ *   2  (f is the force at CENTER + delta N*, N* = c1 N + s1 THETA with c1 = sqrt((1 + C2) / 2), s1 = S2 / (2 c1), formed as the
+ *      launch before formed them.)  C* = sum(F0 - f, N*) / delta;  a1 = (C - C* + b1 S2) / (1 - C2);  the angle phi that minimises the
+ *      fitted curvature a0 / 2 + a1 cos 2 phi + b1 sin 2 phi has (cos 2 phi, sin 2 phi) = -(a1, b1) / sqrt(a1^2 + b1^2) (phi = 0 when
+ *      that root is 0 or not finite);  cos phi = sqrt((1 + cos 2 phi) / 2), sin phi = sign(sin 2 phi) sqrt((1 - cos 2 phi) / 2)
+ *      -- of these two roots the one that does not cancel is taken and the other formed from sin 2 phi = 2 sin phi cos phi, and
+ *      1 - C2 is formed as 2 s1^2;
+ *      F1 = [(s1 cos phi - c1 sin phi) / s1] F1 + [sin phi / s1] f + [1 - cos phi - sin phi s1 / (1 + c1)] F0;
+ *      THETA_ROT = -sin phi N + cos phi THETA;  N = (cos phi N + sin phi THETA) / |...|;  ROT += 1, ROT_TOTAL += 1; then ASSESS.
+ *   ASSESS     g = F1 - F0;  C = -sum(g, N) / delta;  G = g - sum(g, N) N.  Direction D: after phase 1, D = G; after phase 2,
+ *              beta = max(0, sum(G, G - G_OLD) / sum(G_OLD, G_OLD)) (0 when the divisor is 0), D = G + beta DNORM THETA_ROT,
+ *              D -= sum(D, N) N, and D = G unless sum(D, G) > 0.  DNORM = |D|;  THETA = D / DNORM;  b1 = -sum(g, THETA) / delta;
+ *              r = -b1 / |C|;  C2 = 1 / sqrt(1 + r^2), S2 = r C2 (C == 0, or 1 + r^2 not finite: C2 = 0, S2 = 1, r = +inf).
+ *              The rotation is done when DNORM == 0, r < rot_tol or ROT >= max_rotations: TRANSLATE.  Otherwise G_OLD = G,
+ *              pos_out = CENTER + delta N*, PHASE = 2.
+ *   TRANSLATE  p = sum(F0, N);  F+ = F0 - 2 p N when C < 0, else -p N.  One step of nnhip_lbfgs_step's recursion on (CENTER, F+):
+ *              its pending pair and acceptance rule, H0 = 1 / alpha, the maxstep cap.  The history holds pairs of translations
+ *              made with C < 0 alone: with C >= 0 the step is the plain F+ / alpha (capped), PAIRS = 0 and PENDING = 0 -- -p N is
+ *              no gradient, it turns with N, and a pair formed from it describes that rotation and not the surface; with C < 0
+ *              the pending pair is completed only when PENDING is set, and PENDING = 1 afterwards.
+ *              X_PREV = CENTER;  CENTER = pos_out = the new centre;  F_PREV = F+;  STEPS += 1;  PHASE = 0.
+ * pos_out may NOT overlap pos_in (NNHIP_E_INVALID, nothing is launched), for the reason given at nnhip_md_step.  NULL mandatory
+ * pointers, memory outside 1 .. NNHIP_LBFGS_MAX_MEMORY, unknown flag bits, delta, rot_tol, alpha or maxstep that are not finite and
+ * > 0, tol2 < 0 (or NaN) and max_rotations < 0 are refused likewise.  n_mol == 0 is success without a launch.  A molecule whose
+ * state words are impossible (STATUS outside 0 .. 1, PHASE outside 0 .. 2, a negative count, HEAD outside 0 .. m-1, PAIRS outside
+ * 0 .. m, PENDING outside 0 .. 1, EVALS == 0 with PHASE != 0, a C that is not finite once STEPS >= 1 or PHASE == 2, atom offsets outside 0 .. n_atoms) is
+ * not touched and gets fmax_out = NaN.
+ * Cost: a translate launch walks the history (about 2 m ceil(n / 64) dependent sweeps of one wave), a rotate launch about ten
+ * sweeps -- a kernel for batches of molecules.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_DIMER_CHECK_ONLY 1
+#define NNHIP_DIMER_N_INT 9
+#define NNHIP_DIMER_I_STATUS 0
+#define NNHIP_DIMER_I_PHASE 1
+#define NNHIP_DIMER_I_STEPS 2
+#define NNHIP_DIMER_I_EVALS 3
+#define NNHIP_DIMER_I_ROT 4
+#define NNHIP_DIMER_I_ROT_TOTAL 5
+#define NNHIP_DIMER_I_PAIRS 6
+#define NNHIP_DIMER_I_HEAD 7
+#define NNHIP_DIMER_I_PENDING 8
+#define NNHIP_DIMER_N_FLOAT 5
+#define NNHIP_DIMER_F_CURVATURE 0
+#define NNHIP_DIMER_F_SLOPE 1
+#define NNHIP_DIMER_F_C2 2
+#define NNHIP_DIMER_F_S2 3
+#define NNHIP_DIMER_F_DNORM 4
+#define NNHIP_DIMER_N_VEC 9
+#define NNHIP_DIMER_V_CENTER 0
+#define NNHIP_DIMER_V_MODE 1
+#define NNHIP_DIMER_V_F0 2
+#define NNHIP_DIMER_V_F1 3
+#define NNHIP_DIMER_V_THETA 4
+#define NNHIP_DIMER_V_THETA_ROT 5
+#define NNHIP_DIMER_V_G_OLD 6
+#define NNHIP_DIMER_V_X_PREV 7
+#define NNHIP_DIMER_V_F_PREV 8
+int nnhip_dimer_step(const float* pos_in, const float* force, const float* energy, const uint8_t* free_mask, const int32_t* mol_ptr,
+                     int32_t n_mol, int32_t n_atoms, int32_t memory, float delta, float rot_tol, int32_t max_rotations, float tol2,
+                     float alpha, float maxstep, int32_t flags, int32_t* istate, float* fstate, float* vstate, float* S, float* Y,
+                     float* rho, float* work, float* pos_out, float* fmax_out, float* energy_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Nudged elastic band on the device (csrc/neb.hip): ONE launch on `stream` moves every band of a batch by one FIRE step on its NEB
  * forces, from the forces and energies just evaluated.  Improved tangent (Henkelman and Jonsson 2000), one spring constant,
  * climbing image (Henkelman, Uberuaga and Jonsson 2000), FIRE as ase.optimize.FIRE states it (mass 1, one step length per band).

@@ -1,0 +1,245 @@
+// The per-molecule L-BFGS step of the optimiser kernels (gfx950, fp32): the one definition that lbfgs_step_kernel (relax.hip, for
+// nnhip_lbfgs_step: minima, on the model's forces) and dimer_step_kernel (dimer.hip, for nnhip_dimer_step: the translation of a
+// dimer, on the forces with their component along the lowest mode inverted) share, so that "nnhip_lbfgs_step's recursion" is a
+// property of the text and not of two texts that agree.
+//
+// One wave64 works on one molecule [a0, a1).  Lane l owns the atoms l, l + 64, ... in EVERY sweep, so a lane only ever re-reads
+// what it wrote itself: no barrier, no LDS.  Every per-molecule reduction is a lane-local sum (or max) in atom order, then the fixed
+// butterfly __shfl_xor 32, 16, ..., 1 -- a + b and b + a round alike, so all 64 lanes hold the same bits afterwards and every
+// decision is uniform over the wave.  Every multiply-add is an explicit __fmaf_rn and every lone product / sum / quotient an
+// explicit __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn (tests/relax_ref.py restates the chain in fp64, one 2^-24 per operation):
+//   pair     y_i = f_prev_i - f_i;  ys = sum_l dot3(y_i, s_i), yy = sum_l dot3(y_i, y_i), ss = sum_l dot3(s_i, s_i)   (s = S[head])
+//            accept iff ys > 0 and ys ys > (c c) (yy ss)   (c = NNHIP_LBFGS_CURVATURE_MIN; each product one rounding);  rho = 1 / ys
+//            (rejected with all m slots taken: the pending s had replaced the oldest pair's, so that pair is gone: n_pairs = m - 1)
+//   loop 1   q = -f;  newest pair first:  a = rho (sum_l dot3(s_i, q_i));  q = fma(-a, y, q)
+//            z = q / alpha
+//   loop 2   oldest pair first:  c = a - rho (sum_l dot3(y_i, z_i));  z = fma(c, s, z)
+//   step     l2 = max_i dot3(z_i, z_i);  longest = sqrt(l2);  if longest >= maxstep:  z = z (maxstep / longest)
+//            x_out = x + (-z)  (a fixed atom: x itself);  S[head] = x_out - x;  f_prev = f
+//
+// The caller's side of a step is a policy object P:
+//   void force(int i, float* f) const          the force of atom i the optimiser sees, exactly 0 for a fixed atom
+//   bool is_free(int i) const
+//   void load_x(size_t o, float* x) const      the point the step leaves from (o = 3 i)
+//   void store_x(size_t o, const float* x_out, const float* x) const     where the new point goes
+#pragma once
+#include "common.h"
+
+namespace lbfgs_chain {
+
+struct History {
+  float* S;        // [m][N][3]
+  float* Y;        // [m][N][3]
+  float* rho;      // [B][m]
+  float* f_prev;   // [N][3]
+  float* work;     // [N][3]: the two-loop vector of molecules above 64 atoms
+  float alpha, maxstep;
+  int memory, n_atoms;
+};
+
+__device__ __forceinline__ float dot3(const float* a, const float* b) {
+  return __fmaf_rn(a[2], b[2], __fmaf_rn(a[1], b[1], __fmul_rn(a[0], b[0])));
+}
+
+__device__ __forceinline__ float wave_sum(float s) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s = __fadd_rn(s, __shfl_xor(s, d, 64));
+  return s;
+}
+
+__device__ __forceinline__ float wave_max(float s) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s = fmaxf(s, __shfl_xor(s, d, 64));
+  return s;
+}
+
+__device__ __forceinline__ void load3(const float* p, size_t o, float* v) {
+  v[0] = p[o];
+  v[1] = p[o + 1];
+  v[2] = p[o + 2];
+}
+
+__device__ __forceinline__ void store3(float* p, size_t o, const float* v) {
+  p[o] = v[0];
+  p[o + 1] = v[1];
+  p[o + 2] = v[2];
+}
+
+// the two-loop work vector of one lane: its single atom's three values in registers (REG: molecules of up to 64 atoms), or the
+// lane's own rows of History::work
+template <bool REG>
+struct Work {
+  float r[3];
+  float* w;
+  __device__ __forceinline__ void get(size_t o, float* v) const {
+    if (REG) {
+      v[0] = r[0], v[1] = r[1], v[2] = r[2];
+    } else {
+      load3(w, o, v);
+    }
+  }
+  __device__ __forceinline__ void put(size_t o, const float* v) {
+    if (REG) {
+      r[0] = v[0], r[1] = v[1], r[2] = v[2];
+    } else {
+      store3(w, o, v);
+    }
+  }
+};
+
+// the pending pair of a molecule that has stepped before: s is in slot `head`, y = f_prev - f.  np, head: the state before, and on
+// return after, the pair.  fresh_slot (-1: none) is the slot whose rho this launch has just formed: fresh_rho is that value in a
+// register of every lane (lane 0's store of it is not a thing the other lanes may read back)
+template <class P>
+__device__ __forceinline__ void pending_pair(const History& h, const P& p, int b, int a0, int a1, int lane, int& np, int& head,
+                                             int& fresh_slot, float& fresh_rho) {
+  const int m = h.memory;
+  const size_t slot_stride = 3 * (size_t)h.n_atoms;
+  const float* Sh = h.S + head * slot_stride;
+  float ys = 0.f, yy = 0.f, ss = 0.f;
+  for (int i = a0 + lane; i < a1; i += 64) {
+    float f[3], fp[3], s[3], y[3];
+    p.force(i, f);
+    load3(h.f_prev, 3 * (size_t)i, fp);
+    load3(Sh, 3 * (size_t)i, s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) y[k] = __fsub_rn(fp[k], f[k]);
+    ys = __fadd_rn(ys, dot3(y, s));
+    yy = __fadd_rn(yy, dot3(y, y));
+    ss = __fadd_rn(ss, dot3(s, s));
+  }
+  ys = wave_sum(ys);
+  yy = wave_sum(yy);
+  ss = wave_sum(ss);
+  const float c2 = __fmul_rn(NNHIP_LBFGS_CURVATURE_MIN, NNHIP_LBFGS_CURVATURE_MIN);
+  if (ys > 0.f && __fmul_rn(ys, ys) > __fmul_rn(c2, __fmul_rn(yy, ss))) {
+    float* Yh = h.Y + head * slot_stride;
+    for (int i = a0 + lane; i < a1; i += 64) {
+      float f[3], fp[3], y[3];
+      p.force(i, f);
+      load3(h.f_prev, 3 * (size_t)i, fp);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) y[k] = __fsub_rn(fp[k], f[k]);
+      store3(Yh, 3 * (size_t)i, y);
+    }
+    fresh_slot = head;
+    fresh_rho = __fdiv_rn(1.f, ys);
+    if (lane == 0) h.rho[(size_t)b * m + head] = fresh_rho;
+    np = np + 1 > m ? m : np + 1;
+    head = (head + 1) % m;
+  } else if (np == m) {
+    np = m - 1;                                    // a full ring: the rejected s had overwritten the oldest pair's
+  }
+}
+
+// the two-loop recursion, the clamp and the step of the molecule [a0, a1) of this wave; np, head: the state AFTER the pending pair
+template <bool REG, class P>
+__device__ void two_loop_and_step(const History& h, const P& p, int b, int a0, int a1, int lane, int np, int head, int fresh_slot,
+                                  float fresh_rho) {
+  const int m = h.memory;
+  const size_t slot_stride = 3 * (size_t)h.n_atoms;
+  const float* rho = h.rho + (size_t)b * m;
+  Work<REG> q;
+  q.w = h.work;
+  for (int i = a0 + lane; i < a1; i += 64) {
+    float f[3];
+    p.force(i, f);
+    const float v[3] = {-f[0], -f[1], -f[2]};
+    q.put(3 * (size_t)i, v);
+  }
+  float a_lane = 0.f;                                   // lane j: the coefficient a of the j-th newest pair
+  for (int j = 0; j < np; ++j) {
+    const int slot = (head - 1 - j + 2 * m) % m;
+    const float* Sj = h.S + slot * slot_stride;
+    const float* Yj = h.Y + slot * slot_stride;
+    float acc = 0.f;
+    for (int i = a0 + lane; i < a1; i += 64) {
+      float s[3], v[3];
+      load3(Sj, 3 * (size_t)i, s);
+      q.get(3 * (size_t)i, v);
+      acc = __fadd_rn(acc, dot3(s, v));
+    }
+    const float a = __fmul_rn(slot == fresh_slot ? fresh_rho : rho[slot], wave_sum(acc));
+    if (lane == j) a_lane = a;
+    for (int i = a0 + lane; i < a1; i += 64) {
+      float y[3], v[3];
+      load3(Yj, 3 * (size_t)i, y);
+      q.get(3 * (size_t)i, v);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[k] = __fmaf_rn(-a, y[k], v[k]);
+      q.put(3 * (size_t)i, v);
+    }
+  }
+  for (int i = a0 + lane; i < a1; i += 64) {
+    float v[3];
+    q.get(3 * (size_t)i, v);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = __fdiv_rn(v[k], h.alpha);
+    q.put(3 * (size_t)i, v);
+  }
+  for (int j = np - 1; j >= 0; --j) {
+    const int slot = (head - 1 - j + 2 * m) % m;
+    const float* Sj = h.S + slot * slot_stride;
+    const float* Yj = h.Y + slot * slot_stride;
+    float acc = 0.f;
+    for (int i = a0 + lane; i < a1; i += 64) {
+      float y[3], v[3];
+      load3(Yj, 3 * (size_t)i, y);
+      q.get(3 * (size_t)i, v);
+      acc = __fadd_rn(acc, dot3(y, v));
+    }
+    const float c = __fsub_rn(__shfl(a_lane, j, 64), __fmul_rn(slot == fresh_slot ? fresh_rho : rho[slot], wave_sum(acc)));
+    for (int i = a0 + lane; i < a1; i += 64) {
+      float s[3], v[3];
+      load3(Sj, 3 * (size_t)i, s);
+      q.get(3 * (size_t)i, v);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[k] = __fmaf_rn(c, s[k], v[k]);
+      q.put(3 * (size_t)i, v);
+    }
+  }
+  float l2 = 0.f;
+  for (int i = a0 + lane; i < a1; i += 64) {
+    float v[3];
+    q.get(3 * (size_t)i, v);
+    l2 = fmaxf(l2, dot3(v, v));
+  }
+  const float longest = __fsqrt_rn(wave_max(l2));
+  const bool clamp = longest >= h.maxstep;
+  const float scale = clamp ? __fdiv_rn(h.maxstep, longest) : 1.f;
+  float* Sh = h.S + head * slot_stride;
+  for (int i = a0 + lane; i < a1; i += 64) {
+    const size_t o = 3 * (size_t)i;
+    float v[3], x[3], f[3], xo[3], s[3];
+    q.get(o, v);
+    p.load_x(o, x);
+    p.force(i, f);
+    const bool is_free = p.is_free(i);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float z = clamp ? __fmul_rn(v[k], scale) : v[k];
+      xo[k] = is_free ? __fadd_rn(x[k], -z) : x[k];
+      s[k] = __fsub_rn(xo[k], x[k]);
+    }
+    p.store_x(o, xo, x);
+    store3(Sh, o, s);
+    store3(h.f_prev, o, f);
+  }
+}
+
+// one whole step: the pending pair when the molecule has stepped before (`stepped`), then the recursion and the step.  np, head:
+// the state words before; on return the ones to store
+template <class P>
+__device__ __forceinline__ void step(const History& h, const P& p, int b, int a0, int a1, int lane, bool stepped, int& np,
+                                     int& head) {
+  int fresh_slot = -1;
+  float fresh_rho = 0.f;
+  if (stepped) pending_pair(h, p, b, a0, a1, lane, np, head, fresh_slot, fresh_rho);
+  if (a1 - a0 <= 64) {
+    two_loop_and_step<true>(h, p, b, a0, a1, lane, np, head, fresh_slot, fresh_rho);
+  } else {
+    two_loop_and_step<false>(h, p, b, a0, a1, lane, np, head, fresh_slot, fresh_rho);
+  }
+}
+
+}  // namespace lbfgs_chain

@@ -871,6 +871,44 @@ def irc_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.Ten
                                 _ptr(pos_out), _ptr(fmax_out), _stream(dev)), 'nnhip_irc_step')
 
 
+DIMER_CHECK_ONLY = _K['NNHIP_DIMER_CHECK_ONLY']             # flag of nnhip_dimer_step
+# rows of its state blocks istate [DIMER_N_INT, B], fstate [DIMER_N_FLOAT, B] and vstate [DIMER_N_VEC, N, 3]
+DIMER_N_INT, DIMER_N_FLOAT, DIMER_N_VEC = _K['NNHIP_DIMER_N_INT'], _K['NNHIP_DIMER_N_FLOAT'], _K['NNHIP_DIMER_N_VEC']
+DIMER_I = {k[len('NNHIP_DIMER_I_'):].lower(): v for k, v in _K.items() if k.startswith('NNHIP_DIMER_I_')}
+DIMER_F = {k[len('NNHIP_DIMER_F_'):].lower(): v for k, v in _K.items() if k.startswith('NNHIP_DIMER_F_')}
+DIMER_V = {k[len('NNHIP_DIMER_V_'):].lower(): v for k, v in _K.items() if k.startswith('NNHIP_DIMER_V_')}
+
+
+def dimer_step(pos_in: torch.Tensor, force: torch.Tensor, energy: Optional[torch.Tensor], free: Optional[torch.Tensor],
+               mol_ptr: torch.Tensor, memory: int, delta: float, rot_tol: float, max_rotations: int, tol2: float, alpha: float,
+               maxstep: float, flags: int, istate: torch.Tensor, fstate: torch.Tensor, vstate: torch.Tensor, S: torch.Tensor,
+               Y: torch.Tensor, rho: torch.Tensor, work: Optional[torch.Tensor], pos_out: torch.Tensor, fmax_out: torch.Tensor,
+               energy_out: Optional[torch.Tensor] = None):
+    """One launch of the dimer-method step (nnhip_dimer_step, csrc/dimer.hip; the contract is in include/newtonnet_hip.h) on the
+    current stream, for the B molecules mol_ptr (int32 [B+1]) delimits.  pos_in (the probes), force [N,3] and energy [B] (or None)
+    are read; free: bool / uint8 [N] (False = fixed atom) or None; the state (istate int32 [DIMER_N_INT,B]; fstate fp32
+    [DIMER_N_FLOAT,B]; vstate fp32 [DIMER_N_VEC,N,3]; S, Y fp32 [memory,N,3]; rho fp32 [B,memory]) is updated in place, pos_out
+    [N,3] (the next probes), fmax_out [B] and energy_out [B] (or None) are written: all of these must be contiguous tensors of
+    exactly that type (a copy would take the result away).  work: fp32 [N,3] scratch, needed when N > 64.  pos_out may not overlap
+    pos_in."""
+    B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
+    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
+        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
+    N, rows = pos_out.shape[0], max(m, 0)
+    _written(dev, optional=('work', 'energy_out'), istate=(istate, DIMER_N_INT * B, i32), fstate=(fstate, DIMER_N_FLOAT * B),
+             vstate=(vstate, DIMER_N_VEC * N * 3), S=(S, rows * N * 3), Y=(Y, rows * N * 3), rho=(rho, B * rows), work=(work, 3 * N),
+             pos_out=(pos_out, 3 * N), fmax_out=(fmax_out, B), energy_out=(energy_out, B))
+    if free is not None:
+        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
+            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
+        free = free.contiguous()
+    pos_in, force, energy = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), energy=(energy, B))
+    _check(lib().nnhip_dimer_step(_ptr(pos_in), _ptr(force), _ptr(energy), _ptr(free), _ptr(mol_ptr), B, N, m, float(delta),
+                                  float(rot_tol), int(max_rotations), float(tol2), float(alpha), float(maxstep), int(flags),
+                                  _ptr(istate), _ptr(fstate), _ptr(vstate), _ptr(S), _ptr(Y), _ptr(rho), _ptr(work), _ptr(pos_out),
+                                  _ptr(fmax_out), _ptr(energy_out), _stream(dev)), 'nnhip_dimer_step')
+
+
 REMD_MAX_REPLICAS = _K['NNHIP_REMD_MAX_REPLICAS']
 
 

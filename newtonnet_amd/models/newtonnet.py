@@ -876,6 +876,23 @@ class NewtonNet(nn.Module):
                                error_target=error_target, timestep=timestep, timestep_min=timestep_min, timestep_max=timestep_max,
                                initial_displacement=initial_displacement, fmax=fmax, fixed=fixed)
 
+    def saddle_search(self, z, pos, cell, batch, direction=None, fmax=0.001, dimer_length=0.01, rotation_tolerance=5.0,
+                      max_rotations=8, memory=16, maxstep=0.2, alpha=70.0, fixed=None, solver='lds'):
+        """Dimer-method saddle search from the geometries `pos` of every molecule of the batch on the device: a
+        newtonnet_amd.dimer.SaddleSearch whose run(max_evaluations, check_every, record_every) steps every dimer together, one
+        force evaluation and one launch (csrc/dimer.hip) per step.  Gradients only: conjugate-gradient rotations of the dimer
+        towards the lowest mode at one evaluation each (Heyden et al. 2005, Kaestner & Sherwood 2008), L-BFGS translations on the
+        force with its component along the mode inverted.  direction: fp32 [N,3] Cartesian, normalised per molecule -- after a
+        band, BandResult.tangent at saddle_image -- or None for each molecule's lowest normal mode (normal_modes is called with
+        `solver`; the mode need not be imaginary).  fmax (eV / Angstrom): the convergence threshold on the largest atomic force at
+        the dimer's centre, with a negative curvature along the mode; dimer_length (Angstrom): centre to endpoint;
+        rotation_tolerance (degrees), max_rotations: when a rotation cycle ends; memory, maxstep, alpha: as for relaxation.
+        fixed: bool [N], atoms that never move.  Eval mode only; needs the 'energy' and 'gradient_force' heads."""
+        from newtonnet_amd import dimer as _d
+        return _d.SaddleSearch(self, z, pos, cell, batch, direction=direction, fmax=fmax, dimer_length=dimer_length,
+                               rotation_tolerance=rotation_tolerance, max_rotations=max_rotations, memory=memory, maxstep=maxstep,
+                               alpha=alpha, fixed=fixed, solver=solver)
+
     def _forward_train(self, z, pos, cell, batch, keys, energy_idx, displacement):
         """Train mode (create_graph=True): outputs stay attached to autograd so a force loss can be back-propagated
         (trainer.py:301-313): newtonnet_amd/train_fused.py, no torch autograd graph inside the step."""

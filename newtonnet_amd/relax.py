@@ -8,7 +8,8 @@ of a step capped at maxstep), every molecule with its own history and its own st
 stated in include/newtonnet_hip.h: a curvature pair enters the history only when y.s > 0 and cos(y, s) > 1e-4.
 
 A molecule that has converged is frozen -- later launches leave every bit of it alone -- but model() keeps evaluating it with the
-rest of the batch: compacting the batch is not done here.  Minima only: no saddles, no Hessian-based steps, no cell relaxation, no
+rest of the batch: compacting the batch is not done here.  Minima only (saddles: newtonnet_amd.dimer, which takes its translation
+from the same device code, csrc/lbfgs_chain.h): no Hessian-based steps, no cell relaxation, no
 constraint other than fixed atoms.  The launch gives one wave64 to a molecule, whatever its size: it is meant for batches of
 molecules, and one large system pays about 2 memory ceil(n / 64) dependent sweeps of a single wave per step.
 
@@ -57,6 +58,32 @@ def check_arguments(fmax, memory, maxstep, alpha):
     return fmax, int(memory), maxstep, alpha
 
 
+def check_inputs(model, who, z, pos, cell, batch, fixed):
+    """the model and the tensors of a driver named `who` (Relaxation, SaddleSearch), refused without touching the device; returns
+    (N, B)"""
+    if getattr(model, 'training', False):
+        raise ValueError(f'{who} needs the model in eval mode: call model.eval()')
+    props = list(getattr(model, 'output_properties', []))
+    if 'energy' not in props or 'gradient_force' not in props:
+        raise ValueError(f"{who} needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
+    for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
+    N = pos.shape[0]
+    if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
+        raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
+    B = cell.shape[0]
+    if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
+        raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
+    if pos.dtype != torch.float32 or cell.dtype != torch.float32:
+        raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
+    if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
+        raise ValueError(f'fixed: a bool tensor [{N}] expected')
+    return N, B
+
+
 def check_run_arguments(max_steps, check_every, record_every):
     for name, v in (('max_steps', max_steps), ('check_every', check_every), ('record_every', record_every)):
         if int(v) != v or v < 0:
@@ -77,26 +104,7 @@ class Relaxation:
 
     def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
         # ---- everything that can be refused without touching the device
-        if getattr(model, 'training', False):
-            raise ValueError('Relaxation needs the model in eval mode: call model.eval()')
-        props = list(getattr(model, 'output_properties', []))
-        if 'energy' not in props or 'gradient_force' not in props:
-            raise ValueError(f"Relaxation needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
-        for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
-        if pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
-        N = pos.shape[0]
-        if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
-            raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
-        B = cell.shape[0]
-        if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
-            raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
-        if pos.dtype != torch.float32 or cell.dtype != torch.float32:
-            raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
-        if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
-            raise ValueError(f'fixed: a bool tensor [{N}] expected')
+        N, B = check_inputs(model, 'Relaxation', z, pos, cell, batch, fixed)
         fmax, memory, maxstep, alpha = check_arguments(fmax, memory, maxstep, alpha)
         if not pos.is_cuda:
             raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: move the model and the inputs to '

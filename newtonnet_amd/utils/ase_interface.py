@@ -624,6 +624,56 @@ class MLAseCalculator(_Base):
             out = {k: v[0] for k, v in out.items()}
         return out
 
+    def find_saddle(self, atoms_or_list, direction=None, fmax: float = 0.001, max_evaluations: int = 1000,
+                    dimer_length: float = 0.01, rotation_tolerance: float = 5.0, max_rotations: int = 8, memory: int = 16,
+                    maxstep: float = 0.2, alpha: float = 70.0, check_every: int = 10, fixed=None, solver: str = 'lds'):
+        """Dimer-method saddle search from one guessed transition geometry or a list of equally sized ones, all stepped together
+        on the device (NewtonNet.saddle_search: gradients only, one force evaluation and one launch per step), until every
+        structure's largest atomic force is below fmax (eV / Angstrom) with a negative curvature along its mode, or
+        max_evaluations evaluations have been made.  direction: array [n_atoms, 3] (one structure) or [n_frames, n_atoms, 3], the
+        start direction of each dimer, or None for the lowest normal mode of every structure.  fixed: bool array [n_atoms], the
+        same atoms held in every structure.  Returns a dict of numpy arrays: positions, mode [n_frames, n_atoms, 3], energy, fmax,
+        curvature, converged, n_steps, n_evaluations, n_rotations [n_frames]; one structure drops the frame axis.  The Atoms objects
+        are not modified."""
+        from newtonnet_amd import dimer as _d
+        from newtonnet_amd.vibrations import _check_solver
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('find_saddle: at least one structure expected')
+        n_frames, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('find_saddle: frames of different sizes cannot share one array; use model.saddle_search (packed per '
+                             'molecule)')
+        _d.check_arguments(fmax, dimer_length, rotation_tolerance, max_rotations, memory, maxstep, alpha)
+        _d.check_run_arguments(max_evaluations, check_every, 0)
+        _check_solver(solver)
+        if fixed is not None:
+            fixed = np.asarray(fixed)
+            if fixed.dtype != np.bool_ or fixed.shape != (n_atoms,):
+                raise ValueError(f'fixed: a bool array [{n_atoms}] expected')
+        if direction is not None:
+            direction = np.asarray(direction, dtype=np.float32)
+            if direction.shape not in ((n_frames, n_atoms, 3),) + (((n_atoms, 3),) if n_frames == 1 else ()):
+                raise ValueError(f'direction: an array [{n_frames}, {n_atoms}, 3] expected (got {direction.shape})')
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd saddle searches run on an MI355X (ROCm) device only: make the calculator with '
+                               'device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        held = None if fixed is None else torch.from_numpy(np.tile(fixed, n_frames)).to(pos.device)
+        along = None if direction is None else torch.from_numpy(direction.reshape(-1, 3).copy()).to(pos.device)
+        search = self.model.saddle_search(z, pos.float(), cell.float(), batch, direction=along, fmax=fmax, dimer_length=dimer_length,
+                                          rotation_tolerance=rotation_tolerance, max_rotations=max_rotations, memory=memory,
+                                          maxstep=maxstep, alpha=alpha, fixed=held, solver=solver)
+        res = search.run(int(max_evaluations), int(check_every))
+        out = dict(positions=res.pos.cpu().numpy().reshape(n_frames, n_atoms, 3),
+                   mode=res.mode.cpu().numpy().reshape(n_frames, n_atoms, 3), energy=res.energy.cpu().numpy(),
+                   fmax=res.fmax.cpu().numpy(), curvature=res.curvature.cpu().numpy(), converged=res.converged.cpu().numpy(),
+                   n_steps=res.n_steps.cpu().numpy(), n_evaluations=res.n_evaluations.cpu().numpy(),
+                   n_rotations=res.n_rotations.cpu().numpy())
+        if n_frames == 1:
+            out = {k: v[0] for k, v in out.items()}
+        return out
+
     # ------------------------------------------------------------------ MD-loop latency path (SURVEY 8f rank 2)
     def _calculate_md(self, atoms):
         """One structure per call, called thousands of times by an MD driver (simulate.py:21-30): keep everything that does
