@@ -542,6 +542,47 @@ int nnhip_head_out(const float* e2, const float* w4, const float* b4, const floa
                    const int64_t* z, const int32_t* mol_ptr, int32_t n_atoms, int32_t n_mol, int32_t activation,
                    float* atom_energy, float* g_e2, float* energy, void* stream);
 
+/* The same stages with what nnhip_energy_forces hands its launchers besides the arrays above, so that every kernel form the
+ * pipeline runs can be called (and tested) on its own.  A NULL member / zero means "as the plain entry point":
+ *   pair_ptr [N + 1]  exclusive scan of the number of pairs a row owns (its upper edges, the last ones of the row): the rows
+ *                     take their split from it instead of a ballot over col
+ *   rev [E]           reverse edge: force_message_bwd then lets the pair's owner write g_u of both directions
+ *   mol_ptr [n_mol+1] molecule offsets: batches that pay (edge_kernels_from_molecules <= n_mol, 8 n_mol <= N <=
+ *                     NNHIP_MOL_STAGE_MAX n_mol, see nnhip_config "molecule_forms") take the molecule-resident kernels of
+ *                     message_bwd and force_message_fwd; no edge may join two molecules
+ *   small_molecules   edge_embed_bwd / head_out: the batch may take their molecule-resident kernels (mol_ptr / n_mol are
+ *                     arguments of those two entry points).  nnhip_edge_embed_bwd_ex refuses g_d == NULL where g_d is written:
+ *                     with a virial, and with more than 2^20 edges
+ *   tail_*            message_bwd with need_gm = 0 only: the molecule-resident kernel goes on with the geometry adjoint and writes
+ *                     tail_forces [N][3] from g_x (the head of a [tail_n_layers][tail_n_edges] array whose first row this
+ *                     launch writes), tail_g_u [L][E][4], tail_geo and rev, as nnhip_edge_embed_bwd would have.  *tail_done
+ *                     says whether it did (1) or the forces are still to be formed (0: another form served the launch). */
+typedef struct {
+  const int32_t* pair_ptr; const int32_t* rev; const int32_t* mol_ptr;
+  int32_t n_mol, small_molecules;
+  const float* tail_g_u; const float* tail_geo; float* tail_forces;
+  int32_t tail_n_edges, tail_n_layers;
+  float tail_cutoff; int32_t pad_;
+} nnhip_stage_opts;
+int nnhip_message_bwd_ex(const float* g_msg, const float* g_a, const float* m, const int32_t* xg, const float* table,
+                         const int32_t* row_ptr, const int32_t* col, const int32_t* pid, float* g_m, float* g_x,
+                         int32_t n_atoms, int32_t need_gm, const nnhip_stage_opts* opts, int32_t* tail_done, void* stream);
+int nnhip_force_message_fwd_ex(const float* phi1, const float* phi2, const float* geo, const int32_t* xg,
+                               const int32_t* row_ptr, const int32_t* col, const int32_t* pid, const float* f_in,
+                               float* f_out, int32_t n_atoms, const nnhip_stage_opts* opts, void* stream);
+int nnhip_force_message_bwd_ex(const float* gf, const float* phi1, const float* phi2, const float* geo, const int32_t* xg,
+                               const int32_t* row_ptr, const int32_t* col, const int32_t* pid, const float* f_in,
+                               float* g_h12, float* g_u, float* g_fin, int32_t n_atoms, const nnhip_stage_opts* opts,
+                               void* stream);
+int nnhip_edge_embed_bwd_ex(const float* g_x, const float* g_u, const float* geo, const float* disp, const float* pos,
+                            const float* cell, const int32_t* row_ptr, const int32_t* col, const int32_t* rev,
+                            const int32_t* mol_ptr, int32_t n_atoms, int32_t n_edges, int32_t n_mol, int32_t n_layers,
+                            float cutoff, float* g_d, float* forces, float* virial, const nnhip_stage_opts* opts,
+                            void* stream);
+int nnhip_head_out_ex(const float* e2, const float* w4, const float* b4, const float* scale, const float* shift,
+                      const int64_t* z, const int32_t* mol_ptr, int32_t n_atoms, int32_t n_mol, int32_t activation,
+                      float* atom_energy, float* g_e2, float* energy, const nnhip_stage_opts* opts, void* stream);
+
 /* Fused Linear -> act -> Linear with every option (nnhip_mlp128 is the plain subset):
  *   mode 0 FWD : H = X W1^T + b1 (stored);  Y = act(H) W2^T + b2
  *   mode 1 BWD : T = X W1^T;  Y (+)= (T act'(H)) W2^T

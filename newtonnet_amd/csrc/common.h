@@ -42,6 +42,14 @@ void nnhip_set_error(const char* fmt, ...);
     }                                                                                      \
   } while (0)
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
+// argument check of an exported entry point: the failed condition goes into the error string
+#define ARG_CHECK(cond, who)                                   \
+  do {                                                         \
+    if (!(cond)) {                                             \
+      nnhip_set_error("%s: bad arguments (%s)", who, #cond);   \
+      return NNHIP_E_INVALID;                                  \
+    }                                                          \
+  } while (0)
 
 // do a [n] and b [n] share an element (an output that may not alias an input, overlapping views included)
 inline bool overlap(const float* a, const float* b, size_t n) { return a < b + n && b < a + n; }

@@ -1168,6 +1168,71 @@ extern "C" int nnhip_edge_embed_bwd(const float* g_x, const float* g_u, const fl
   return launch_geometry_bwd(g_x, g_u, geo, disp, pos, cell, row_ptr, col, rev, mol_ptr, n_atoms, n_edges, n_mol, n_layers,
                              cutoff, g_d, forces, virial, (hipStream_t)stream);
 }
+// ---- the same stages with the pipeline's extra arguments (header: nnhip_stage_opts); the plain entry points above keep theirs ----
+extern "C" int nnhip_message_bwd_ex(const float* g_msg, const float* g_a, const float* m, const int32_t* xg, const float* table,
+                                    const int32_t* row_ptr, const int32_t* col, const int32_t* pid, float* g_m, float* g_x,
+                                    int32_t n_atoms, int32_t need_gm, const nnhip_stage_opts* opts, int32_t* tail_done,
+                                    void* stream) {
+  ARG_CHECK(opts && n_atoms >= 0 && opts->n_mol >= 0, "nnhip_message_bwd_ex");
+  const bool tail = opts->tail_forces != nullptr;
+  ARG_CHECK(!tail || (tail_done && !need_gm && opts->tail_g_u && opts->tail_geo && opts->rev && opts->mol_ptr && opts->pair_ptr &&
+                      opts->tail_n_edges >= 0 && opts->tail_n_layers >= 1 && opts->tail_n_layers <= NNHIP_MAX_LAYERS &&
+                      opts->tail_cutoff > 0.f && opts->n_mol > 0 && (long)n_atoms <= (long)opts->n_mol * NNHIP_MOL_STAGE_MAX),
+            "nnhip_message_bwd_ex");
+  if (tail_done) *tail_done = 0;
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(g_msg && g_a && m && xg && table && row_ptr && col && pid && g_x && (g_m || !need_gm), "nnhip_message_bwd_ex");
+  const MsgBwdForceTail ft = {opts->tail_g_u, opts->tail_geo, opts->rev, opts->tail_n_edges, opts->tail_n_layers,
+                              tail ? 1.0f / opts->tail_cutoff : 0.f, opts->tail_forces};
+  bool done = false;
+  const int rc = launch_msg_bwd(g_msg, g_a, m, xg, table, row_ptr, col, pid, g_m, g_x, n_atoms, need_gm != 0, (hipStream_t)stream,
+                                opts->pair_ptr, opts->mol_ptr, opts->n_mol, tail ? &ft : nullptr, tail ? &done : nullptr);
+  if (tail_done) *tail_done = done ? 1 : 0;
+  return rc;
+}
+extern "C" int nnhip_force_message_fwd_ex(const float* phi1, const float* phi2, const float* geo, const int32_t* xg,
+                                          const int32_t* row_ptr, const int32_t* col, const int32_t* pid, const float* f_in,
+                                          float* f_out, int32_t n_atoms, const nnhip_stage_opts* opts, void* stream) {
+  ARG_CHECK(opts && n_atoms >= 0 && opts->n_mol >= 0, "nnhip_force_message_fwd_ex");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(phi1 && geo && row_ptr && col && pid && f_out && (phi2 || !f_in), "nnhip_force_message_fwd_ex");
+  return launch_force_fwd(f_in != nullptr, phi1, phi2, geo, row_ptr, col, pid, f_in, f_out, n_atoms, xg, (hipStream_t)stream,
+                          opts->pair_ptr, opts->mol_ptr, opts->n_mol);
+}
+extern "C" int nnhip_force_message_bwd_ex(const float* gf, const float* phi1, const float* phi2, const float* geo,
+                                          const int32_t* xg, const int32_t* row_ptr, const int32_t* col, const int32_t* pid,
+                                          const float* f_in, float* g_h12, float* g_u, float* g_fin, int32_t n_atoms,
+                                          const nnhip_stage_opts* opts, void* stream) {
+  ARG_CHECK(opts && n_atoms >= 0, "nnhip_force_message_bwd_ex");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(gf && phi1 && geo && row_ptr && col && pid && g_h12 && g_u && (!f_in || (phi2 && g_fin)), "nnhip_force_message_bwd_ex");
+  return launch_force_bwd(f_in != nullptr, gf, phi1, phi2, geo, row_ptr, col, pid, f_in, g_h12, g_u, g_fin, n_atoms, xg,
+                          (hipStream_t)stream, opts->pair_ptr, opts->rev);
+}
+extern "C" int nnhip_edge_embed_bwd_ex(const float* g_x, const float* g_u, const float* geo, const float* disp, const float* pos,
+                                       const float* cell, const int32_t* row_ptr, const int32_t* col, const int32_t* rev,
+                                       const int32_t* mol_ptr, int32_t n_atoms, int32_t n_edges, int32_t n_mol, int32_t n_layers,
+                                       float cutoff, float* g_d, float* forces, float* virial, const nnhip_stage_opts* opts,
+                                       void* stream) {
+  ARG_CHECK(opts && n_atoms >= 0 && n_edges >= 0 && n_mol >= 0 && n_layers >= 1 && n_layers <= NNHIP_MAX_LAYERS && cutoff > 0.f,
+            "nnhip_edge_embed_bwd_ex");
+  if (n_atoms == 0) return NNHIP_OK;
+  // (g_d: written by the two-launch path, which serves the virial and more than 2^20 edges -- launch_geometry_bwd, edge.hip)
+  ARG_CHECK(g_x && g_u && geo && row_ptr && rev && forces && (!opts->small_molecules || mol_ptr) &&
+                (g_d || (!virial && n_edges <= (1 << 20))) && (!virial || (disp && pos && cell && col && mol_ptr)),
+            "nnhip_edge_embed_bwd_ex");
+  return launch_geometry_bwd(g_x, g_u, geo, disp, pos, cell, row_ptr, col, rev, mol_ptr, n_atoms, n_edges, n_mol, n_layers,
+                             cutoff, g_d, forces, virial, (hipStream_t)stream, opts->small_molecules != 0);
+}
+extern "C" int nnhip_head_out_ex(const float* e2, const float* w4, const float* b4, const float* scale, const float* shift,
+                                 const int64_t* z, const int32_t* mol_ptr, int32_t n_atoms, int32_t n_mol, int32_t activation,
+                                 float* atom_energy, float* g_e2, float* energy, const nnhip_stage_opts* opts, void* stream) {
+  ARG_CHECK(opts && n_atoms >= 0 && n_mol >= 0 && activation >= NNHIP_ACT_SILU && activation <= NNHIP_ACT_SSP, "nnhip_head_out_ex");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(e2 && w4 && b4 && z && mol_ptr && atom_energy && energy, "nnhip_head_out_ex");
+  return launch_head_out(e2, w4, b4, scale, shift, z, mol_ptr, n_atoms, n_mol, activation, atom_energy, g_e2, energy,
+                         (hipStream_t)stream, opts->small_molecules != 0);
+}
 extern "C" int nnhip_node_fwd(const float* f, const float* a_mid, const float* Wu, float* q, float* a_out, const float* W0,
                               const float* b0, const float* W2, const float* b2, float* hn, float* m, int32_t n_atoms,
                               int32_t activation, void* stream) {

@@ -14,8 +14,9 @@
 //     the lower endpoint, no float atomics), reading values and tangents side by side;
 //   then every weight gradient is a sum of two products  dW = A1^T B1 + A2^T B2  over the rows (pairs or atoms):
 //     wgrad_kernel, a split-K fp32-MFMA reduction with deterministic slab + tree-free final sum.
-// tests/tangent_ref.py writes the same four sweeps in fp64 torch; tests/test_hip_train.py checks every stage against it and
-// the result against the oracle's autograd double backward.
+// tests/tangent_ref.py writes the same four sweeps in fp64 torch; tests/test_hip_train.py checks the stages chained on one
+// workspace against it (norm-wise) and the result against the oracle's autograd double backward; tests/test_hip_edge_stages.py calls
+// the edge and pair stages one by one on independent inputs and compares every element with tests/edge_ref.py.
 #include <string.h>
 
 #include "edge_common.h"
@@ -1388,13 +1389,6 @@ int launch_layer_norm_tan_bwd(const float* gy, float* dga, const float* xhat, co
 // =============================================================================================
 // C ABI (include/newtonnet_hip.h, "Training")
 // =============================================================================================
-#define ARG_CHECK(cond, who)                                   \
-  do {                                                         \
-    if (!(cond)) {                                             \
-      nnhip_set_error("%s: bad arguments (%s)", who, #cond);   \
-      return NNHIP_E_INVALID;                                  \
-    }                                                          \
-  } while (0)
 static inline int rows_grid(int n_atoms) { return cdiv(n_atoms, EDGE_ROWS); }
 
 extern "C" int nnhip_embed(const int64_t* z, const float* table, int32_t n_atoms, float* out, void* stream) {

@@ -151,3 +151,75 @@ def test_every_entry_point_is_declared_at_load():
         assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype is restype, name
     assert L.nnhip_spatial_order_scratch_bytes.restype is C.c_size_t and L.nnhip_bf16_mlp_launches.restype is C.c_int64
     assert L.nnhip_last_error.restype is C.c_char_p
+
+
+def test_stage_ex_entry_points_check_their_arguments():
+    """the *_ex stage entry points (nnhip_stage_opts) refuse bad arguments before any launch, in the ARG_CHECK style -- the failed
+    condition is in the error string -- and zero atoms is NNHIP_OK without a launch (no GPU is touched: the pointers are never
+    followed)"""
+    L = hip.lib()
+    OK, E_INVALID = 0, 1
+    p = 0x7f0000001000                        # stands for any device array
+    N, E = 99, 1502
+    Opts = abi.STRUCTS['nnhip_stage_opts']
+    assert abi.FUNCTIONS['nnhip_message_bwd_ex'][1][12] == C.POINTER(Opts) and C.sizeof(Opts) == 72
+
+    def opts(**kw):
+        o = Opts()
+        o.pair_ptr = o.rev = o.mol_ptr = p
+        o.n_mol, o.small_molecules = 7, 1
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+    def tail(**kw):
+        return opts(**dict(dict(tail_g_u=p, tail_geo=p, tail_forces=p, tail_n_edges=E, tail_n_layers=3, tail_cutoff=5.0), **kw))
+
+    def refused(rc, who, needle):
+        assert rc == E_INVALID, (who, rc)
+        msg = L.nnhip_last_error().decode()
+        assert msg.startswith(who + ': bad arguments (') and needle in msg, msg
+    done = C.c_int32(7)
+    msg_bwd = lambda n, need_gm, o, d: L.nnhip_message_bwd_ex(p, p, p, p, p, p, p, p, p, p, n, need_gm, o, d, None)  # noqa: E731
+    refused(msg_bwd(N, 0, None, None), 'nnhip_message_bwd_ex', 'opts')
+    refused(msg_bwd(-1, 0, C.byref(opts()), None), 'nnhip_message_bwd_ex', 'n_atoms >= 0')
+    refused(msg_bwd(N, 1, C.byref(tail()), C.byref(done)), 'nnhip_message_bwd_ex', '!need_gm')       # the force tail: layer 0 only,
+    refused(msg_bwd(N, 0, C.byref(tail()), None), 'nnhip_message_bwd_ex', 'tail_done')                # with somewhere to report,
+    for kw in (dict(rev=None), dict(mol_ptr=None), dict(pair_ptr=None), dict(tail_g_u=None), dict(tail_geo=None), dict(tail_cutoff=0.0),
+               dict(tail_n_layers=0), dict(tail_n_layers=abi.CONSTANTS['NNHIP_MAX_LAYERS'] + 1), dict(tail_n_edges=-1), dict(n_mol=0),
+               dict(n_mol=4), dict(n_mol=-1)):                                                         # everything the kernel reads,
+        refused(msg_bwd(N, 0, C.byref(tail(**kw)), C.byref(done)), 'nnhip_message_bwd_ex', 'opts')    # molecules of <= 24 atoms on average
+    assert done.value == 7                                   # (a refused call reports nothing)
+    assert msg_bwd(0, 0, C.byref(tail(n_mol=1)), C.byref(done)) == OK and done.value == 0
+    refused(L.nnhip_message_bwd_ex(p, p, p, p, p, p, p, p, None, p, N, 1, C.byref(opts()), None, None), 'nnhip_message_bwd_ex', 'g_m')
+    ffwd = lambda n, o, phi2=p, f_out=p: L.nnhip_force_message_fwd_ex(p, phi2, p, p, p, p, p, p, f_out, n, o, None)  # noqa: E731
+    refused(ffwd(N, None), 'nnhip_force_message_fwd_ex', 'opts')
+    refused(ffwd(N, C.byref(opts(n_mol=-1))), 'nnhip_force_message_fwd_ex', 'n_mol >= 0')
+    refused(ffwd(N, C.byref(opts()), phi2=None), 'nnhip_force_message_fwd_ex', 'phi2')               # f_in without phi2
+    refused(ffwd(N, C.byref(opts()), f_out=None), 'nnhip_force_message_fwd_ex', 'f_out')
+    assert ffwd(0, C.byref(opts())) == OK
+    fbwd = lambda n, o, g_fin=p, g_u=p: L.nnhip_force_message_bwd_ex(p, p, p, p, p, p, p, p, p, p, g_u, g_fin, n, o, None)  # noqa: E731
+    refused(fbwd(N, None), 'nnhip_force_message_bwd_ex', 'opts')
+    refused(fbwd(N, C.byref(opts()), g_fin=None), 'nnhip_force_message_bwd_ex', 'g_fin')              # f_in without g_fin
+    refused(fbwd(N, C.byref(opts()), g_u=None), 'nnhip_force_message_bwd_ex', 'g_u')
+    assert fbwd(0, C.byref(opts())) == OK
+    geom = lambda n, o, n_layers=3, cutoff=5.0, mol=p, rev=p, virial=None, g_d=p: L.nnhip_edge_embed_bwd_ex(  # noqa: E731
+        p, p, p, p, p, p, p, p, rev, mol, n, E, 7, n_layers, cutoff, g_d, p, virial, o, None)
+    refused(geom(N, None), 'nnhip_edge_embed_bwd_ex', 'opts')
+    refused(geom(N, C.byref(opts()), n_layers=0), 'nnhip_edge_embed_bwd_ex', 'n_layers >= 1')
+    refused(geom(N, C.byref(opts()), cutoff=0.0), 'nnhip_edge_embed_bwd_ex', 'cutoff > 0.f')
+    refused(geom(N, C.byref(opts()), mol=None), 'nnhip_edge_embed_bwd_ex', 'mol_ptr')                 # small_molecules without offsets
+    refused(geom(N, C.byref(opts()), rev=None), 'nnhip_edge_embed_bwd_ex', 'rev')
+    refused(geom(N, C.byref(opts()), virial=p, g_d=None), 'nnhip_edge_embed_bwd_ex', 'g_d')           # the virial is formed from g_d,
+    big = L.nnhip_edge_embed_bwd_ex(p, p, p, p, p, p, p, p, p, p, N, (1 << 20) + 1, 7, 3, 5.0, None, p, None, C.byref(opts()), None)
+    refused(big, 'nnhip_edge_embed_bwd_ex', 'g_d')                                                     # and so are the forces of > 2^20 edges
+    assert geom(0, C.byref(opts())) == OK
+    head = lambda n, o, act=0, mol=p, energy=p: L.nnhip_head_out_ex(p, p, p, None, None, p, mol, n, 7, act, p, None, energy, o, None)  # noqa: E731
+    refused(head(N, None), 'nnhip_head_out_ex', 'opts')
+    refused(head(N, C.byref(opts()), act=99), 'nnhip_head_out_ex', 'activation')
+    refused(head(N, C.byref(opts()), mol=None), 'nnhip_head_out_ex', 'mol_ptr')
+    refused(head(N, C.byref(opts()), energy=None), 'nnhip_head_out_ex', 'energy')
+    assert head(0, C.byref(opts())) == OK
+    # the plain entry points are what they were: zero atoms is NNHIP_OK
+    assert L.nnhip_message_bwd(p, p, p, p, p, p, p, p, p, p, 0, 1, None) == OK
+    assert L.nnhip_head_out(p, p, p, None, None, p, p, 0, 7, 0, p, None, p, None) == OK
