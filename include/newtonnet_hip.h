@@ -1068,6 +1068,59 @@ int nnhip_lbfgs_step(const float* pos_in, const float* force, const uint8_t* fre
                      float* pos_out, float* fmax_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Variable-cell geometry relaxation on the device (csrc/cellrelax.hip): ONE launch on `stream` moves the atoms and the cell of
+ * every periodic system of a batch by one L-BFGS step from the forces and the virial just evaluated.  The method is ASE's
+ * UnitCellFilter under nnhip_lbfgs_step's recursion (one text: csrc/lbfgs_chain.h).  Per system b with n atoms: h the cell (rows
+ * are lattice vectors), h0 the cell at the start, F the deformation gradient, q the reference-frame positions:
+ *   h = h0 F^T,   x = q F^T,   generalised coordinates X = [q ; c F]  (n + 3 rows of 3),   generalised forces G = [f F ; Wc / c]
+ *   Wc = (W - p V I) F^-T   with W the virial (minus the strain derivative of the energy, eV), V = det h, p = pressure[b] in
+ *   eV / Angstrom^3 and c = cell_factor[b]; G is minus the gradient of the enthalpy E + p V with respect to X.
+ * Launch shape and rounding discipline are nnhip_lbfgs_step's (one wave64 per system, fixed reductions, no float atomics, every
+ * operation one fp32 rounding; a system's bits do not depend on the rest of the batch).  tests/cellrelax_ref.py restates it.
+ *
+ * Row layout: x_in, x_out, G, g_prev, work and every slot of S and Y have R = n_atoms + 3 n_mol rows of 3; system b owns the rows
+ * [mol_ptr[b] + 3 b, mol_ptr[b+1] + 3 b + 3): its atom rows, then its three cell rows (c F, row by row).  Before the first step
+ * the caller fills x_in with q = pos and c I (F = I, cell_in = h0) and zeroes the state.
+ * State of system b (memory = m): converged, n_steps, n_pairs, head int32 [B]; S, Y fp32 [m][R][3]; rho fp32 [B][m]; g_prev fp32
+ * [R][3] (the generalised forces of the previous step) -- as nnhip_lbfgs_step's, over generalised rows.
+ * Per launch: x_in [R,3]; pos_in, force [N,3]; virial, cell_in, h0 [B,3,3]; free_mask uint8 [N] or NULL; mol_ptr int32 [B+1];
+ * pressure, cell_factor fp32 [B]; tol2 = fl32(fmax^2); alpha; maxstep; strain_mask: bit k frees the Voigt component k (xx, yy, zz,
+ * yz, xz, xy), 63 = all; flags; work [R,3] scratch (may be NULL when R <= 64).  Outputs: G [R,3] (written for the systems that
+ * step), x_out [R,3], pos_out [N,3], cell_out [B,3,3], fmax_out [B].
+ *
+ * One step for system b (dot3(a, b) = fma(a2, b2, fma(a1, b1, a0 b0)); cof(A): rows A1 x A2, A2 x A0, A0 x A1 with
+ * (u x v)_0 = fma(u1, v2, -(u2 v1)) and cyclic; det(A) = dot3(A0, cof(A)0)):
+ *   1. F_jk = x_in[n + j][k] / c;  V = det(cell_in);  FinvT = cof(F) / det(F).
+ *      The system is SKIPPED (nothing written but fmax_out[b] = NaN) when det F <= 0, when F, det F, V, p or c is not finite, when
+ *      c <= 0, or when its state words are impossible (as nnhip_lbfgs_step).
+ *   2. Wp = W with p V subtracted on the diagonal;  Wc_ij = fma(Wp_i2, FinvT_2j, fma(Wp_i1, FinvT_1j, Wp_i0 FinvT_0j));  then, in this
+ *      order:  NNHIP_CELL_LBFGS_HYDROSTATIC  Wc = (((Wc_00 + Wc_11) + Wc_22) / 3) I;   strain_mask  the masked components are +0;
+ *      NNHIP_CELL_LBFGS_CONSTANT_VOLUME  Wc_ii -= ((Wc_00 + Wc_11) + Wc_22) / 3.
+ *   3. G: cell row i = Wc_i / c;  atom row a, component j = fma(f_a2, F_2j, fma(f_a1, F_1j, f_a0 F_0j)), exactly 0 for a fixed atom
+ *      (its q is frozen: it rides with the cell).
+ *   4. fmax2 = max over all n + 3 rows of |G_row|^2;  fmax_out[b] = sqrt(fmax2).
+ *   5. Frozen when converged[b] is set, or fmax2 < tol2, or flags has NNHIP_CELL_LBFGS_CHECK_ONLY: converged[b] is set in the first
+ *      two cases only; x_out, pos_out, cell_out = x_in, pos_in, cell_in bitwise; nothing else is touched (G included).
+ *   6. Otherwise steps 4 to 7 of nnhip_lbfgs_step on (X, G) over the n + 3 rows (the clamp takes the longest ROW, cell rows
+ *      included; the work vector is in registers up to 64 rows), G_prev = G, n_steps[b] += 1.
+ *   7. F'_jk = x_out[n + j][k] / c;  cell_out_ij = dot3_k(h0_ik, F'_jk);  pos_out_aj = dot3_k(q_ak, F'_jk) with q = x_out's atom rows.
+ * x_out, pos_out and cell_out may NOT overlap x_in, pos_in and cell_in (NNHIP_E_INVALID, nothing is launched), for the reason
+ * given at nnhip_md_step.  NULL mandatory pointers, memory outside 1 .. NNHIP_LBFGS_MAX_MEMORY, unknown flag bits, strain_mask
+ * outside 0 .. 63, tol2 < 0, alpha or maxstep that are not finite and > 0 are refused likewise; cell_factor lives on the device,
+ * so a value that is not finite and > 0 skips its system (step 1).  n_mol == 0 is success without a launch.
+ * Cost: a system of n atoms takes about 2 m ceil((n + 3) / 64) dependent sweeps of ONE wave.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_CELL_LBFGS_CHECK_ONLY 1
+#define NNHIP_CELL_LBFGS_HYDROSTATIC 2
+#define NNHIP_CELL_LBFGS_CONSTANT_VOLUME 4
+int nnhip_cell_lbfgs_step(const float* x_in, const float* pos_in, const float* force, const float* virial, const float* cell_in,
+                          const float* h0, const uint8_t* free_mask, const int32_t* mol_ptr, const float* pressure,
+                          const float* cell_factor, int32_t n_mol, int32_t n_atoms, int32_t memory, float tol2, float alpha,
+                          float maxstep, int32_t strain_mask, int32_t flags, int32_t* converged, int32_t* n_steps, int32_t* n_pairs,
+                          int32_t* head, float* S, float* Y, float* rho, float* g_prev, float* work, float* G, float* x_out,
+                          float* pos_out, float* cell_out, float* fmax_out, void* stream);
+
+/* --------------------------------------------------------------------------
  * Intrinsic-reaction-coordinate following on the device (csrc/irc.hip): ONE launch on `stream` moves every path of a batch by one
  * step of the damped velocity Verlet scheme (after Hratchian and Schlegel, J. Phys. Chem. A 106, 165 (2002)) from the forces just
  * evaluated.  The path is a trajectory whose speed is reset to the constant v0 after every step: with a = c F / m

@@ -799,7 +799,50 @@ def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.T
            'nnhip_lbfgs_step')
 
 
-NEB_CHECK_ONLY, NEB_CLIMB = _K['NNHIP_NEB_CHECK_ONLY'], _K['NNHIP_NEB_CLIMB']      # flags of nnhip_neb_step
+# flags of nnhip_cell_lbfgs_step
+CELL_LBFGS_CHECK_ONLY, CELL_LBFGS_HYDROSTATIC, CELL_LBFGS_CONSTANT_VOLUME = (
+    _K['NNHIP_CELL_LBFGS_' + name] for name in ('CHECK_ONLY', 'HYDROSTATIC', 'CONSTANT_VOLUME'))
+CELL_LBFGS_MASK_ALL = 63         # strain_mask with all six Voigt components (xx, yy, zz, yz, xz, xy) free
+
+
+def cell_lbfgs_step(x_in: torch.Tensor, pos_in: torch.Tensor, force: torch.Tensor, virial: torch.Tensor, cell_in: torch.Tensor,
+                    h0: torch.Tensor, free: Optional[torch.Tensor], mol_ptr: torch.Tensor, pressure: torch.Tensor,
+                    cell_factor: torch.Tensor, memory: int, tol2: float, alpha: float, maxstep: float, strain_mask: int, flags: int,
+                    converged: torch.Tensor, n_steps: torch.Tensor, n_pairs: torch.Tensor, head: torch.Tensor, S: torch.Tensor,
+                    Y: torch.Tensor, rho: torch.Tensor, g_prev: torch.Tensor, work: Optional[torch.Tensor], G: torch.Tensor,
+                    x_out: torch.Tensor, pos_out: torch.Tensor, cell_out: torch.Tensor, fmax_out: torch.Tensor):
+    """One launch of the variable-cell L-BFGS step (nnhip_cell_lbfgs_step, csrc/cellrelax.hip; the contract is in
+    include/newtonnet_hip.h) on the current stream, for the B periodic systems mol_ptr (int32 [B+1]) delimits.  With R = N + 3 B
+    generalised rows (system b: its atom rows, then the three rows of cell_factor x F): x_in [R,3], pos_in, force [N,3], virial,
+    cell_in, h0 [B,3,3], pressure (eV / Angstrom^3) and cell_factor [B] are read; free: bool / uint8 [N] (False = fixed atom) or
+    None; strain_mask: bit k frees the Voigt component k; the state (converged, n_steps, n_pairs, head int32 [B]; S, Y fp32
+    [memory,R,3]; rho fp32 [B,memory]; g_prev fp32 [R,3]) is updated in place, G and x_out [R,3], pos_out [N,3], cell_out [B,3,3]
+    and fmax_out [B] are written: all of these must be contiguous tensors of exactly that type (a copy would take the result
+    away).  work: fp32 [R,3] scratch, needed when R > 64.  x_out, pos_out, cell_out may not overlap x_in, pos_in, cell_in."""
+    B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
+    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
+        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
+    N, slots = pos_out.shape[0], max(m, 0)
+    R = N + 3 * B
+    _written(dev, optional=('work',), converged=(converged, B, i32), n_steps=(n_steps, B, i32), n_pairs=(n_pairs, B, i32),
+             head=(head, B, i32), S=(S, slots * R * 3), Y=(Y, slots * R * 3), rho=(rho, B * slots), g_prev=(g_prev, 3 * R),
+             work=(work, 3 * R), G=(G, 3 * R), x_out=(x_out, 3 * R), pos_out=(pos_out, 3 * N), cell_out=(cell_out, 9 * B),
+             fmax_out=(fmax_out, B))
+    if free is not None:
+        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
+            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
+        free = free.contiguous()
+    x_in, pos_in, force, virial, cell_in, h0, pressure, cell_factor = _read(
+        dev, x_in=(x_in, 3 * R), pos_in=(pos_in, 3 * N), force=(force, 3 * N), virial=(virial, 9 * B), cell_in=(cell_in, 9 * B),
+        h0=(h0, 9 * B), pressure=(pressure, B), cell_factor=(cell_factor, B))
+    _check(lib().nnhip_cell_lbfgs_step(
+        _ptr(x_in), _ptr(pos_in), _ptr(force), _ptr(virial), _ptr(cell_in), _ptr(h0), _ptr(free), _ptr(mol_ptr), _ptr(pressure),
+        _ptr(cell_factor), B, N, m, float(tol2), float(alpha), float(maxstep), int(strain_mask), int(flags), _ptr(converged),
+        _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S), _ptr(Y), _ptr(rho), _ptr(g_prev), _ptr(work), _ptr(G), _ptr(x_out),
+        _ptr(pos_out), _ptr(cell_out), _ptr(fmax_out), _stream(dev)), 'nnhip_cell_lbfgs_step')
+
+
+NEB_CHECK_ONLY, NEB_CLIMB =_K['NNHIP_NEB_CHECK_ONLY'], _K['NNHIP_NEB_CLIMB']      # flags of nnhip_neb_step
 NEB_MAX_IMAGES = _K['NNHIP_NEB_MAX_IMAGES']
 # ase.optimize.FIRE's defaults, in the order nnhip_neb_step takes them: dt, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep
 NEB_FIRE_DEFAULTS = (0.1, 1.0, 5, 1.1, 0.5, 0.1, 0.99, 0.2)

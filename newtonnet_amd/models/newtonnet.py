@@ -848,6 +848,22 @@ class NewtonNet(nn.Module):
         from newtonnet_amd import relax as _r
         return _r.Relaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, fixed=fixed)
 
+    def cell_relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, pressure=0.0, mask=None,
+                        hydrostatic=False, constant_volume=False, cell_factor=None, fixed=None):
+        """Variable-cell relaxation of every periodic system of the batch on the device, atoms and cell together: a
+        newtonnet_amd.cellrelax.CellRelaxation whose run(max_steps, check_every, record_every) makes one model call and one launch
+        (csrc/cellrelax.hip) per step, each system with its own history and convergence flag.  ASE's UnitCellFilter under the
+        L-BFGS of `relaxation`: fmax (eV / Angstrom) bounds the largest generalised force, atoms and cell rows alike; pressure
+        (bar): a number or one per system, the stress the cell is relaxed to; mask: six 0/1 flags (xx, yy, zz, yz, xz, xy) of
+        the strain components that may change; hydrostatic: only the volume changes; constant_volume: only the shape changes;
+        cell_factor: the weight of the cell rows (None: the atom count); fixed: bool [N], atoms that keep their scaled position
+        and ride with the cell.  Eval mode only; needs the 'energy' and 'gradient_force' heads and a 'virial' or 'stress' head;
+        every system needs det(cell) > 0."""
+        from newtonnet_amd import cellrelax as _c
+        return _c.CellRelaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, pressure=pressure,
+                                 mask=mask, hydrostatic=hydrostatic, constant_volume=constant_volume, cell_factor=cell_factor,
+                                 fixed=fixed)
+
     def band(self, z, pos, cell, batch, n_images, spring=0.1, fmax=0.05, climb=True, climb_below=None, fixed=None, dt=0.1,
              dt_max=1.0, maxstep=0.2):
         """Nudged-elastic-band saddle search on the device: a newtonnet_amd.neb.Band whose run(max_steps, check_every,

@@ -9,8 +9,8 @@ stated in include/newtonnet_hip.h: a curvature pair enters the history only when
 
 A molecule that has converged is frozen -- later launches leave every bit of it alone -- but model() keeps evaluating it with the
 rest of the batch: compacting the batch is not done here.  Minima only (saddles: newtonnet_amd.dimer, which takes its translation
-from the same device code, csrc/lbfgs_chain.h): no Hessian-based steps, no cell relaxation, no
-constraint other than fixed atoms.  The launch gives one wave64 to a molecule, whatever its size: it is meant for batches of
+from the same device code, csrc/lbfgs_chain.h) at a fixed cell (the cell is relaxed by newtonnet_amd.cellrelax, again on that
+device code): no Hessian-based steps, no constraint other than fixed atoms.  The launch gives one wave64 to a molecule, whatever its size: it is meant for batches of
 molecules, and one large system pays about 2 memory ceil(n / 64) dependent sweeps of a single wave per step.
 
 Units: positions in Angstrom, forces and fmax in eV / Angstrom, alpha in eV / Angstrom^2."""

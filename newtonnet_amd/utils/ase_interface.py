@@ -510,6 +510,52 @@ class MLAseCalculator(_Base):
             out = {k: v[0] for k, v in out.items()}
         return out
 
+    def relax_cell(self, atoms_or_list, fmax: float = 0.01, max_steps: int = 500, memory: int = 16, maxstep: float = 0.2,
+                   alpha: float = 70.0, pressure=0.0, mask=None, hydrostatic: bool = False, constant_volume: bool = False,
+                   cell_factor=None, check_every: int = 10, fixed=None):
+        """Relax the atoms and the cell of one periodic structure or a list of equally sized ones, all stepped together on the
+        device (NewtonNet.cell_relaxation: ASE's UnitCellFilter under L-BFGS), until the largest generalised force of a structure
+        (atoms and cell rows alike) is below fmax (eV / Angstrom) or max_steps steps have been taken.  pressure in bar (a number,
+        or one value per structure); mask: six 0/1 flags xx, yy, zz, yz, xz, xy; fixed: bool array [n_atoms], the same atoms held
+        (at their scaled positions) in every structure.  The calculator's model needs a virial or stress head (properties with
+        'stress').  Returns a dict of numpy arrays: positions [n_frames, n_atoms, 3], cell and stress (bar) [n_frames, 3, 3],
+        volume, energy, enthalpy, fmax, converged, failed, n_steps [n_frames]; one structure drops the frame axis.  The Atoms
+        objects are not modified."""
+        from newtonnet_amd import cellrelax as _c
+        from newtonnet_amd import relax as _r
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        if not atoms:
+            raise ValueError('relax_cell: at least one structure expected')
+        n_frames, n_atoms = len(atoms), len(atoms[0])
+        if any(len(a) != n_atoms for a in atoms):
+            raise ValueError('relax_cell: frames of different sizes cannot share one array; use model.cell_relaxation (packed per '
+                             'system)')
+        _r.check_arguments(fmax, memory, maxstep, alpha)
+        _r.check_run_arguments(max_steps, check_every, 0)
+        if isinstance(pressure, (list, tuple, np.ndarray)):
+            pressure = torch.tensor(np.asarray(pressure, dtype=np.float64))
+        _c.check_cell_arguments(n_frames, pressure, mask, hydrostatic, constant_volume, cell_factor)
+        _c.check_model(self.model, 'relax_cell')
+        if fixed is not None:
+            fixed = np.asarray(fixed)
+            if fixed.dtype != np.bool_ or fixed.shape != (n_atoms,):
+                raise ValueError(f'fixed: a bool array [{n_atoms}] expected')
+        if self.device.type != 'cuda':
+            raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: make the calculator with device="cuda"')
+        z, pos, cell, batch = self.format_data(atoms)
+        held = None if fixed is None else torch.from_numpy(np.tile(fixed, n_frames)).to(pos.device)
+        rel = self.model.cell_relaxation(z, pos.float(), cell.float(), batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha,
+                                         pressure=pressure, mask=mask, hydrostatic=hydrostatic, constant_volume=constant_volume,
+                                         cell_factor=cell_factor, fixed=held)
+        res = rel.run(int(max_steps), int(check_every))
+        out = dict(positions=res.pos.cpu().numpy().reshape(n_frames, n_atoms, 3), cell=res.cell.cpu().numpy(),
+                   stress=res.stress.cpu().numpy(), volume=res.volume.cpu().numpy(), energy=res.energy.cpu().numpy(),
+                   enthalpy=res.enthalpy.cpu().numpy(), fmax=res.fmax.cpu().numpy(), converged=res.converged.cpu().numpy(),
+                   failed=res.failed.cpu().numpy(), n_steps=res.n_steps.cpu().numpy())
+        if n_frames == 1:
+            out = {k: v[0] for k, v in out.items()}
+        return out
+
     def neb(self, images_or_list_of_bands, spring: float = 0.1, fmax: float = 0.05, max_steps: int = 500, climb: bool = True,
             climb_below=None, dt: float = 0.1, dt_max: float = 1.0, maxstep: float = 0.2, check_every: int = 10, fixed=None):
         """Nudged-elastic-band saddle search of one band (a list of Atoms-like images in path order, the first and last being the
