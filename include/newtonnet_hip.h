@@ -1585,6 +1585,43 @@ int nnhip_npt_step(const float* pos_in, float* vel, const float* force, const fl
                    float c1, int32_t flags, int32_t n_atoms, float* pos_out, float* ke_out, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Batched phonon dispersion of crystals (csrc/phonon.hip): the dynamical matrix D(q) of every (crystal, wave vector) pair
+ * assembled and diagonalised in ONE launch; a problem has d = 3 n_b coordinates (n_b atoms of the primitive cell).
+ *   fc / fc_ptr [n_cry]: force constants Phi(i, J) = d^2 E / d r_i d r_J of the home atoms i against the N_b atoms J of a
+ *     supercell, fp32 [n_b][3][N_b][3] per crystal at fc + fc_ptr[b]; J = R n_b + j is copy R of home atom j, the home cell first.
+ *   cry_ptr [n_cry + 1] (device) / cry_ptr_host (host, identical): home-atom offsets; sc_atoms [n_cry]: N_b (a multiple of n_b).
+ *   img_ptr [n_cry], img_start, img_off: the image table.  Pair (i, J) of crystal b owns the rows
+ *     img_start[img_ptr[b] + i N_b + J] .. img_start[img_ptr[b] + i N_b + J + 1] - 1 of img_off [.][3] (fp64): the m_iJ equally near
+ *     supercell-lattice images of J seen from i, each as r_J + T - r_i in units of the PRIMITIVE lattice vectors.
+ *   masses [n_home] (amu; null: unit masses), q [n_q][3] fp64: wave vectors in units of the primitive reciprocal vectors, shared
+ *     by all crystals.  out_ptr [n_cry]: sum of d^2 over the crystals before b.
+ *   D_ij(q) = (m_i m_j)^-1/2 sum_J Phi(i, J) (1 / m_iJ) sum_T exp(2 pi i q . x_T), J over the copies of j, then (D + D^H) / 2.  The
+ *     phase product is formed in fp64 and reduced to [-1/2, 1/2] before the sine and cosine; every sum has a fixed order.
+ *   Complex Hermitian cyclic Jacobi in LDS, round-robin ordering, until off(A) <= 2^-24 ||A||_F or 30 sweeps (the rule and the
+ *     status bits of nnhip_eig_blocks: bit 0 sweep cap, bit 1 cry_ptr gives the crystal more atoms than cry_ptr_host did, bit 2 a
+ *     mass that is not positive and finite; with bit 1 or 2 nothing of the problem is written).
+ *   evals: [n_q][d] per crystal at n_q 3 cry_ptr[b], ascending per (b, q).  modes (may be null: the eigenvalues keep every bit):
+ *     complex64 (re, im) [n_q][d][d] per crystal at 2 n_q out_ptr[b] floats, ROW k = mode k, unit norm, the component of largest
+ *     magnitude real and positive (lowest index on a tie).  dmat (may be null): D(q) itself, laid out like modes.
+ *     sweeps / status: [n_cry][n_q].
+ * A crystal with d <= 32 gives each problem one wave (four problems per workgroup), a larger one a whole workgroup; the result of
+ * a (b, q) does not depend on that, nor on the other problems of the launch.  No float atomics: bitwise repeatable.
+ * Checked from cry_ptr_host BEFORE any launch: NNHIP_E_UNSUPPORTED above nnhip_phonon_max_dim (96: 32 atoms; A and the modes of a
+ * problem take 16 d (d + 1) bytes of the 160 KiB of LDS), the message names the bound and the crystal.
+ *   nnhip_phonon_dos: density of states of values [val_ptr[b], val_ptr[b + 1]) per crystal over n_bins equal bins of [lo, hi]: one
+ *     thread per bin walks the values in order.  counts (int32 [n_cry][n_bins], may be null): the histogram, integers only
+ *     (a value equal to hi falls into the last bin, values outside are not counted).  density (fp32 [n_cry][n_bins], may be null;
+ *     needs width > 0): sum over the values of the unit Gaussian of standard deviation `width` at the bin centre, summed in fp64.
+ * ------------------------------------------------------------------------ */
+int nnhip_phonon_max_dim(void);
+int nnhip_phonon_bands(const float* fc, const int64_t* fc_ptr, const int32_t* cry_ptr, const int32_t* cry_ptr_host,
+                       const int32_t* sc_atoms, const int64_t* img_ptr, const int32_t* img_start, const double* img_off,
+                       const float* masses, const int64_t* out_ptr, int32_t n_cry, const double* q, int32_t n_q, float* evals,
+                       float* modes, float* dmat, int32_t* sweeps, int32_t* status, void* stream);
+int nnhip_phonon_dos(const float* values, const int64_t* val_ptr, int32_t n_cry, float lo, float hi, int32_t n_bins, float width,
+                     int32_t* counts, float* density, void* stream);
+
+/* --------------------------------------------------------------------------
  * Timing hook for bench.py: wraps the kernels of one nnhip_energy_forces call
  * in HIP events on `stream` and accumulates per-kernel-class milliseconds.
  * classes: 0 = edge kernels (message/force fwd+adjoint), 1 = all dense MFMA kernels, 2 = everything else,

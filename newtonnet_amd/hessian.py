@@ -101,12 +101,14 @@ def replicas_for(n_atoms: int, n_dirs: int) -> int:
     return max(1, min(n_dirs, REPLICA_ATOM_BUDGET // n_atoms))
 
 
-def hessian_blocks_counts(model, z, pos, cell, batch,
-                          replicas: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def hessian_blocks_counts(model, z, pos, cell, batch, replicas: Optional[int] = None,
+                          n_dirs: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Packed per-molecule Hessians plus the atom counts: (blocks fp32 [sum_b 9 n_b^2], blk_ptr int64 [B] on the device, counts
     int64 [B] on the CPU); block b = blocks[blk_ptr[b]:][:9 n_b^2] viewed as [n_b, 3, n_b, 3].  `replicas`: R of the replica
     scheme (None: replicas_for).  The counts are what this function brings to the host for blk_ptr anyway; a consumer of the
-    blocks (newtonnet_amd/vibrations.py) takes them from here for its own offsets and size checks instead of copying again."""
+    blocks (newtonnet_amd/vibrations.py) takes them from here for its own offsets and size checks instead of copying again.
+    n_dirs: only the first n_dirs columns of every block are computed (None: all 3 max n_b; the other columns of the returned
+    blocks are then not written) -- what newtonnet_amd/phonons.py needs of a supercell's Hessian are its home atoms' columns."""
     _validate(model, pos)
     n_mol = cell.shape[0]
     counts = torch.bincount(batch.long().reshape(-1), minlength=n_mol).cpu() if pos.shape[0] else torch.zeros(n_mol, dtype=torch.long)
@@ -115,7 +117,8 @@ def hessian_blocks_counts(model, z, pos, cell, batch,
     total = int(sizes.sum())
     blocks = torch.empty(total, dtype=torch.float32, device=pos.device)
     blk_dev = blk_ptr.to(pos.device)
-    n_dirs = 3 * int(counts.max()) if n_mol else 0
+    n_all = 3 * int(counts.max()) if n_mol else 0
+    n_dirs = n_all if n_dirs is None else max(0, min(int(n_dirs), n_all))
     if total == 0:
         return blocks, blk_dev, counts
     r = replicas_for(pos.shape[0], n_dirs) if replicas is None else max(1, min(int(replicas), n_dirs))

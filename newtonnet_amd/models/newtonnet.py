@@ -754,6 +754,17 @@ class NewtonNet(nn.Module):
             return _v.normal_modes(self, z, pos, cell, batch, masses=masses, project=project, modes=modes, tol_zero=tol_zero,
                                    solver=solver)
 
+    def phonons(self, z, pos, cell, batch, supercell, masses=None, asr: bool = True):
+        """Phonons of B crystals (z, pos, cell, batch are their primitive cells, every cell non-zero): the analytic force
+        constants of the home atoms on a supercell (`supercell`: three integers, or an integer [B, 3]; every perpendicular
+        width of it at least twice the cutoff), as a newtonnet_amd.phonons.Phonons.  Its frequencies(q) / band_structure(points,
+        n) / mesh(n1, n2, n3) assemble and diagonalise the dynamical matrix of every (crystal, wave vector) pair in one launch
+        (csrc/phonon.hip); the mesh gives dos(n_bins, width) and thermochemistry(T) per primitive cell.  masses: fp32 [N] amu
+        (None: standard atomic weights of z); asr: impose the acoustic sum rule.  Primitive cells of up to phonons.max_dim() / 3
+        = 32 atoms.  Eval mode only; needs the 'energy' head; uses the current parameters."""
+        from newtonnet_amd import phonons as _p
+        return _p.phonons(self, z, pos, cell, batch, supercell, masses=masses, asr=asr)
+
     def sample_displacements(self, z, pos, cell, batch, n_samples: int, temperature: float, quantum: bool = False, masses=None,
                              generator=None, solver: str = 'lds'):
         """n_samples displaced geometries per molecule drawn from the harmonic distribution around `pos` at `temperature` (K):

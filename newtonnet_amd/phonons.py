@@ -1,0 +1,544 @@
+"""Batched phonon dispersion, density of states and harmonic thermochemistry of crystals on the HIP path.
+
+normal_modes treats a periodic system as a molecule at Gamma.  Here B primitive cells go through the finite-displacement-free
+supercell method: the analytic Hessian columns of the home atoms on a supercell (nnhip_hessian_blocks with n_dirs = 3 n_b) are
+the force constants Phi(i, J); ONE launch of nnhip_phonon_bands (csrc/phonon.hip) then assembles the dynamical matrix D(q) and
+diagonalises the complex Hermitian d x d problem (d = 3 n_b) for every crystal and every wave vector of a path or a mesh.
+
+Convention.  Supercell atom J = R n_b + j is the copy of home atom j at lattice offset R (the home cell R = 0 first, then the
+offsets in lexicographic order, last index fastest).  For each (i, J) the image table holds the supercell-lattice translations
+T in {-1, 0, 1}^3 that minimise |r_J + T - r_i| (ties at relative 1e-8, m_iJ of them), stored as r_J + T - r_i in units of the
+primitive lattice vectors, and
+    D_ij(q) = (m_i m_j)^-1/2 sum_{J in copies of j} Phi(i, J) (1 / m_iJ) sum_T exp(i q . (r_J + T - r_i)),   then (D + D^H) / 2.
+It is Hermitian at any q and reproduces the supercell's spectrum exactly over the commensurate q.  q is given in units of the
+primitive reciprocal vectors (q_frac . x_frac = q . r / 2 pi).
+
+Units as in vibrations.py: eigenvalues in eV / (A^2 amu), frequencies in cm^-1 (x 521.4709, negative = imaginary).
+
+Left out: the non-analytic LO-TO correction (it needs Born charges, which the model has not got), symmetry reduction of meshes
+and paths, group velocities, primitive cells above max_dim() coordinates.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from newtonnet_amd import hessian as _hessian
+from newtonnet_amd import hip
+from newtonnet_amd import vibrations as _v
+
+TIE_TOL = 1e-8          # relative tolerance at which two images count as equally near
+EPS32 = _v.EPS32
+
+
+def max_dim() -> int:
+    """Largest d = 3 n_b of a primitive cell nnhip_phonon_bands serves (nnhip_phonon_max_dim): the dynamical matrix and its
+    eigenvectors of one (crystal, q) problem live in the LDS of one workgroup."""
+    return int(hip.lib().nnhip_phonon_max_dim())
+
+
+# ---- host helpers (numpy, fp64) ----------------------------------------------------------------------------------------------
+
+def lattice_offsets(supercell) -> np.ndarray:
+    """int [S1 S2 S3, 3]: the lattice offsets of the supercell's copies, the home cell (0, 0, 0) first, last index fastest."""
+    a, b, c = (int(s) for s in supercell)
+    return np.array([(i, j, k) for i in range(a) for j in range(b) for k in range(c)], dtype=np.int64).reshape(-1, 3)
+
+
+def build_supercell(z, pos, cell, supercell):
+    """(z [N], pos [N,3] fp64, cell [3,3] fp64) of the supercell of one primitive cell (z [n], pos [n,3], cell [3,3] with the
+    lattice vectors as rows): atom R n + j is home atom j moved by offset R of lattice_offsets."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    L = lattice_offsets(supercell).astype(np.float64)
+    big = (pos[None, :, :] + (L @ cell)[:, None, :]).reshape(-1, 3)
+    return np.tile(np.asarray(z).reshape(-1), len(L)), big, np.asarray(supercell, dtype=np.float64).reshape(3, 1) * cell
+
+
+def perpendicular_widths(cell) -> np.ndarray:
+    """[3]: distance between the two faces of the cell that lattice vector k connects, V / |a_l x a_m|."""
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    vol = abs(np.linalg.det(cell))
+    return np.array([vol / np.linalg.norm(np.cross(cell[(k + 1) % 3], cell[(k + 2) % 3])) for k in range(3)])
+
+
+_T27 = np.array([(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)], dtype=np.float64)
+
+
+def image_table(pos, cell, supercell, tol: float = TIE_TOL):
+    """(start int32 [n N + 1], offsets fp64 [n_img, 3]) of one crystal: pair (i, J) owns offsets[start[i N + J]:start[i N + J + 1]],
+    the nearest images r_J + T - r_i in units of the primitive lattice vectors, T in lexicographic order."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    S = np.asarray(supercell, dtype=np.float64).reshape(3)
+    frac = pos @ np.linalg.inv(cell)
+    n = len(pos)
+    fJ = (lattice_offsets(supercell).astype(np.float64)[:, None, :] + frac[None, :, :]).reshape(-1, 3)
+    x = fJ[None, :, None, :] - frac[:, None, None, :] + (_T27 * S)[None, None, :, :]          # [n, N, 27, 3]
+    dist = np.linalg.norm(x @ cell, axis=-1)
+    keep = dist <= dist.min(axis=-1, keepdims=True) * (1.0 + tol)
+    start = np.zeros(n * len(fJ) + 1, dtype=np.int64)
+    np.cumsum(keep.sum(axis=-1).reshape(-1), out=start[1:])
+    if start[-1] >= 2 ** 31:
+        raise NotImplementedError('image table above 2^31 entries')
+    return start.astype(np.int32), np.ascontiguousarray(x[keep])
+
+
+def monkhorst_pack(n1: int, n2: int, n3: int, shift: bool = False) -> np.ndarray:
+    """fp64 [n1 n2 n3, 3]: the full regular grid q_c = (k_c + s) / n_c, k_c = 0 .. n_c - 1, folded into [-1/2, 1/2); s = 0
+    (the grid holds Gamma; mesh(S1, S2, S3) is the set commensurate with an S1 x S2 x S3 supercell) or s = 1/2 (shift=True).  Last
+    index fastest, no symmetry reduction."""
+    ns = []
+    for n in (n1, n2, n3):
+        if int(n) != n or int(n) < 1:
+            raise ValueError(f'mesh: positive integers expected (got {(n1, n2, n3)!r})')
+        ns.append(int(n))
+    axes = [(np.arange(n, dtype=np.float64) + (0.5 if shift else 0.0)) / n for n in ns]
+    axes = [u - np.floor(u + 0.5) for u in axes]
+    g = np.stack(np.meshgrid(*axes, indexing='ij'), axis=-1).reshape(-1, 3)
+    return np.ascontiguousarray(g)
+
+
+def band_path(points, n_per_segment: int):
+    """(q fp64 [Q, 3], ticks): the piecewise-linear path through `points` ([P, 3], fractional reciprocal coordinates) with
+    n_per_segment points per segment (the start of a segment included, its end not) plus the last point; ticks[k] is the index
+    of points[k] in q."""
+    p = np.asarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 2 or not np.isfinite(p).all():
+        raise ValueError('points: at least two finite [3] wave vectors expected')
+    if int(n_per_segment) != n_per_segment or int(n_per_segment) < 1:
+        raise ValueError(f'n_per_segment: a positive integer expected (got {n_per_segment!r})')
+    m = int(n_per_segment)
+    t = np.arange(m, dtype=np.float64)[:, None] / m
+    q = [p[k][None, :] + t * (p[k + 1] - p[k])[None, :] for k in range(len(p) - 1)]
+    q.append(p[-1:])
+    return np.concatenate(q), [m * k for k in range(len(p))]
+
+
+def path_length(q, cell) -> np.ndarray:
+    """fp64 [Q]: cumulative length in 1 / Angstrom of the path q (fractional) in the reciprocal lattice 2 pi inv(cell)^T."""
+    recip = 2.0 * np.pi * np.linalg.inv(np.asarray(cell, dtype=np.float64).reshape(3, 3)).T
+    step = np.linalg.norm(np.diff(np.asarray(q, dtype=np.float64), axis=0) @ recip, axis=1)
+    return np.concatenate([[0.0], np.cumsum(step)])
+
+
+def symmetric_cell(pos, cell):
+    """(pos', cell') of one crystal (pos [n,3], cell [3,3], numpy fp64) rotated rigidly so that cell' is a symmetric matrix: the
+    polar decomposition cell = P Q (P symmetric positive definite, Q a rotation for a right-handed cell), cell' = P and
+    pos' = pos Q^T.  The form phonons() needs of a non-orthogonal cell (see there)."""
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    u, s, vh = np.linalg.svd(cell)
+    return np.asarray(pos, dtype=np.float64).reshape(-1, 3) @ (u @ vh).T, (u * s[None, :]) @ u.T
+
+
+def _supercells(supercell, n_cry: int) -> np.ndarray:
+    s = supercell.detach().cpu().numpy() if isinstance(supercell, torch.Tensor) else np.asarray(supercell)
+    if s.dtype.kind not in 'iu' or s.shape not in ((3,), (n_cry, 3)):
+        raise ValueError(f'supercell: three integers, or an integer [{n_cry}, 3], expected (got {supercell!r})')
+    s = np.broadcast_to(s.astype(np.int64), (n_cry, 3)).copy()
+    if (s < 1).any():
+        raise ValueError(f'supercell: every entry must be at least 1 (got {s.tolist()})')
+    return s
+
+
+def _cells(cell) -> np.ndarray:
+    c = cell.detach().double().cpu().numpy().reshape(-1, 3, 3)
+    for b in range(len(c)):
+        if not np.isfinite(c[b]).all() or not (np.abs(c[b]).max() > 0) or abs(np.linalg.det(c[b])) <= 1e-12 * np.abs(c[b]).max() ** 3:
+            raise ValueError(f'crystal {b}: a zero (or singular) cell has no phonon dispersion; use normal_modes for a molecule')
+    return c
+
+
+def _counts(batch, n_cry: int, n_atoms: int):
+    counts = torch.bincount(batch.long().reshape(-1).cpu(), minlength=n_cry).tolist() if n_atoms else [0] * n_cry
+    if len(counts) != n_cry:
+        raise ValueError('batch names more crystals than cell holds')
+    b = batch.long().reshape(-1).cpu()
+    if n_atoms and bool((b[1:] < b[:-1]).any()):
+        raise ValueError('batch: the atoms of a crystal must be contiguous and the crystals ascending')
+    return counts
+
+
+def _check_bound(counts):
+    bound = max_dim()
+    for b, n in enumerate(counts):
+        if 3 * n > bound:
+            raise NotImplementedError(f'crystal {b} has 3 x {n} = {3 * n} coordinates per primitive cell, above the {bound} of '
+                                      f'phonons.max_dim() (nnhip_phonon_max_dim)')
+
+
+# ---- results -------------------------------------------------------------------------------------------------------------------
+
+class PhononBands:
+    """Spectra of B crystals at Q wave vectors, packed per crystal (crystal b owns [Q, d_b] values at Q ptr[b]).
+
+    eigenvalues  fp32 [Q sum d_b]   eV / (A^2 amu), ascending per (b, q)
+    frequencies  fp32 [Q sum d_b]   cm^-1 = sign(lambda) sqrt(|lambda|) x 521.4709; negative = imaginary
+    modes        complex64 [Q sum d_b^2] or None: per (b, q) a [d_b, d_b] matrix, ROW k = mode k (mass-weighted, unit norm, the
+                 component of largest magnitude real and positive)
+    dynamical_matrix  complex64, laid out like modes, or None
+    sweeps, status    int32 [B, Q]  Jacobi sweeps used; status bit 0 = the sweep cap was hit, bit 2 = a bad mass
+    q            fp64 numpy [Q, 3]; path (band_structure only): fp64 numpy [B, Q] cumulative length in 1 / Angstrom, ticks
+    """
+
+    def __init__(self, **kw):
+        self.path = None
+        self.ticks = None
+        self.__dict__.update(kw)
+
+    def crystal(self, b: int):
+        """(eigenvalues [Q, d], frequencies [Q, d], modes [Q, d, d] or None) of crystal b: views, no copy."""
+        Q, d, o = len(self.q), self._dims[b], self._offsets[b]
+        ev = self.eigenvalues[Q * o:Q * (o + d)].view(Q, d)
+        fr = self.frequencies[Q * o:Q * (o + d)].view(Q, d)
+        return ev, fr, self._square(self.modes, b)
+
+    def _square(self, x, b):
+        if x is None:
+            return None
+        Q, d, o = len(self.q), self._dims[b], self._sq_offsets[b]
+        return x[Q * o:Q * (o + d * d)].view(Q, d, d)
+
+    def dynamical(self, b: int):
+        """D(q) of crystal b as complex64 [Q, d, d] (frequencies(..., dynamical_matrix=True) only)."""
+        return self._square(self.dynamical_matrix, b)
+
+
+class PhononDOS:
+    """frequencies fp32 [n_bins] (bin centres, cm^-1), dos fp32 [B, n_bins] in states per cm^-1 per primitive cell (it
+    integrates to d_b over the range), counts int32 [B, n_bins] or None (histogram form), bin_width."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class PhononThermochemistry:
+    """ZPE, U, F (eV) and S, Cv (eV / K) per primitive cell, fp32 [B], at `temperature` (K), averaged over the mesh;
+    n_skipped_zero / n_skipped_imaginary int64 [B]: the (q, mode) pairs of the mesh left out."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class PhononMesh:
+    """The spectra of a regular mesh (Phonons.mesh): `bands` (a PhononBands over the mesh points, equal weights)."""
+
+    def __init__(self, bands: PhononBands, phonons: 'Phonons'):
+        self.bands = bands
+        self._ph = phonons
+
+    def dos(self, n_bins: int, width: Optional[float] = None, lo: Optional[float] = None, hi: Optional[float] = None) -> PhononDOS:
+        """Density of states over n_bins equal bins of [lo, hi] cm^-1 (nnhip_phonon_dos: one thread per bin walks the mesh's
+        modes in a fixed order).  width=None: the plain histogram, integer counts / (Q bin_width); width (cm^-1): every mode
+        a unit Gaussian of that standard deviation, evaluated at the bin centres.  lo / hi default to the spectrum's range over
+        the whole batch, widened by a thousandth of it (by 5 widths for the Gaussian form) so that nothing falls outside."""
+        if int(n_bins) != n_bins or int(n_bins) < 1:
+            raise ValueError(f'n_bins: a positive integer expected (got {n_bins!r})')
+        if width is not None and not (float(width) > 0.0 and math.isfinite(float(width))):
+            raise ValueError(f'width: a finite value > 0 cm^-1 expected (got {width!r})')
+        bands, ph = self.bands, self._ph
+        f = bands.frequencies
+        if lo is None or hi is None:
+            fmin, fmax = (float(f.min()), float(f.max())) if f.numel() else (0.0, 1.0)
+            pad = 5.0 * float(width) if width is not None else 1e-3 * max(fmax - fmin, 1.0)
+            lo = fmin - pad if lo is None else lo
+            hi = fmax + pad if hi is None else hi
+        lo, hi = float(lo), float(hi)
+        if not (hi > lo and math.isfinite(lo) and math.isfinite(hi)):
+            raise ValueError(f'lo < hi, both finite, expected (got {lo!r}, {hi!r})')
+        n_bins, Q, B, dev = int(n_bins), len(bands.q), len(ph.counts), f.device
+        val_ptr = (Q * 3 * ph.cry_ptr.long()).contiguous()
+        counts = torch.zeros(B, n_bins, dtype=torch.int32, device=dev) if width is None else None
+        dens = torch.zeros(B, n_bins, dtype=torch.float32, device=dev) if width is not None else None
+        hip._check(hip.lib().nnhip_phonon_dos(hip._ptr(f), hip._ptr(val_ptr), B, lo, hi, n_bins, 0.0 if width is None else float(width),
+                                              hip._ptr(counts), hip._ptr(dens), hip._stream(dev)), 'nnhip_phonon_dos')
+        # the bins as the kernel sees them (fp32)
+        lo32, hi32 = np.float32(lo), np.float32(hi)
+        wbin = float((hi32 - lo32) / np.float32(n_bins))
+        centres = torch.tensor(lo32 + (np.arange(n_bins, dtype=np.float32) + np.float32(0.5)) * np.float32(wbin), device=dev)
+        dos = counts.float() / (Q * wbin) if width is None else dens / Q
+        return PhononDOS(frequencies=centres, dos=dos, counts=counts, bin_width=wbin, lo=float(lo32), hi=float(hi32))
+
+    def threshold(self, tol_zero: Optional[float] = None) -> torch.Tensor:
+        """fp32 [B]: tol_zero max |lambda| over the crystal's mesh (default tol_zero: 8 x 2 d x 2^-24, the solver's bound for a
+        complex d x d problem).  A mode is live iff lambda > threshold and imaginary iff lambda < -threshold."""
+        bands, ph = self.bands, self._ph
+        out = []
+        for b, n in enumerate(ph.counts):
+            ev = bands.crystal(b)[0]
+            tol = 8.0 * EPS32 * 6 * n if tol_zero is None else float(tol_zero)
+            out.append(tol * ev.abs().max() if ev.numel() else ev.new_zeros(()))
+        return torch.stack(out) if out else torch.zeros(0, device=bands.eigenvalues.device)
+
+    def thermochemistry(self, temperature: float, tol_zero: Optional[float] = None) -> PhononThermochemistry:
+        """Harmonic thermochemistry per primitive cell at `temperature` (K): the per-mode terms of
+        NormalModes.thermochemistry (x = eps / k_B T, eps = hbar omega)
+            ZPE = eps / 2,  U = eps / 2 + eps / (e^x - 1),  S = k_B (x / (e^x - 1) - ln(1 - e^-x)),
+            F = eps / 2 + k_B T ln(1 - e^-x),  C_v = k_B x^2 e^-x / (1 - e^-x)^2
+        summed over the live modes of every mesh point and divided by the number of points.  Modes with |lambda| <= threshold
+        (the three acoustic ones at Gamma) and imaginary ones are skipped and counted.  Elementwise torch ops in fp64 on the
+        device; T = 0 returns U = F = ZPE and S = C_v = 0."""
+        T = _v._temperature(temperature)
+        bands, ph = self.bands, self._ph
+        Q, dev = len(bands.q), bands.eigenvalues.device
+        thr = self.threshold(tol_zero)
+        rows, n_zero, n_imag = [], [], []
+        for b in range(len(ph.counts)):
+            ev = bands.crystal(b)[0].reshape(-1).double()
+            live, imag = ev > thr[b], ev < -thr[b]
+            n_imag.append(imag.sum())
+            n_zero.append((~live & ~imag).sum())
+            eps = _v.EV_PER_SQRT_EIGENVALUE * torch.where(live, ev, torch.ones_like(ev)).sqrt()
+            if T == 0.0:
+                terms = torch.stack([0.5 * eps] + [torch.zeros_like(eps)] * 4, dim=1)
+            else:
+                kT = _v.K_BOLTZMANN * T
+                x = (eps / kT).clamp(max=100.0)
+                em, om = torch.exp(-x), -torch.expm1(-x)
+                occ, ln = em / om, torch.log(om)
+                terms = torch.stack([0.5 * eps, eps * occ, _v.K_BOLTZMANN * (x * occ - ln), kT * ln,
+                                     _v.K_BOLTZMANN * x * x * em / (om * om)], dim=1)
+            rows.append(torch.where(live[:, None], terms, torch.zeros_like(terms)).sum(dim=0) / max(Q, 1))
+        s = torch.stack(rows) if rows else torch.zeros(0, 5, dtype=torch.float64, device=dev)
+        zpe = s[:, 0]
+        return PhononThermochemistry(ZPE=zpe.float(), U=(zpe + s[:, 1]).float(), S=s[:, 2].float(), F=(zpe + s[:, 3]).float(),
+                                     Cv=s[:, 4].float(), temperature=T, threshold=thr,
+                                     n_skipped_zero=torch.stack(n_zero) if n_zero else torch.zeros(0, dtype=torch.long, device=dev),
+                                     n_skipped_imaginary=torch.stack(n_imag) if n_imag else torch.zeros(0, dtype=torch.long, device=dev))
+
+
+class Phonons:
+    """Force constants of B crystals on their supercells, ready for any number of wave vectors.
+
+    fc           fp32, packed [n_b, 3, N_b, 3] per crystal at fc_ptr[b] (force_constants(b) is the view)
+    counts, sc_counts   atoms per primitive cell n_b / per supercell N_b (lists)
+    supercell    int numpy [B, 3]
+    masses       fp32 [n] amu;  z, pos, cell: the primitive cells
+    """
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def force_constants(self, b: int) -> torch.Tensor:
+        o, n, N = self._fc_offsets[b], self.counts[b], self.sc_counts[b]
+        return self.fc[o:o + 9 * n * N].view(n, 3, N, 3)
+
+    @classmethod
+    def from_force_constants(cls, fc, z, pos, cell, supercell, masses=None, batch=None, device=None) -> 'Phonons':
+        """A Phonons from force constants the caller has: fc is one [n, 3, N, 3] array / tensor, a list of them (one per
+        crystal), or the packed 1-d tensor; z [n_total], pos [n_total, 3], cell [B, 3, 3] (or [3, 3]) are the primitive cells,
+        batch [n_total] their crystal index (None: one crystal).  N_b must be n_b x prod(supercell_b), the supercell atoms in the
+        order of build_supercell.  masses: amu per home atom (None: standard atomic weights of z).  No width check and no
+        acoustic sum rule: the force constants are taken as they are.  device: where the tables go (default: that of fc when
+        it is a tensor, else of pos when it is one, else 'cuda')."""
+        if device is None:
+            src = fc if isinstance(fc, torch.Tensor) else fc[0] if isinstance(fc, (list, tuple)) and fc and \
+                isinstance(fc[0], torch.Tensor) else pos if isinstance(pos, torch.Tensor) else None
+            device = src.device if src is not None else torch.device('cuda')
+        device = torch.device(device)
+        pos_t = torch.as_tensor(np.asarray(pos) if not isinstance(pos, torch.Tensor) else pos).detach().reshape(-1, 3)
+        cell_t = torch.as_tensor(np.asarray(cell) if not isinstance(cell, torch.Tensor) else cell).detach().reshape(-1, 3, 3)
+        z_t = torch.as_tensor(np.asarray(z) if not isinstance(z, torch.Tensor) else z).detach().reshape(-1).long()
+        n_total, B = pos_t.shape[0], cell_t.shape[0]
+        if z_t.numel() != n_total:
+            raise ValueError(f'z: {z_t.numel()} values for {n_total} atoms')
+        if batch is None:
+            if B != 1:
+                raise ValueError(f'batch: needed with {B} crystals')
+            batch_t = torch.zeros(n_total, dtype=torch.long)
+        else:
+            batch_t = torch.as_tensor(np.asarray(batch) if not isinstance(batch, torch.Tensor) else batch).detach().reshape(-1).long()
+            if batch_t.numel() != n_total:
+                raise ValueError(f'batch: {batch_t.numel()} values for {n_total} atoms')
+        cells = _cells(cell_t)
+        S = _supercells(supercell, B)
+        counts = _counts(batch_t, B, n_total)
+        sc_counts = [n * int(np.prod(S[b])) for b, n in enumerate(counts)]
+        sizes = [9 * n * N for n, N in zip(counts, sc_counts)]
+        if isinstance(fc, (list, tuple)) or (hasattr(fc, 'ndim') and fc.ndim == 4):
+            parts = [fc] if not isinstance(fc, (list, tuple)) else list(fc)
+            if len(parts) != B:
+                raise ValueError(f'fc: {len(parts)} blocks for {B} crystals')
+            flat = []
+            for b, p in enumerate(parts):
+                p = torch.as_tensor(np.asarray(p) if not isinstance(p, torch.Tensor) else p).detach()
+                if tuple(p.shape) != (counts[b], 3, sc_counts[b], 3):
+                    raise ValueError(f'fc of crystal {b}: [{counts[b]}, 3, {sc_counts[b]}, 3] expected (got {tuple(p.shape)})')
+                flat.append(p.to(device=device, dtype=torch.float32).reshape(-1))
+            fc_t = torch.cat(flat) if flat else torch.zeros(0, dtype=torch.float32, device=device)
+        else:
+            fc_t = torch.as_tensor(fc).detach()
+            if fc_t.dim() != 1 or fc_t.numel() != sum(sizes):
+                raise ValueError(f'fc: packed 1-d with {sum(sizes)} values expected (got {tuple(fc_t.shape)})')
+            fc_t = hip._f32c(fc_t, 'fc').to(device)
+        _check_bound(counts)
+        if masses is None:
+            m_t = _v.table_masses(z_t)
+        else:
+            m_t = torch.as_tensor(np.asarray(masses) if not isinstance(masses, torch.Tensor) else masses).detach().reshape(-1)
+            if m_t.numel() != n_total:
+                raise ValueError(f'masses: {m_t.numel()} values for {n_total} atoms')
+        return cls._assemble(fc_t.contiguous(), z_t, pos_t, cell_t, cells, S, counts, sc_counts, m_t, device)
+
+    @classmethod
+    def _assemble(cls, fc_t, z_t, pos_t, cell_t, cells, S, counts, sc_counts, m_t, device) -> 'Phonons':
+        """the image tables (host, fp64, once per crystal) and the offset arrays of nnhip_phonon_bands"""
+        B = len(counts)
+        pos_h = pos_t.detach().double().cpu().numpy()
+        cry = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(counts, out=cry[1:])
+        starts, offs, img_ptr, n_off = [], [], [], 0
+        for b in range(B):
+            st, off = image_table(pos_h[cry[b]:cry[b + 1]], cells[b], S[b])
+            img_ptr.append(sum(len(s) for s in starts))
+            starts.append(st.astype(np.int64) + n_off)
+            offs.append(off)
+            n_off += len(off)
+        if n_off >= 2 ** 31:
+            raise NotImplementedError('image tables above 2^31 entries in one batch')
+        sizes = np.array([9 * n * N for n, N in zip(counts, sc_counts)], dtype=np.int64)
+        sq = np.array([9 * n * n for n in counts], dtype=np.int64)
+
+        def dev(a, dtype):
+            return torch.tensor(np.asarray(a), dtype=dtype).to(device)
+        cry_host = torch.tensor(cry, dtype=torch.int32)
+        return cls(fc=fc_t, fc_ptr=dev(np.cumsum(sizes) - sizes, torch.int64), _fc_offsets=(np.cumsum(sizes) - sizes).tolist(),
+                   counts=list(counts), sc_counts=list(sc_counts), supercell=S, masses=m_t.to(device=device, dtype=torch.float32).contiguous(),
+                   z=z_t.to(device), pos=pos_t.to(device), cell=cell_t.to(device), _cells=cells,
+                   cry_ptr=cry_host.to(device), _cry_host=cry_host, sc_atoms=dev(sc_counts, torch.int32),
+                   img_ptr=dev(img_ptr, torch.int64),
+                   img_start=dev(np.concatenate(starts) if starts else np.zeros(0), torch.int32),
+                   img_off=dev(np.concatenate(offs) if offs else np.zeros((0, 3)), torch.float64).contiguous(),
+                   out_ptr=dev(np.cumsum(sq) - sq, torch.int64), _sq_offsets=(np.cumsum(sq) - sq).tolist(),
+                   _offsets=(3 * cry[:-1]).tolist(), _dims=[3 * n for n in counts])
+
+    # ---- wave vectors ---------------------------------------------------------------------------------------------------------
+    def frequencies(self, q, modes: bool = False, dynamical_matrix: bool = False) -> PhononBands:
+        """The spectra at the wave vectors q ([Q, 3], units of the primitive reciprocal vectors, shared by all crystals) in one
+        launch of nnhip_phonon_bands.  modes=True also returns the eigenvectors; the eigenvalues are bitwise the same either
+        way, and those of a q do not depend on the other q of the call.  dynamical_matrix=True also returns D(q)."""
+        qh = q.detach().double().cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q, dtype=np.float64)
+        qh = np.ascontiguousarray(qh.reshape(-1, 3) if qh.size else qh.reshape(0, 3))
+        if not np.isfinite(qh).all():
+            raise ValueError('q: finite wave vectors expected')
+        dev = self.fc.device
+        if dev.type != 'cuda':
+            raise RuntimeError('newtonnet_amd phonons run on an MI355X (ROCm) device only: build the Phonons on "cuda"')
+        Q, B = len(qh), len(self.counts)
+        n_val, n_sq = 3 * sum(self.counts), sum(9 * n * n for n in self.counts)
+        evals = torch.zeros(Q * n_val, dtype=torch.float32, device=dev)
+        vec = torch.zeros(Q * n_sq, 2, dtype=torch.float32, device=dev) if modes else None
+        dm = torch.zeros(Q * n_sq, 2, dtype=torch.float32, device=dev) if dynamical_matrix else None
+        sweeps, status = (torch.zeros(B, Q, dtype=torch.int32, device=dev) for _ in range(2))
+        q_dev = torch.tensor(qh, dtype=torch.float64).to(dev)
+        if B and Q and n_val:
+            rc = hip.lib().nnhip_phonon_bands(hip._ptr(self.fc), hip._ptr(self.fc_ptr), hip._ptr(self.cry_ptr), self._cry_host.data_ptr(),
+                                              hip._ptr(self.sc_atoms), hip._ptr(self.img_ptr), hip._ptr(self.img_start),
+                                              hip._ptr(self.img_off), hip._ptr(self.masses), hip._ptr(self.out_ptr), B, hip._ptr(q_dev), Q,
+                                              hip._ptr(evals), hip._ptr(vec), hip._ptr(dm), hip._ptr(sweeps), hip._ptr(status),
+                                              hip._stream(dev))
+            if rc == 2:
+                raise NotImplementedError(hip.lib().nnhip_last_error().decode())
+            hip._check(rc, 'nnhip_phonon_bands')
+        freq = torch.sign(evals) * evals.abs().sqrt() * _v.WAVENUMBER_PER_SQRT_EIGENVALUE
+        return PhononBands(eigenvalues=evals, frequencies=freq, modes=None if vec is None else torch.view_as_complex(vec),
+                           dynamical_matrix=None if dm is None else torch.view_as_complex(dm), sweeps=sweeps, status=status, q=qh,
+                           _dims=self._dims, _offsets=self._offsets, _sq_offsets=self._sq_offsets)
+
+    def band_structure(self, points, n_per_segment: int = 20, modes: bool = False) -> PhononBands:
+        """frequencies() along the piecewise-linear path through `points` (band_path); the result also holds `path`, the
+        cumulative length in 1 / Angstrom per crystal [B, Q], and `ticks`, the indices of the given points."""
+        q, ticks = band_path(points, n_per_segment)
+        bands = self.frequencies(q, modes=modes)
+        bands.path = np.stack([path_length(q, c) for c in self._cells]) if len(self._cells) else np.zeros((0, len(q)))
+        bands.ticks = ticks
+        return bands
+
+    def mesh(self, n1: int, n2: int, n3: int, shift: bool = False) -> PhononMesh:
+        """The spectra on the full n1 x n2 x n3 grid of monkhorst_pack (no symmetry reduction), eigenvalues only."""
+        return PhononMesh(self.frequencies(monkhorst_pack(n1, n2, n3, shift)), self)
+
+
+# ---- from a model ----------------------------------------------------------------------------------------------------------------
+
+def _validate_model(model):
+    if model.training:
+        raise NotImplementedError('phonons run in eval mode only (training on Hessian labels is not supported): call model.eval()')
+    if 'energy' not in list(model.output_properties):
+        raise NotImplementedError("the force constants are the energy's: the model needs the 'energy' head (output_properties)")
+
+
+def acoustic_sum_rule(phi: torch.Tensor) -> torch.Tensor:
+    """Phi(i, i) <- Phi(i, i) - sum_J Phi(i, J) over ALL supercell atoms J (i itself included), then that 3 x 3 block symmetrised;
+    phi is [n, 3, N, 3] with the home atoms first (returns a new tensor)."""
+    phi = phi.clone()
+    n = phi.shape[0]
+    s = phi.double().sum(dim=2)                                    # [n, 3, 3]
+    idx = torch.arange(n, device=phi.device)
+    blk = phi[idx, :, idx, :].double() - s
+    phi[idx, :, idx, :] = (0.5 * (blk + blk.transpose(1, 2))).to(phi.dtype)
+    return phi
+
+
+def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor] = None, asr: bool = True) -> Phonons:
+    """Force constants of every primitive cell of the batch on its supercell at the current parameters (see the module text).
+    supercell: three integers, or an integer [B, 3].  Every perpendicular width of a supercell must be at least twice the
+    model's cutoff (its neighbour list takes one minimum image): ValueError otherwise, before any kernel.  A cell that is not
+    orthogonal must be given as a symmetric matrix (symmetric_cell rotates any crystal into that form): the model's minimum-image
+    shift is a lattice vector for such cells only.  masses: fp32 [N] amu
+    (None: standard atomic weights of z).  asr: impose the acoustic sum rule on the fp32 force constants."""
+    _validate_model(model)
+    n_atoms, B = pos.shape[0], cell.shape[0]
+    if tuple(pos.shape) != (n_atoms, 3) or tuple(cell.shape) != (B, 3, 3) or batch.numel() != n_atoms or z.numel() != n_atoms:
+        raise ValueError('z [N], pos [N,3], cell [B,3,3] and batch [N] expected')
+    cells = _cells(cell)
+    for b in range(B):
+        if np.abs(cells[b] - cells[b].T).max() > 1e-5 * np.abs(cells[b]).max():
+            raise ValueError(f'crystal {b}: the cell is not a symmetric matrix.  The model shifts a pair to its minimum image by '
+                             f'cell @ round(frac), as the reference writes it, which is a lattice vector only when cell = cell^T; with '
+                             f'another cell the supercell is not periodic in the primitive lattice and has no dispersion.  Rotate '
+                             f'the crystal first: phonons.symmetric_cell(pos, cell)')
+    S = _supercells(supercell, B)
+    counts = _counts(batch, B, n_atoms)
+    _check_bound(counts)
+    cutoff = float(model.embedding_layers.edge_embedding.cutoff)
+    for b in range(B):
+        w = perpendicular_widths(cells[b]) * S[b]
+        if (w < 2.0 * cutoff).any():
+            raise ValueError(f'crystal {b}: the supercell {S[b].tolist()} has perpendicular widths '
+                             f'{", ".join(f"{x:.3f}" for x in w)} A, below 2 x cutoff = {2.0 * cutoff:.3f} A (the neighbour list takes '
+                             f'a single minimum image): enlarge the supercell')
+    if masses is not None and masses.numel() != n_atoms:
+        raise ValueError(f'masses: {masses.numel()} values for {n_atoms} atoms')
+    m = _v.table_masses(z) if masses is None else masses.detach().reshape(-1)
+    if not pos.is_cuda:
+        raise RuntimeError('newtonnet_amd phonons run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
+    dev = pos.device
+    # the supercells as one batch (host, fp64, rounded once to fp32)
+    pos_h, z_h = pos.detach().double().cpu().numpy(), z.detach().reshape(-1).cpu().numpy()
+    off = np.concatenate([[0], np.cumsum(counts)])
+    zs, ps, cs, bs = [], [], [], []
+    for b in range(B):
+        zb, pb, cb = build_supercell(z_h[off[b]:off[b + 1]], pos_h[off[b]:off[b + 1]], cells[b], S[b])
+        zs.append(zb)
+        ps.append(pb)
+        cs.append(cb)
+        bs.append(np.full(len(zb), b))
+    sc_counts = [len(x) for x in zs]
+    z_sc = torch.tensor(np.concatenate(zs), dtype=torch.long, device=dev)
+    pos_sc = torch.tensor(np.concatenate(ps), dtype=torch.float32, device=dev)
+    cell_sc = torch.tensor(np.stack(cs), dtype=torch.float32, device=dev)
+    batch_sc = torch.tensor(np.concatenate(bs), dtype=torch.long, device=dev)
+    with torch.no_grad():
+        blocks, blk_ptr, _ = _hessian.hessian_blocks_counts(model, z_sc, pos_sc, cell_sc, batch_sc, n_dirs=3 * max(counts))
+    ptr = blk_ptr.tolist()
+    parts = []
+    for b, (n, N) in enumerate(zip(counts, sc_counts)):
+        # block[J, beta, i, alpha] = d^2 E / d r_J,beta d r_i,alpha: the first 3 n columns are the home atoms'
+        phi = blocks[ptr[b]:ptr[b] + 9 * N * N].view(N, 3, N, 3)[:, :, :n, :].permute(2, 3, 0, 1).contiguous()
+        parts.append((acoustic_sum_rule(phi) if asr else phi).reshape(-1))
+    fc_t = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
+    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev)

@@ -147,6 +147,19 @@ class MLAseCalculator(_Base):
         modes = nm.modes.cpu().numpy().reshape(n_frames, 3 * n_atoms, n_atoms, 3)
         return (freq[0], modes[0]) if n_frames == 1 else (freq, modes)
 
+    def phonons(self, atoms_or_list, supercell, asr: bool = True):
+        """Phonons of one crystal or a list of crystals (NewtonNet.phonons): a newtonnet_amd.phonons.Phonons over the
+        primitive cells given, ready for frequencies(q), band_structure(points, n) and mesh(n1, n2, n3).  supercell: three
+        integers, or one triple per structure.  Masses from atoms.get_masses() when the objects have it, else standard atomic
+        weights.  The structures may differ in size.  A method of its own: not a property of calculate()."""
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        z, pos, cell, batch = self.format_data(atoms)
+        masses = None
+        if all(hasattr(a, 'get_masses') for a in atoms):
+            masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
+                                  dtype=torch.float32, device=pos.device)
+        return self.model.phonons(z, pos.float(), cell.float(), batch, supercell, masses=masses, asr=asr)
+
     def sample(self, atoms, n_samples: int, temperature: float, quantum: bool = False, seed=None, solver: str = 'lds'):
         """n_samples geometries of one structure drawn from its harmonic distribution at `temperature` (K), as an
         [n_samples, n_atoms, 3] array in Angstrom (NewtonNet.sample_displacements: classical normal-mode sampling, or Wigner

@@ -1,0 +1,193 @@
+"""fp64 yardstick of the phonon module for the tests (pure numpy, plain loops): the supercell builder, the image table, the
+dynamical matrix D(q) with its rounding bound, the q grids and paths, the per-mode thermochemistry, and two synthetic crystals --
+an analytic cubic spring lattice and random translation-invariant force constants.  Independent of the package: nothing here
+imports newtonnet_amd."""
+import itertools
+
+import numpy as np
+
+from tests import vib_ref as vr
+
+EPS32 = vr.EPS32
+TIE_TOL = 1e-8
+K_BOLTZMANN = 8.617333262e-5
+EV_PER_SQRT_EIGENVALUE = vr.EV_PER_WAVENUMBER * vr.WAVENUMBER
+
+
+def lattice_offsets(S):
+    """the home cell first, then lexicographic, last index fastest"""
+    return [(i, j, k) for i in range(S[0]) for j in range(S[1]) for k in range(S[2])]
+
+
+def build_supercell(z, pos, cell, S):
+    """(z [N], pos [N,3], cell [3,3]): atom R n + j = home atom j + offset R"""
+    pos, cell = np.asarray(pos, dtype=np.float64), np.asarray(cell, dtype=np.float64)
+    zs, ps = [], []
+    for R in lattice_offsets(S):
+        shift = R[0] * cell[0] + R[1] * cell[1] + R[2] * cell[2]
+        for j in range(len(pos)):
+            zs.append(z[j])
+            ps.append(pos[j] + shift)
+    return np.array(zs), np.array(ps), np.array([S[k] * cell[k] for k in range(3)])
+
+
+def image_table(pos, cell, S):
+    """{(i, J): [x, ...]}: the nearest images r_J + T - r_i, T over the supercell lattice in {-1,0,1}^3 (lexicographic), ties at
+    relative 1e-8, each in units of the primitive lattice vectors"""
+    pos, cell = np.asarray(pos, dtype=np.float64), np.asarray(cell, dtype=np.float64)
+    inv = np.linalg.inv(cell)
+    n = len(pos)
+    out = {}
+    for i in range(n):
+        fi = pos[i] @ inv
+        for r, R in enumerate(lattice_offsets(S)):
+            for j in range(n):
+                fj = pos[j] @ inv + np.array(R, dtype=np.float64)
+                cands = []
+                for T in itertools.product((-1, 0, 1), repeat=3):
+                    x = fj - fi + np.array([T[0] * S[0], T[1] * S[1], T[2] * S[2]], dtype=np.float64)
+                    cands.append((np.linalg.norm(x @ cell), x))
+                dmin = min(c[0] for c in cands)
+                out[(i, r * n + j)] = [x for d, x in cands if d <= dmin * (1.0 + TIE_TOL)]
+    return out
+
+
+def dynamical_matrix(fc, pos, cell, S, masses, q, table=None, with_bound=False):
+    """D(q) complex128 [3n, 3n] = ((D0 + D0^H) / 2) with D0_ij = (m_i m_j)^-1/2 sum_J Phi(i, J) mean_T exp(2 pi i q . x).
+    with_bound: also the elementwise bound (n_terms + 8) eps32 sum |terms| of an fp32 assembly (recursive summation plus the
+    rounding of the phase factor, the product, the mass factor and the symmetrisation), averaged over (i, j) and (j, i) as D is."""
+    fc = np.asarray(fc, dtype=np.float64)
+    n, N = fc.shape[0], fc.shape[2]
+    table = image_table(pos, cell, S) if table is None else table
+    m = np.ones(n) if masses is None else np.asarray(masses, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64)
+    D = np.zeros((3 * n, 3 * n), dtype=np.complex128)
+    A = np.zeros((3 * n, 3 * n))
+    for i in range(n):
+        for J in range(N):
+            j = J % n
+            xs = table[(i, J)]
+            w = sum(np.exp(2j * np.pi * float(q @ x)) for x in xs) / len(xs)
+            f = 1.0 / np.sqrt(m[i] * m[j])
+            D[3 * i:3 * i + 3, 3 * j:3 * j + 3] += fc[i, :, J, :] * w * f
+            A[3 * i:3 * i + 3, 3 * j:3 * j + 3] += np.abs(fc[i, :, J, :]) * abs(w) * f
+    Dh = 0.5 * (D + D.conj().T)
+    if not with_bound:
+        return Dh
+    return Dh, (N // n + 8) * EPS32 * 0.5 * (A + A.T)
+
+
+def commensurate_q(S):
+    return np.array([(i / S[0], j / S[1], k / S[2]) for i in range(S[0]) for j in range(S[1]) for k in range(S[2])])
+
+
+def monkhorst_pack(n1, n2, n3, shift=False):
+    s = 0.5 if shift else 0.0
+    out = []
+    for i in range(n1):
+        for j in range(n2):
+            for k in range(n3):
+                u = np.array([(i + s) / n1, (j + s) / n2, (k + s) / n3])
+                out.append(u - np.floor(u + 0.5))
+    return np.array(out)
+
+
+def band_path(points, m, cell):
+    """(q, cumulative length in 1/A, ticks): m points per segment (start included) plus the last point"""
+    points = np.asarray(points, dtype=np.float64)
+    q = []
+    for k in range(len(points) - 1):
+        for s in range(m):
+            q.append(points[k] + (s / m) * (points[k + 1] - points[k]))
+    q.append(points[-1])
+    q = np.array(q)
+    recip = 2.0 * np.pi * np.linalg.inv(np.asarray(cell, dtype=np.float64)).T
+    length = [0.0]
+    for a, b in zip(q[:-1], q[1:]):
+        length.append(length[-1] + np.linalg.norm((b - a) @ recip))
+    return q, np.array(length), [m * k for k in range(len(points))]
+
+
+def thermochemistry(evals, T, threshold):
+    """dict(ZPE, U, S, F, Cv, n_zero, n_imag) per primitive cell of eigenvalues [Q, d] (eV / (A^2 amu)): the per-mode harmonic
+    formulas summed over the modes with lambda > threshold and divided by Q"""
+    ev = np.asarray(evals, dtype=np.float64)
+    Q = ev.shape[0]
+    live = ev > threshold
+    eps = EV_PER_SQRT_EIGENVALUE * np.sqrt(ev[live])
+    out = dict(n_imag=int((ev < -threshold).sum()), n_zero=int((~live & ~(ev < -threshold)).sum()), ZPE=0.5 * eps.sum() / Q)
+    if T == 0.0:
+        out.update(U=out['ZPE'], F=out['ZPE'], S=0.0, Cv=0.0)
+        return out
+    kT = K_BOLTZMANN * T
+    x = np.minimum(eps / kT, 100.0)
+    em, om = np.exp(-x), -np.expm1(-x)
+    out['U'] = out['ZPE'] + (eps * em / om).sum() / Q
+    out['S'] = K_BOLTZMANN * (x * em / om - np.log(om)).sum() / Q
+    out['F'] = out['ZPE'] + kT * np.log(om).sum() / Q
+    out['Cv'] = K_BOLTZMANN * (x * x * em / (om * om)).sum() / Q
+    return out
+
+
+# ---- synthetic crystals -------------------------------------------------------------------------------------------------------
+
+CUBIC_A, CUBIC_MASS, CUBIC_K, CUBIC_S = 2.5, 2.0, (3.0, 1.7, 0.9), (2, 3, 4)
+
+
+def cubic_lattice(S=CUBIC_S, K=CUBIC_K, a=CUBIC_A):
+    """Simple cubic, one atom, a spring K_c between neighbours along axis c acting on displacement component c only:
+    (fc [1,3,N,3], pos [1,3], cell [3,3]).  Phi(0, 0)_cc = 2 K_c, Phi(0, +-e_c)_cc = -K_c; with S_c = 2 both neighbours are the
+    same supercell atom (it gets -2 K_c and two equally near images), with S_c = 1 everything lands on the atom itself."""
+    offs = lattice_offsets(S)
+    fc = np.zeros((1, 3, len(offs), 3))
+    for c in range(3):
+        fc[0, c, 0, c] += 2.0 * K[c]
+        for sgn in (1, -1):
+            R = [0, 0, 0]
+            R[c] = sgn % S[c]
+            fc[0, c, offs.index(tuple(R)), c] -= K[c]
+    return fc, np.array([[0.1, 0.2, 0.3]]), a * np.eye(3)
+
+
+def cubic_omega2(q, K=CUBIC_K, m=CUBIC_MASS):
+    """sorted eigenvalues (2 K_c / m) (1 - cos 2 pi q_c)"""
+    return np.sort([(2.0 * K[c] / m) * (1.0 - np.cos(2.0 * np.pi * q[c])) for c in range(3)])
+
+
+TRICLINIC_CELL = np.array([[4.1, 0.0, 0.0], [0.7, 3.8, 0.0], [-0.5, 0.9, 4.4]])
+TRICLINIC_POS = np.array([[0.3, 0.2, 0.1], [1.9, 1.6, 2.3]])
+TRICLINIC_MASSES = np.array([12.011, 1.008])
+TRICLINIC_S = (3, 2, 3)
+
+
+def random_crystal(n, S, seed, scale=1.0):
+    """Random translation-invariant symmetric force constants of an n-atom cell on the supercell S: the full supercell matrix
+    H [N,3,N,3] with H[(R, i), (R', j)] = C(i, j, R' - R mod S), C(i, j, D)_ab = C(j, i, -D)_ba (no acoustic sum rule: the
+    spectrum has no zero modes).  Returns (H, fc = H[:n])."""
+    rng = np.random.default_rng(seed)
+    offs = lattice_offsets(S)
+    nR = len(offs)
+    C = rng.standard_normal((n, n, nR, 3, 3)) * scale
+
+    def neg(r):
+        R = offs[r]
+        return offs.index(((-R[0]) % S[0], (-R[1]) % S[1], (-R[2]) % S[2]))
+    Cs = np.zeros_like(C)
+    for i in range(n):
+        for j in range(n):
+            for r in range(nR):
+                Cs[i, j, r] = 0.5 * (C[i, j, r] + C[j, i, neg(r)].T)
+    N = n * nR
+    H = np.zeros((N, 3, N, 3))
+    for r1, R1 in enumerate(offs):
+        for r2, R2 in enumerate(offs):
+            d = offs.index(((R2[0] - R1[0]) % S[0], (R2[1] - R1[1]) % S[1], (R2[2] - R1[2]) % S[2]))
+            for i in range(n):
+                for j in range(n):
+                    H[r1 * n + i, :, r2 * n + j, :] = Cs[i, j, d]
+    return H, H[:n].copy()
+
+
+def supercell_eigenvalues(H, masses, nR):
+    """sorted eigenvalues of the supercell's mass-weighted matrix (masses of the primitive cell, repeated per copy)"""
+    return np.linalg.eigvalsh(vr.mass_weighted(H, np.tile(np.asarray(masses, dtype=np.float64), nR)))
