@@ -536,6 +536,58 @@ int nnhip_node_bwd(const float* g_top, const float* h_top, const float* W2T, con
                    int32_t accumulate_ga, const float* f, const float* q, const float* G_f, const float* WuT, float* gf,
                    int32_t n_atoms, int32_t activation, void* stream);
 
+/* The same two stages, their fused turn-around and their tangent forms in every form the pipelines launch.
+ *   nnhip_node_images   split-f16 images (nnhip_weight_images) of Wu, W0, W2 and of their transposes; NULL member = absent.
+ *   images == NULL      (node_fwd_ex / node_bwd_ex only) the fp32 kernels, any activation: what nnhip_node_fwd / _bwd run.
+ *   images != NULL      the split-f16 kernels: SiLU only; the products read the IMAGES, and the fp32 weight pointers only say which
+ *                       part runs (W0: next message_nodepart / head; W2T: MLP adjoint; WuT: update adjoint) and may be any non-NULL.
+ *   node_bwd_ex         T [N][F] (may be NULL, images only): receives t = g_top W2 before the act' factor; g_a_in (may be NULL, images
+ *                       only): with accumulate_ga the running g_a is read from it instead of from g_a.  q == NULL with WuT: q is
+ *                       formed again from f and images->Wu (refused without that image).
+ *   node_turn           node_fwd into the head, the head tail ( atom_energy = (<silu(e2), w4> + b4) scale[z] + shift[z],
+ *                       g_e2 = scale w4 silu'(e2) ), the head adjoint and the update adjoint with G_f = 0, in one launch; all six
+ *                       images; scale / shift may be NULL (1 / 0).  Outputs a_out, atom_energy [N], g_a, gf: the bits of
+ *                       nnhip_node_fwd_ex -> nnhip_head_out -> nnhip_node_bwd_ex.
+ *   node_tan_fwd        dq_k = df_k Wu^T; da_out = da_mid + sum_k (df_k q_k + f_k dq_k); T = da_out W0^T; Y = (T silu'(hn)) W2^T
+ *   node_tan_bwd        part A (g_top != NULL): dT = g_top W2; G = dT silu'(h_top) + t2_top silu''(h_top) hd_top (t2 / hd NULL = 0);
+ *                       dga (+)= G W0.  Part B (f != NULL): gq_k = ga f_k; dgq_k = dga f_k + ga df_k;
+ *                       dgf_k = dgf_in,k + dga q_k + ga dq_k + dgq_k Wu  (dgf_in may be NULL).  Without part A dga is an input.
+ * Every entry point refuses (NNHIP_E_INVALID, nothing launched) a negative n_atoms, an activation out of range, a missing image or
+ * pointer of the chosen form; n_atoms == 0 returns NNHIP_OK. */
+typedef struct {
+  const void* Wu; const void* W0; const void* W2;
+  const void* W2T; const void* W0T; const void* WuT;
+} nnhip_node_images;
+int nnhip_node_fwd_ex(const float* f, const float* a_mid, const float* Wu, float* q, float* a_out, const float* W0,
+                      const float* b0, const float* W2, const float* b2, float* hn, float* m, int32_t n_atoms,
+                      int32_t activation, const nnhip_node_images* images, void* stream);
+int nnhip_node_bwd_ex(const float* g_top, const float* h_top, const float* W2T, const float* W0T, float* g_a,
+                      int32_t accumulate_ga, const float* f, const float* q, const float* G_f, const float* WuT, float* gf,
+                      float* T, const float* g_a_in, int32_t n_atoms, int32_t activation, const nnhip_node_images* images,
+                      void* stream);
+int nnhip_node_turn(const float* f, const float* a_mid, float* a_out, const float* b0, const float* b2, const float* w4,
+                    const float* b4, const float* scale, const float* shift, const int64_t* z, float* atom_energy, float* g_a,
+                    float* gf, int32_t n_atoms, const nnhip_node_images* images, void* stream);
+int nnhip_node_tan_fwd(const float* df, const float* f, const float* q, const float* da_mid, const float* hn, float* dq,
+                       float* da_out, float* T, float* Y, int32_t n_atoms, const nnhip_node_images* images, void* stream);
+int nnhip_node_tan_bwd(const float* g_top, const float* h_top, const float* t2_top, const float* hd_top, float* G, float* dga,
+                       int32_t accumulate_dga, const float* ga, const float* f, const float* df, const float* q, const float* dq,
+                       const float* dgf_in, float* gq, float* dgq, float* dgf, int32_t n_atoms, const nnhip_node_images* images,
+                       void* stream);
+
+/* LayerNorm over the F features of atom_node (eps 1e-5), one wave per row, and its adjoint and tangents:
+ *   fwd      in place: xhat = (x - mean) rstd, rstd = 1 / sqrt(var + eps) ([N]); a = xhat gamma + beta
+ *   bwd      in place: g_a = rstd (g' - mean(g') - xhat mean(g' xhat)),  g' = g_a gamma
+ *   tan_fwd  in place: s = mean(xhat dx); dxhat = rstd (dx - mean(dx) - xhat s); drstd = -rstd^2 s ([N]); da = gamma dxhat
+ *   tan_bwd  in place on dga (in dg_y, out dg_x = drstd A + rstd dA, A as in bwd, dA its tangent); row_w = dg_y xhat + g_y dxhat;
+ *            row_b = dg_y  (the rows whose column sums are the tangent parts of dL/dgamma, dL/dbeta) */
+int nnhip_layer_norm_fwd(float* a, const float* gamma, const float* beta, int32_t n_atoms, float* xhat, float* rstd, void* stream);
+int nnhip_layer_norm_bwd(float* g_a, const float* gamma, const float* xhat, const float* rstd, int32_t n_atoms, void* stream);
+int nnhip_layer_norm_tan_fwd(float* da, const float* xhat, const float* rstd, const float* gamma, int32_t n_atoms, float* dxhat,
+                             float* drstd, void* stream);
+int nnhip_layer_norm_tan_bwd(const float* gy, float* dga, const float* xhat, const float* rstd, const float* dxhat,
+                             const float* drstd, const float* gamma, int32_t n_atoms, float* row_w, float* row_b, void* stream);
+
 /* Energy head tail (output.py:98-100 last linear, scalers.py:55-58, output.py:246) and the reverse seed:
  *   atom_energy[i] = (<act(e2_i), w4> + b4) scale[z_i] + shift[z_i];  energy[b] = sum;  g_e2[i] = scale w4 act'(e2)  (may be NULL) */
 int nnhip_head_out(const float* e2, const float* w4, const float* b4, const float* scale, const float* shift,

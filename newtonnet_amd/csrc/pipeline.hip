@@ -1233,27 +1233,116 @@ extern "C" int nnhip_head_out_ex(const float* e2, const float* w4, const float* 
   return launch_head_out(e2, w4, b4, scale, shift, z, mol_ptr, n_atoms, n_mol, activation, atom_energy, g_e2, energy,
                          (hipStream_t)stream, opts->small_molecules != 0);
 }
-extern "C" int nnhip_node_fwd(const float* f, const float* a_mid, const float* Wu, float* q, float* a_out, const float* W0,
-                              const float* b0, const float* W2, const float* b2, float* hn, float* m, int32_t n_atoms,
-                              int32_t activation, void* stream) {
+// ---- the row-local node stages one by one (header: nnhip_node_images).  images == NULL: the fp32 kernels of node128.hip; images
+// given: the split-f16 kernels of node128s.hip, where the fp32 weight pointers only say which parts run
+static NodeImages node_images(const nnhip_node_images* im) {
+  NodeImages r;
+  memset(&r, 0, sizeof(r));
+  if (im) {
+    r.Wu = (const char*)im->Wu; r.W0 = (const char*)im->W0; r.W2 = (const char*)im->W2;
+    r.W2T = (const char*)im->W2T; r.W0T = (const char*)im->W0T; r.WuT = (const char*)im->WuT;
+  }
+  return r;
+}
+extern "C" int nnhip_node_fwd_ex(const float* f, const float* a_mid, const float* Wu, float* q, float* a_out, const float* W0,
+                                 const float* b0, const float* W2, const float* b2, float* hn, float* m, int32_t n_atoms,
+                                 int32_t activation, const nnhip_node_images* images, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && activation >= NNHIP_ACT_SILU && activation <= NNHIP_ACT_SSP, "nnhip_node_fwd");
+  ARG_CHECK(!images || (activation == NNHIP_ACT_SILU && images->Wu && (!W0 || (images->W0 && images->W2))), "nnhip_node_fwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(f && a_mid && a_out && (images || Wu) && (!W0 || (b0 && b2 && hn && m && (images || W2))), "nnhip_node_fwd");
   NodeFwdArgs na;
   memset(&na, 0, sizeof(na));
   na.f = f; na.a_mid = a_mid; na.Wu = Wu; na.q = q; na.a_out = a_out;
   na.W0 = W0; na.b0 = b0; na.W2 = W2; na.b2 = b2; na.hn = hn; na.m = m;
   na.N = n_atoms;
   na.act = activation;
-  return launch_node_fwd(na, (hipStream_t)stream);
+  return images ? launch_node_fwd_split(na, node_images(images), (hipStream_t)stream) : launch_node_fwd(na, (hipStream_t)stream);
+}
+extern "C" int nnhip_node_fwd(const float* f, const float* a_mid, const float* Wu, float* q, float* a_out, const float* W0,
+                              const float* b0, const float* W2, const float* b2, float* hn, float* m, int32_t n_atoms,
+                              int32_t activation, void* stream) {
+  return nnhip_node_fwd_ex(f, a_mid, Wu, q, a_out, W0, b0, W2, b2, hn, m, n_atoms, activation, nullptr, stream);
+}
+extern "C" int nnhip_node_bwd_ex(const float* g_top, const float* h_top, const float* W2T, const float* W0T, float* g_a,
+                                 int32_t accumulate_ga, const float* f, const float* q, const float* G_f, const float* WuT,
+                                 float* gf, float* T, const float* g_a_in, int32_t n_atoms, int32_t activation,
+                                 const nnhip_node_images* images, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && activation >= NNHIP_ACT_SILU && activation <= NNHIP_ACT_SSP, "nnhip_node_bwd");
+  ARG_CHECK(images || (!T && !g_a_in), "nnhip_node_bwd");            // (the training members belong to the split-f16 kernel)
+  ARG_CHECK(!images || (activation == NNHIP_ACT_SILU && (!W2T || (images->W2T && images->W0T)) && (!WuT || images->WuT)),
+            "nnhip_node_bwd");
+  ARG_CHECK(!WuT || q || (images && images->Wu), "nnhip_node_bwd");  // no q: it is formed again, from the image of W_u
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(g_a && (!W2T || (g_top && h_top && (images || W0T))) && (!WuT || (f && gf)), "nnhip_node_bwd");
+  NodeBwdArgs nb;
+  memset(&nb, 0, sizeof(nb));
+  nb.g_top = g_top; nb.h_top = h_top; nb.W2T = W2T; nb.W0T = W0T; nb.g_a = g_a; nb.acc_ga = accumulate_ga;
+  nb.f = f; nb.q = q; nb.G_f = G_f; nb.WuT = WuT; nb.gf = gf; nb.T = T; nb.g_a_in = g_a_in;
+  nb.N = n_atoms;
+  nb.act = activation;
+  return images ? launch_node_bwd_split(nb, node_images(images), (hipStream_t)stream) : launch_node_bwd(nb, (hipStream_t)stream);
 }
 extern "C" int nnhip_node_bwd(const float* g_top, const float* h_top, const float* W2T, const float* W0T, float* g_a,
                               int32_t accumulate_ga, const float* f, const float* q, const float* G_f, const float* WuT,
                               float* gf, int32_t n_atoms, int32_t activation, void* stream) {
-  NodeBwdArgs nb;
-  memset(&nb, 0, sizeof(nb));
-  nb.g_top = g_top; nb.h_top = h_top; nb.W2T = W2T; nb.W0T = W0T; nb.g_a = g_a; nb.acc_ga = accumulate_ga;
-  nb.f = f; nb.q = q; nb.G_f = G_f; nb.WuT = WuT; nb.gf = gf;
-  nb.N = n_atoms;
-  nb.act = activation;
-  return launch_node_bwd(nb, (hipStream_t)stream);
+  return nnhip_node_bwd_ex(g_top, h_top, W2T, W0T, g_a, accumulate_ga, f, q, G_f, WuT, gf, nullptr, nullptr, n_atoms, activation,
+                           nullptr, stream);
+}
+extern "C" int nnhip_node_turn(const float* f, const float* a_mid, float* a_out, const float* b0, const float* b2, const float* w4,
+                               const float* b4, const float* scale, const float* shift, const int64_t* z, float* atom_energy,
+                               float* g_a, float* gf, int32_t n_atoms, const nnhip_node_images* images, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && images && images->Wu && images->W0 && images->W2 && images->W2T && images->W0T && images->WuT,
+            "nnhip_node_turn");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(f && a_mid && a_out && b0 && b2 && w4 && b4 && z && atom_energy && g_a && gf, "nnhip_node_turn");
+  NodeTurnArgs nt;
+  memset(&nt, 0, sizeof(nt));
+  nt.f = f; nt.a_mid = a_mid; nt.a_out = a_out; nt.b0 = b0; nt.b2 = b2; nt.w4 = w4; nt.b4 = b4;
+  nt.scale = scale; nt.shift = shift; nt.z = z; nt.atom_energy = atom_energy; nt.g_a = g_a; nt.gf = gf;
+  nt.N = n_atoms;
+  return launch_node_turn_split(nt, node_images(images), (hipStream_t)stream);
+}
+extern "C" int nnhip_node_tan_fwd(const float* df, const float* f, const float* q, const float* da_mid, const float* hn, float* dq,
+                                  float* da_out, float* T, float* Y, int32_t n_atoms, const nnhip_node_images* images,
+                                  void* stream) {
+  ARG_CHECK(n_atoms >= 0 && images && images->Wu && images->W0 && images->W2, "nnhip_node_tan_fwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(df && f && q && da_mid && hn && dq && da_out && T && Y, "nnhip_node_tan_fwd");
+  NodeTanFwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.df = df; a.f = f; a.q = q; a.da_mid = da_mid; a.hn = hn; a.dq = dq; a.da_out = da_out; a.T = T; a.Y = Y;
+  a.N = n_atoms;
+  return launch_node_tan_fwd_split(a, node_images(images), (hipStream_t)stream);
+}
+extern "C" int nnhip_node_tan_bwd(const float* g_top, const float* h_top, const float* t2_top, const float* hd_top, float* G,
+                                  float* dga, int32_t accumulate_dga, const float* ga, const float* f, const float* df,
+                                  const float* q, const float* dq, const float* dgf_in, float* gq, float* dgq, float* dgf,
+                                  int32_t n_atoms, const nnhip_node_images* images, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && images && (!g_top || (images->W2T && images->W0T)) && (!f || images->WuT), "nnhip_node_tan_bwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(dga && (!g_top || (h_top && G && (!t2_top == !hd_top))) && (!f || (ga && df && q && dq && gq && dgq && dgf)),
+            "nnhip_node_tan_bwd");
+  NodeTanBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g_top = g_top; a.h_top = h_top; a.t2_top = t2_top; a.hd_top = hd_top; a.G = G; a.dga = dga; a.acc_dga = accumulate_dga;
+  a.ga = ga; a.f = f; a.df = df; a.q = q; a.dq = dq; a.dgf_in = dgf_in; a.gq = gq; a.dgq = dgq; a.dgf = dgf;
+  a.N = n_atoms;
+  return launch_node_tan_bwd_split(a, node_images(images), (hipStream_t)stream);
+}
+extern "C" int nnhip_layer_norm_fwd(float* a, const float* gamma, const float* beta, int32_t n_atoms, float* xhat, float* rstd,
+                                    void* stream) {
+  ARG_CHECK(n_atoms >= 0, "nnhip_layer_norm_fwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(a && gamma && beta && xhat && rstd, "nnhip_layer_norm_fwd");
+  return launch_layer_norm_fwd(a, gamma, beta, n_atoms, xhat, rstd, (hipStream_t)stream);
+}
+extern "C" int nnhip_layer_norm_bwd(float* g_a, const float* gamma, const float* xhat, const float* rstd, int32_t n_atoms,
+                                    void* stream) {
+  ARG_CHECK(n_atoms >= 0, "nnhip_layer_norm_bwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(g_a && gamma && xhat && rstd, "nnhip_layer_norm_bwd");
+  return launch_layer_norm_bwd(g_a, gamma, xhat, rstd, n_atoms, (hipStream_t)stream);
 }
 extern "C" int nnhip_head_out(const float* e2, const float* w4, const float* b4, const float* scale, const float* shift,
                               const int64_t* z, const int32_t* mol_ptr, int32_t n_atoms, int32_t n_mol, int32_t activation,

@@ -1520,6 +1520,23 @@ extern "C" int nnhip_head_seed_tan(const float* e2, const float* de2, const floa
   return NNHIP_OK;
 }
 
+extern "C" int nnhip_layer_norm_tan_fwd(float* da, const float* xhat, const float* rstd, const float* gamma, int32_t n_atoms,
+                                        float* dxhat, float* drstd, void* stream) {
+  ARG_CHECK(n_atoms >= 0, "nnhip_layer_norm_tan_fwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(da && xhat && rstd && gamma && dxhat && drstd, "nnhip_layer_norm_tan_fwd");
+  return launch_layer_norm_tan_fwd(da, xhat, rstd, gamma, n_atoms, dxhat, drstd, (hipStream_t)stream);
+}
+
+extern "C" int nnhip_layer_norm_tan_bwd(const float* gy, float* dga, const float* xhat, const float* rstd, const float* dxhat,
+                                        const float* drstd, const float* gamma, int32_t n_atoms, float* row_w, float* row_b,
+                                        void* stream) {
+  ARG_CHECK(n_atoms >= 0, "nnhip_layer_norm_tan_bwd");
+  if (n_atoms == 0) return NNHIP_OK;
+  ARG_CHECK(gy && dga && xhat && rstd && dxhat && drstd && gamma && row_w && row_b, "nnhip_layer_norm_tan_bwd");
+  return launch_layer_norm_tan_bwd(gy, dga, xhat, rstd, dxhat, drstd, gamma, n_atoms, row_w, row_b, (hipStream_t)stream);
+}
+
 extern "C" int nnhip_pair_rbf(const float* rbf, const float* drbf, const float* tgeo, const int64_t* edge_index,
                               const int32_t* pid, int32_t n_edges, int32_t n_basis, float* rb, void* stream) {
   ARG_CHECK(n_edges >= 0 && n_basis >= 1 && n_basis <= NNHIP_MAX_NB && (n_edges == 0 || (rbf && drbf && tgeo && edge_index &&
