@@ -1674,6 +1674,39 @@ int nnhip_phonon_dos(const float* values, const int64_t* val_ptr, int32_t n_cry,
                      int32_t* counts, float* density, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Analytic elastic constants of crystals.  The kernels, nnhip_elastic_fold and nnhip_elastic_relax are in csrc/elastic.hip;
+ * nnhip_strain_vp is implemented in csrc/train_step.hip, next to the static tangent sweeps it drives.
+ *   nnhip_strain_vp: the tangent-over-reverse pass of nnhip_hessian_vp seeded with a homogeneous strain instead of a position
+ *     direction.  eta6 [n_mol][6] (device): the strain of every system of the batch in Voigt components with engineering shears,
+ *     eps = [[e1, e6/2, e5/2], [e6/2, e2, e4/2], [e5/2, e4/2, e3]]; x -> (1 + eps) x moves every displacement vector of the graph by
+ *     dd_e = eps d_e (periodic shifts included).  dgrad [N][3] = d(dE/dpos)/d eps along eta; d2 [n_mol][6]: d2[b][I] =
+ *     d/d eta (dE/d e_I) = sum_ab (d eps_ab / d e_I) sum_e dg_d[e]_a d_e,b over the edges of system b (fp64 sums, fixed order).
+ *     Needs what nnhip_hessian_vp needs (a prior nnhip_train_values on train_ws, train_ws->bf16_wgrad == 0) plus train_ws->batch
+ *     and train_ws->mol_ptr.  The six unit strains give the clamped-ion (Born) matrix d^2E/de_I de_J column by column.
+ *   nnhip_elastic_fold: Phi0[i a][j b] = sum over the supercell copies J of j of fc[i][a][J][b], then (Phi0 + Phi0^T) / 2: the force
+ *     constants at Gamma of every crystal, from fc / fc_ptr / cry_ptr / sc_atoms as nnhip_phonon_bands takes them, written as
+ *     [n_b][3][n_b][3] at phi0 + out_ptr[b] (out_ptr[b] = sum of 9 n_b'^2 before b: the blocks of nnhip_eig_blocks).  status [n_cry]:
+ *     0, or NNHIP_ELASTIC_STATUS_SIZE where sc_atoms[b] is no multiple of the crystal's atoms (nothing of that crystal is written).
+ *   nnhip_elastic_relax: R_IJ = sum_m (q_m . Lambda_I)(q_m . Lambda_J) / lambda_m of every crystal, one wave each, over the
+ *     eigenpairs of Phi0 (evals [3 n] at 3 cry_ptr[b], modes at blk_ptr[b] with ROW m = mode m, as nnhip_eig_blocks writes them with
+ *     unit masses) with |lambda_m| > threshold[b], ascending in lambda, fp64 sums.  lambda [3 n][6]: d(dE/dpos)/d e_I of the home
+ *     atoms.  relax [n_cry][6][6] (symmetric).  n_zero / n_negative [n_cry]: modes left out / below -threshold; status [n_cry]:
+ *     NNHIP_ELASTIC_STATUS_ZERO = n_zero != 3, NNHIP_ELASTIC_STATUS_NEGATIVE = a negative mode entered the sum (the geometry is no
+ *     minimum: R is the formula's value, not a physical relaxation).
+ * No float atomics, one writer per output: bitwise repeatable.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_ELASTIC_STATUS_ZERO 1
+#define NNHIP_ELASTIC_STATUS_NEGATIVE 2
+#define NNHIP_ELASTIC_STATUS_SIZE 8
+int nnhip_strain_vp(const nnhip_model* model, const nnhip_train_ws* train_ws, const nnhip_hvp_ws* hvp_ws, const float* eta6,
+                    float* dgrad, float* d2, void* stream);
+int nnhip_elastic_fold(const float* fc, const int64_t* fc_ptr, const int32_t* cry_ptr, const int32_t* sc_atoms,
+                       const int64_t* out_ptr, int32_t n_cry, float* phi0, int32_t* status, void* stream);
+int nnhip_elastic_relax(const float* evals, const float* modes, const int64_t* blk_ptr, const int32_t* cry_ptr, const float* lambda,
+                        const float* threshold, int32_t n_cry, float* relax, int32_t* n_zero, int32_t* n_negative, int32_t* status,
+                        void* stream);
+
+/* --------------------------------------------------------------------------
  * Timing hook for bench.py: wraps the kernels of one nnhip_energy_forces call
  * in HIP events on `stream` and accumulates per-kernel-class milliseconds.
  * classes: 0 = edge kernels (message/force fwd+adjoint), 1 = all dense MFMA kernels, 2 = everything else,

@@ -374,15 +374,16 @@ struct LayerHook {
   int (*fn)(const nnhip_model* model, const nnhip_train_ws* w, const void* ctx, int l, void* s);
   const void* ctx;
 };
-static int tangent_sweeps(const nnhip_model* model, const nnhip_train_ws* w, const float* v, float sign, const float* g_energy,
-                          const float* seed_a, const float* seed_f, const LayerHook* layer_hook, void* s) {
+// The sweeps read the direction through w->tgeo alone: tangent_sweeps_seeded runs them on the edge tangent the caller left there
+// (the strain seed of csrc/elastic.hip), tangent_sweeps writes the position seed first.
+static int tangent_sweeps_seeded(const nnhip_model* model, const nnhip_train_ws* w, const float* g_energy, const float* seed_a,
+                                 const float* seed_f, const LayerHook* layer_hook, void* s) {
   const int N = w->n_atoms, E = w->n_edges, L = w->n_layers, P = E / 2, act = model->activation;
   const bool img_on = train_images(model, w);
   const bool ln = has_ln(model);
   const bool node_img = img_on && !ln;
   const bool bf = train_bf16(model, w);
-  // ---- sweep 3: tangent forward along sign * v (training: v = dL/dF, sign = -1)
-  TS_TRY(nnhip_edge_tangent_geom(v, sign, w->edge_index, w->geo, E, model->cutoff, w->tgeo, s));
+  // ---- sweep 3: tangent forward along the edge tangent in w->tgeo
   for (int l = 0; l < L; ++l) {
     const nnhip_layer_params& lp = model->layer[l];
     const bool first = l == 0;
@@ -543,6 +544,13 @@ static int tangent_sweeps(const nnhip_model* model, const nnhip_train_ws* w, con
   return NNHIP_OK;
 }
 
+static int tangent_sweeps(const nnhip_model* model, const nnhip_train_ws* w, const float* v, float sign, const float* g_energy,
+                          const float* seed_a, const float* seed_f, const LayerHook* layer_hook, void* s) {
+  // the seed along sign * v (training: v = dL/dF, sign = -1)
+  TS_TRY(nnhip_edge_tangent_geom(v, sign, w->edge_index, w->geo, w->n_edges, model->cutoff, w->tgeo, s));
+  return tangent_sweeps_seeded(model, w, g_energy, seed_a, seed_f, layer_hook, s);
+}
+
 extern "C" int nnhip_train_grads_seeded(const nnhip_model* model, const nnhip_train_ws* w, const float* g_energy,
                                         const float* g_forces, const float* seed_a, const float* seed_f, void* s) {
   TS_TRY(check(model, w, "nnhip_train_grads"));
@@ -612,6 +620,28 @@ extern "C" int nnhip_hessian_vp(const nnhip_model* model, const nnhip_train_ws* 
   }
   if (w->n_atoms == 0) return NNHIP_OK;
   return hvp_run(model, w, h, v, hv, s);
+}
+
+// ---- strain tangent pass (include/newtonnet_hip.h, nnhip_strain_vp; the seed and the strain sum: csrc/elastic.hip)
+int launch_strain_tan_geom(const int64_t* edge_index, const int64_t* batch, const float* geo, const float* eta6, int n_edges,
+                           float cutoff, float* tgeo, hipStream_t s);
+int launch_strain_born(const float* dg_d, const float* geo, const int* row_ptr, const int* mol_ptr, int n_mol, float* d2,
+                       hipStream_t s);
+
+extern "C" int nnhip_strain_vp(const nnhip_model* model, const nnhip_train_ws* w, const nnhip_hvp_ws* h, const float* eta6,
+                               float* dgrad, float* d2, void* s) {
+  TS_TRY(hvp_check(model, w, h, "nnhip_strain_vp"));
+  if (!eta6 || !dgrad || !d2 || !w->batch || !w->mol_ptr) {
+    nnhip_set_error("nnhip_strain_vp: bad arguments");
+    return NNHIP_E_INVALID;
+  }
+  if (w->n_atoms == 0) return NNHIP_OK;
+  TS_TRY(launch_strain_tan_geom(w->edge_index, w->batch, w->geo, eta6, w->n_edges, model->cutoff, w->tgeo, (hipStream_t)s));
+  const LayerHook hook = {hvp_layer_stages, h};
+  TS_TRY(tangent_sweeps_seeded(model, w, h->zeros_b, nullptr, nullptr, &hook, s));
+  TS_TRY(launch_hvp_out(w->g_x, w->g_u, h->dg_x, h->dg_u, w->geo, w->tgeo, w->row_ptr, w->rev, w->n_atoms, w->n_edges, w->n_layers,
+                        model->cutoff, h->dg_d, dgrad, (hipStream_t)s));
+  return launch_strain_born(h->dg_d, w->geo, w->row_ptr, w->mol_ptr, w->n_mol, d2, (hipStream_t)s);
 }
 
 extern "C" int nnhip_hessian_blocks(const nnhip_model* model, const nnhip_train_ws* w, const nnhip_hvp_ws* h, int32_t n_dirs,

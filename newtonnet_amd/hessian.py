@@ -30,11 +30,15 @@ def _chk(rc, what):
         raise hip.HipLibraryError(f'{what} failed ({rc}): {hip.lib().nnhip_last_error().decode()}')
 
 
-def _validate(model, pos):
+def _validate_model(model):
     if model.training:
         raise NotImplementedError('Hessians run in eval mode only (training on Hessian labels is not supported): call model.eval()')
     if 'energy' not in list(model.output_properties):
         raise NotImplementedError("the Hessian is the energy's: the model needs the 'energy' head (output_properties)")
+
+
+def _validate(model, pos):
+    _validate_model(model)
     if not pos.is_cuda:
         raise RuntimeError('newtonnet_amd Hessians run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
 
@@ -92,6 +96,49 @@ def hessian_vector_product(model, z, pos, cell, batch, v) -> torch.Tensor:
     p = _Pass(model, z, pos, cell, batch, 1, None)
     _chk(hip.lib().nnhip_hessian_vp(p.model_c, p.ws_c, C.byref(p.h), vv.data_ptr(), out.data_ptr(), p.st), 'nnhip_hessian_vp')
     return out
+
+
+def voigt_strain(strain, n_mol: int) -> torch.Tensor:
+    """[B,6] Voigt components (e1, e2, e3, e4, e5, e6 with engineering shears: e4 = 2 eps_yz, e5 = 2 eps_xz, e6 = 2 eps_xy) of a
+    strain given as [B,6] or as symmetric [B,3,3] matrices (ValueError for a matrix that is not symmetric).  The symmetry check
+    reads the matrices on the host (18 numbers per system; a strain that lives on the device costs one copy), so that it needs no
+    device and raises before any kernel; the [B,6] form is taken as it is."""
+    s = strain.detach()
+    if tuple(s.shape) == (n_mol, 6):
+        return s
+    if tuple(s.shape) != (n_mol, 3, 3):
+        raise ValueError(f'strain: [{n_mol},3,3] symmetric matrices or [{n_mol},6] Voigt components expected (got {tuple(s.shape)})')
+    h = s.double().cpu()
+    if n_mol and float((h - h.transpose(1, 2)).abs().max()) > 1e-6 * max(float(h.abs().max()), 1e-30):
+        raise ValueError('strain: the matrices are not symmetric (a rotation is no strain); symmetrise them first')
+    return torch.stack([s[:, 0, 0], s[:, 1, 1], s[:, 2, 2], s[:, 1, 2] + s[:, 2, 1], s[:, 0, 2] + s[:, 2, 0], s[:, 0, 1] + s[:, 1, 0]],
+                       dim=1)
+
+
+def _strain_pass(p: '_Pass', eta6: torch.Tensor, dgrad: torch.Tensor, d2: torch.Tensor):
+    _chk(hip.lib().nnhip_strain_vp(p.model_c, p.ws_c, C.byref(p.h), eta6.data_ptr(), dgrad.data_ptr(), d2.data_ptr(), p.st),
+         'nnhip_strain_vp')
+
+
+def strain_vector_product(model, z, pos, cell, batch, strain) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dgrad [N,3], d2 [B,6]), fp32: the tangent of dE/dpos and of dE/d e_I (I = 1..6, Voigt with engineering shears) along a
+    homogeneous strain of every system, x -> (1 + eps_b) x with the cell following.  strain: [B,3,3] symmetric or [B,6] Voigt, of
+    any floating dtype and on any device (it is converted to fp32 on the device of pos).
+    One tangent-over-reverse pass seeded on the edges (dd_e = eps d_e, periodic shifts included), so it serves molecules
+    (cell = 0: the strain is the position direction v_i = eps pos_i) and periodic boxes alike."""
+    _validate_model(model)
+    n, n_mol = pos.shape[0], cell.shape[0]
+    if tuple(pos.shape) != (n, 3) or tuple(cell.shape) != (n_mol, 3, 3) or batch.numel() != n or z.numel() != n:
+        raise ValueError('z [N], pos [N,3], cell [B,3,3] and batch [N] expected')
+    eta = voigt_strain(strain, n_mol)
+    _validate(model, pos)
+    eta6 = eta.to(device=pos.device, dtype=torch.float32).contiguous()
+    dgrad = torch.zeros(n, 3, dtype=torch.float32, device=pos.device)
+    d2 = torch.zeros(n_mol, 6, dtype=torch.float32, device=pos.device)
+    if n == 0:
+        return dgrad, d2
+    _strain_pass(_Pass(model, z, pos, cell, batch, 1, None), eta6, dgrad, d2)
+    return dgrad, d2
 
 
 def replicas_for(n_atoms: int, n_dirs: int) -> int:

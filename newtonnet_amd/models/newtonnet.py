@@ -735,6 +735,26 @@ class NewtonNet(nn.Module):
         with torch.no_grad():
             return _h.hessian_vector_product(self, z, pos, cell, batch, v)
 
+    def strain_vector_product(self, z, pos, cell, batch, strain):
+        """(dgrad [N,3], d2 [B,6]) fp32: the tangents of dE/dpos and of dE/d e_I (Voigt, engineering shears) along a homogeneous
+        strain of every system, `strain` [B,3,3] symmetric or [B,6] Voigt -- one tangent-over-reverse pass seeded on the edges
+        (newtonnet_amd/hessian.py, csrc/elastic.hip).  Molecules and periodic boxes alike; eval mode, 'energy' head."""
+        from newtonnet_amd import hessian as _h
+        with torch.no_grad():
+            return _h.strain_vector_product(self, z, pos, cell, batch, strain)
+
+    def elastic_constants(self, z, pos, cell, batch, supercell=(1, 1, 1), relaxed: bool = True, phonons=None, tol_zero=None,
+                          replicas=None):
+        """Analytic elastic constants C_IJ = (1 / V) d^2E / de_I de_J (eV / A^3) of B crystals as a newtonnet_amd.elastic
+        .ElasticConstants: the clamped-ion (Born) tensor from six strain tangent passes on a supercell (checked as phonons()
+        checks it), and with relaxed=True the relaxed-ion correction Lambda^T pinv(Phi0) Lambda / V from the force constants at
+        Gamma (`phonons`: a Phonons of this call's crystals and supercell; None computes one), which assumes zero forces and
+        serves primitive cells of up to elastic.max_dim() / 3 = 32 atoms.  Its helpers give GPa, compliance, Voigt / Reuss / Hill
+        moduli and the stability eigenvalue.  Eval mode only; needs the 'energy' head; uses the current parameters."""
+        from newtonnet_amd import elastic as _e
+        return _e.elastic_constants(self, z, pos, cell, batch, supercell=supercell, relaxed=relaxed, phonons=phonons,
+                                    tol_zero=tol_zero, replicas=replicas)
+
     def normal_modes(self, z, pos, cell, batch, masses=None, project: bool = True, modes: bool = True, tol_zero=None,
                      solver: str = 'lds'):
         """Harmonic normal-mode analysis of every molecule of the batch: the Hessian blocks of hessian() diagonalised on the

@@ -490,6 +490,31 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
     orthogonal must be given as a symmetric matrix (symmetric_cell rotates any crystal into that form): the model's minimum-image
     shift is a lattice vector for such cells only.  masses: fp32 [N] amu
     (None: standard atomic weights of z).  asr: impose the acoustic sum rule on the fp32 force constants."""
+    cells, S, counts = _checked_crystals(model, z, pos, cell, batch, supercell, _check_bound)
+    n_atoms = pos.shape[0]
+    if masses is not None and masses.numel() != n_atoms:
+        raise ValueError(f'masses: {masses.numel()} values for {n_atoms} atoms')
+    m = _v.table_masses(z) if masses is None else masses.detach().reshape(-1)
+    if not pos.is_cuda:
+        raise RuntimeError('newtonnet_amd phonons run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
+    dev = pos.device
+    z_sc, pos_sc, cell_sc, batch_sc, sc_counts = _supercell_batch(z, pos, cells, S, counts, dev)
+    with torch.no_grad():
+        blocks, blk_ptr, _ = _hessian.hessian_blocks_counts(model, z_sc, pos_sc, cell_sc, batch_sc, n_dirs=3 * max(counts))
+    ptr = blk_ptr.tolist()
+    parts = []
+    for b, (n, N) in enumerate(zip(counts, sc_counts)):
+        # block[J, beta, i, alpha] = d^2 E / d r_J,beta d r_i,alpha: the first 3 n columns are the home atoms'
+        phi = blocks[ptr[b]:ptr[b] + 9 * N * N].view(N, 3, N, 3)[:, :, :n, :].permute(2, 3, 0, 1).contiguous()
+        parts.append((acoustic_sum_rule(phi) if asr else phi).reshape(-1))
+    fc_t = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
+    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev)
+
+
+def _checked_crystals(model, z, pos, cell, batch, supercell, check_bound):
+    """The checks phonons() makes before any device work, shared with newtonnet_amd/elastic.py: (cells fp64 numpy [B,3,3],
+    supercells int [B,3], atoms per primitive cell).  check_bound(counts) (may be None) sits where phonons() refuses a primitive
+    cell above max_dim()."""
     _validate_model(model)
     n_atoms, B = pos.shape[0], cell.shape[0]
     if tuple(pos.shape) != (n_atoms, 3) or tuple(cell.shape) != (B, 3, 3) or batch.numel() != n_atoms or z.numel() != n_atoms:
@@ -503,7 +528,8 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
                              f'the crystal first: phonons.symmetric_cell(pos, cell)')
     S = _supercells(supercell, B)
     counts = _counts(batch, B, n_atoms)
-    _check_bound(counts)
+    if check_bound is not None:
+        check_bound(counts)
     cutoff = float(model.embedding_layers.edge_embedding.cutoff)
     for b in range(B):
         w = perpendicular_widths(cells[b]) * S[b]
@@ -511,17 +537,15 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
             raise ValueError(f'crystal {b}: the supercell {S[b].tolist()} has perpendicular widths '
                              f'{", ".join(f"{x:.3f}" for x in w)} A, below 2 x cutoff = {2.0 * cutoff:.3f} A (the neighbour list takes '
                              f'a single minimum image): enlarge the supercell')
-    if masses is not None and masses.numel() != n_atoms:
-        raise ValueError(f'masses: {masses.numel()} values for {n_atoms} atoms')
-    m = _v.table_masses(z) if masses is None else masses.detach().reshape(-1)
-    if not pos.is_cuda:
-        raise RuntimeError('newtonnet_amd phonons run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
-    dev = pos.device
-    # the supercells as one batch (host, fp64, rounded once to fp32)
+    return cells, S, counts
+
+
+def _supercell_batch(z, pos, cells, S, counts, dev):
+    """(z, pos, cell, batch, atoms per supercell): the supercells as one batch on `dev` (host, fp64, rounded once to fp32)"""
     pos_h, z_h = pos.detach().double().cpu().numpy(), z.detach().reshape(-1).cpu().numpy()
     off = np.concatenate([[0], np.cumsum(counts)])
     zs, ps, cs, bs = [], [], [], []
-    for b in range(B):
+    for b in range(len(counts)):
         zb, pb, cb = build_supercell(z_h[off[b]:off[b + 1]], pos_h[off[b]:off[b + 1]], cells[b], S[b])
         zs.append(zb)
         ps.append(pb)
@@ -532,13 +556,4 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
     pos_sc = torch.tensor(np.concatenate(ps), dtype=torch.float32, device=dev)
     cell_sc = torch.tensor(np.stack(cs), dtype=torch.float32, device=dev)
     batch_sc = torch.tensor(np.concatenate(bs), dtype=torch.long, device=dev)
-    with torch.no_grad():
-        blocks, blk_ptr, _ = _hessian.hessian_blocks_counts(model, z_sc, pos_sc, cell_sc, batch_sc, n_dirs=3 * max(counts))
-    ptr = blk_ptr.tolist()
-    parts = []
-    for b, (n, N) in enumerate(zip(counts, sc_counts)):
-        # block[J, beta, i, alpha] = d^2 E / d r_J,beta d r_i,alpha: the first 3 n columns are the home atoms'
-        phi = blocks[ptr[b]:ptr[b] + 9 * N * N].view(N, 3, N, 3)[:, :, :n, :].permute(2, 3, 0, 1).contiguous()
-        parts.append((acoustic_sum_rule(phi) if asr else phi).reshape(-1))
-    fc_t = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
-    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev)
+    return z_sc, pos_sc, cell_sc, batch_sc, sc_counts

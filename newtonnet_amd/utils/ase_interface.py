@@ -160,6 +160,15 @@ class MLAseCalculator(_Base):
                                   dtype=torch.float32, device=pos.device)
         return self.model.phonons(z, pos.float(), cell.float(), batch, supercell, masses=masses, asr=asr)
 
+    def elastic_constants(self, atoms_or_list, supercell, relaxed: bool = True):
+        """Elastic constants of one crystal or a list of crystals (NewtonNet.elastic_constants): a
+        newtonnet_amd.elastic.ElasticConstants over the primitive cells given (C in eV / A^3; .gpa() converts).  supercell:
+        three integers, or one triple per structure.  relaxed=True adds the relaxed-ion term (it assumes relaxed atoms).  The
+        structures may differ in size.  A method of its own: not a property of calculate()."""
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        z, pos, cell, batch = self.format_data(atoms)
+        return self.model.elastic_constants(z, pos.float(), cell.float(), batch, supercell, relaxed=relaxed)
+
     def sample(self, atoms, n_samples: int, temperature: float, quantum: bool = False, seed=None, solver: str = 'lds'):
         """n_samples geometries of one structure drawn from its harmonic distribution at `temperature` (K), as an
         [n_samples, n_atoms, 3] array in Angstrom (NewtonNet.sample_displacements: classical normal-mode sampling, or Wigner

@@ -24,6 +24,7 @@ PATTERNS = [
     (r'^remd_aspirin\.json$', 'tools/bench_remd.py: ms per step of replica-exchange MD, 128 ladders x 8 aspirin replicas and one ladder of 8, an attempt every 10 steps (ReplicaExchange.run / Dynamics.run on the same batch / us per attempt; medians of three runs, all kept)'),
     (r'^pimd_aspirin\.json$', 'tools/bench_pimd.py: ms per step of path-integral MD, 128 ring polymers x 8 aspirin beads and one ring polymer of 8 (PathIntegral.run / Dynamics.run on the same batch / Dynamics.run on the one molecule; medians of three runs, all kept)'),
     (r'^metad_aspirin\.json$', 'tools/bench_metad.py: ms per step of biased MD on collective variables, 1024 aspirin walkers (1 group of 1024, 128 groups of 8) and one group of 8, with 0 / 1e4 / 1e5 hills per group (Metadynamics.run / Dynamics.run on the same batch; medians of three runs, all kept)'),
+    (r'^elastic\.json$', 'tools/bench_elastic.py: 64 crystals of 8 atoms on 3 x 3 x 3 supercells; the six-strain Born step against six hessian_vector_product calls, six strain passes against six HVP passes on one prepared batch, the whole elastic_constants call (relaxed and clamped) against model.phonons alone; medians of three'),
     (r'bench.*\.json$', 'bench.py line, default command (config 2: 1024 aspirin conformers, 1 GPU)'),
     (r'bench_train\.txt$', 'tools/bench_train.py: training step times across batch shapes'),
     (r'box100k.*kernel_stats\.txt$', 'rocprofv3 --kernel-trace --stats summary of the 100k-atom box step'),
@@ -57,7 +58,7 @@ PATTERNS = [
 
 # records of the per-feature benchmark tools carry no tree of their own: they were taken on the change that added the kernel
 WITH_KERNEL = {'md_aspirin.json': 'md', 'relax_aspirin.json': 'relax', 'neb_aspirin.json': 'neb', 'remd_aspirin.json': 'remd',
-               'pimd_aspirin.json': 'pimd', 'metad_aspirin.json': 'bias'}
+               'pimd_aspirin.json': 'pimd', 'metad_aspirin.json': 'bias', 'elastic.json': 'elastic'}
 
 
 def tree_of(path):
