@@ -185,7 +185,21 @@ def _orthorhombic_box(cell: torch.Tensor, cutoff: float, cell_host=None):
         c = cell.reshape(3, 3).cpu()
     diag = torch.diagonal(c)
     ok = bool((c - torch.diag(diag) == 0).all()) and bool((diag >= 3.0003 * cutoff).all())
+    ok = ok and bool((diag <= 2.0 * CELL_LIST_MAX_COORD * cutoff).all())
     return tuple(float(v) for v in diag) if ok else None
+
+
+# The cell list bins fp32 coordinates in fp32, and its bins are only 1.0001 cutoffs wide: far from the origin the rounding of the
+# bin boundaries (and, across periodic images, of the pair predicate itself) eats that margin and a pair two bins apart can pass the
+# predicate -- a neighbor the all-pairs list has and the cell list would lose (first seen near 2500 cutoffs).  Up to 128 cutoffs
+# from the origin, in a box of at most 256 cutoffs, it cannot happen (tests/graph_ref.py); beyond that
+# range -- unwrapped coordinates of a long MD run -- the all-pairs builder serves the system.
+CELL_LIST_MAX_COORD = 128.0
+
+
+def _cell_list_in_range(pos: torch.Tensor, cutoff: float) -> bool:
+    """every |coordinate| <= CELL_LIST_MAX_COORD cutoffs (one 4-byte read-back, on the >= 2048-atom periodic path only)"""
+    return bool(pos.abs().max() <= CELL_LIST_MAX_COORD * cutoff)
 
 
 def build_graph(pos: torch.Tensor, cell: torch.Tensor, batch: torch.Tensor, cutoff: float,
@@ -223,7 +237,7 @@ def build_graph(pos: torch.Tensor, cell: torch.Tensor, batch: torch.Tensor, cuto
     box = None
     if B == 1 and N >= CELL_LIST_MIN_ATOMS:
         lengths = _orthorhombic_box(cell, cutoff, cell_host)
-        if lengths is not None:
+        if lengths is not None and _cell_list_in_range(pos, cutoff):
             box = (C.c_float * 3)(*lengths)
     if box is not None:
         scratch = torch.empty(L.nnhip_graph_cells_scratch_bytes(N, box, float(cutoff)), dtype=torch.uint8, device=dev)
