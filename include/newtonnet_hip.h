@@ -1119,6 +1119,32 @@ int nnhip_lbfgs_step(const float* pos_in, const float* force, const uint8_t* fre
                      int32_t* n_steps, int32_t* n_pairs, int32_t* head, float* S, float* Y, float* rho, float* f_prev, float* work,
                      float* pos_out, float* fmax_out, void* stream);
 
+/* The workgroup-per-system form of nnhip_lbfgs_step, for large systems: the same step, state, arguments, checks and refusals (work
+ * is mandatory when n_atoms > 64, as there), with ONE WORKGROUP of NNHIP_LBFGS_WG_THREADS = 1024 threads (16 waves) working on a
+ * system instead of one wave64.  wg_min_atoms routes each system on the device, from mol_ptr, without a host read:
+ *   wg_min_atoms <= 0   every system (empty ones included) is stepped by the workgroup kernel; the wave kernel is not launched
+ *   wg_min_atoms >  0   a system of n >= wg_min_atoms atoms is stepped by the workgroup kernel, a smaller one by the wave kernel of
+ *                       nnhip_lbfgs_step (and gets exactly the bits that call gives it); both kernels are launched on `stream`,
+ *                       they own disjoint systems and neither touches a word of the other's, so their order does not matter.  (A
+ *                       system whose atom offsets leave 0 .. n_atoms has no atom count: the wave kernel marks it, fmax_out = NaN.)
+ * The workgroup kernel: thread t owns the atoms t, t + 1024, ... of its system in every sweep; the two-loop work vector is three
+ * registers up to 1024 atoms, the thread's rows of `work` above.  A reduction is the thread-local sum (max) in atom order, the
+ * butterfly 32 .. 1 within each wave, the 16 wave results through LDS and one barrier, and a fixed pairwise fold
+ * (p[i] += p[i + d], d = 8, 4, 2, 1) that every thread does itself -- so a dot product over n atoms passes through
+ * 3 + ceil(n / 1024) + 6 + 4 roundings instead of 3 + ceil(n / 64) + 6.  No float atomics, no communication between workgroups: a
+ * system's outputs are bitwise independent of the rest of the batch and of its place in it, frozen systems keep their bits, refused
+ * calls write nothing -- every per-system property of nnhip_lbfgs_step.  Because the order of the reductions differs, THE BITS OF
+ * THE TWO FORMS DIFFER from each other above 64 atoms (up to 64, fifteen of the sixteen wave results are exact zeros and the bits
+ * are the wave form's; y and S[head], single rounded operations, are the same function of their inputs in both at every size);
+ * both satisfy the same fp64 restatement with their own depth.  One workgroup serves a system whatever its size; grid-stride over
+ * the systems with at most 2048 workgroups.
+ * Cost: about 2 m ceil(n / 1024) dependent sweeps of one workgroup, each reduction one barrier. */
+#define NNHIP_LBFGS_WG_THREADS 1024
+int nnhip_lbfgs_step_wg(const float* pos_in, const float* force, const uint8_t* free_mask, const int32_t* mol_ptr, int32_t n_mol,
+                        int32_t n_atoms, int32_t memory, float tol2, float alpha, float maxstep, int32_t wg_min_atoms, int32_t flags,
+                        int32_t* converged, int32_t* n_steps, int32_t* n_pairs, int32_t* head, float* S, float* Y, float* rho,
+                        float* f_prev, float* work, float* pos_out, float* fmax_out, void* stream);
+
 /* --------------------------------------------------------------------------
  * Variable-cell geometry relaxation on the device (csrc/cellrelax.hip): ONE launch on `stream` moves the atoms and the cell of
  * every periodic system of a batch by one L-BFGS step from the forces and the virial just evaluated.  The method is ASE's
@@ -1171,6 +1197,21 @@ int nnhip_cell_lbfgs_step(const float* x_in, const float* pos_in, const float* f
                           float maxstep, int32_t strain_mask, int32_t flags, int32_t* converged, int32_t* n_steps, int32_t* n_pairs,
                           int32_t* head, float* S, float* Y, float* rho, float* g_prev, float* work, float* G, float* x_out,
                           float* pos_out, float* cell_out, float* fmax_out, void* stream);
+
+/* The workgroup-per-system form of nnhip_cell_lbfgs_step: the same step, state, arguments, checks and refusals (work is mandatory
+ * when n_atoms + 3 n_mol > 64, as there), with one workgroup of NNHIP_LBFGS_WG_THREADS threads per system, as nnhip_lbfgs_step_wg
+ * has it.  wg_min_atoms routes a system by its ATOM count n (the chain walks n + 3 rows): <= 0 sends every system to the workgroup
+ * kernel alone; > 0 sends the systems of n >= wg_min_atoms atoms there and leaves the others to the wave kernel of
+ * nnhip_cell_lbfgs_step with exactly that call's bits.  Thread t owns the generalised rows t, t + 1024, ... of its system; the 3x3
+ * quantities of the prologue are formed by every thread from the same loads; the cell rows of G are stored by the threads that own
+ * them; the three new cell rows of x_out reach all threads through LDS and a barrier.  The work vector is in registers up to 1024
+ * rows.  The bits of the two forms differ from each other (the order of the reductions differs). */
+int nnhip_cell_lbfgs_step_wg(const float* x_in, const float* pos_in, const float* force, const float* virial, const float* cell_in,
+                             const float* h0, const uint8_t* free_mask, const int32_t* mol_ptr, const float* pressure,
+                             const float* cell_factor, int32_t n_mol, int32_t n_atoms, int32_t memory, float tol2, float alpha,
+                             float maxstep, int32_t strain_mask, int32_t wg_min_atoms, int32_t flags, int32_t* converged,
+                             int32_t* n_steps, int32_t* n_pairs, int32_t* head, float* S, float* Y, float* rho, float* g_prev,
+                             float* work, float* G, float* x_out, float* pos_out, float* cell_out, float* fmax_out, void* stream);
 
 /* --------------------------------------------------------------------------
  * Intrinsic-reaction-coordinate following on the device (csrc/irc.hip): ONE launch on `stream` moves every path of a batch by one

@@ -17,8 +17,11 @@ mask; constant_volume=True subtracts tr Wc / 3 from its diagonal.  A system has 
 and cell rows alike is below fmax (compared as squares in fp32) -- ASE's criterion under a filter.  A fixed atom has its row of G
 exactly 0: its reference-frame position q is frozen, so it RIDES WITH THE CELL (its Cartesian position changes when F does).
 
-Left out on purpose: Frechet / exponential cell filters; cell relaxation of bands, dimers and reaction paths; a
-workgroup-per-system form for one large box (the launch gives one wave64 to a system: relax.py's cost note, with n + 3 rows).
+`form` chooses the launch as for `Relaxation` (relax.py): 'wave' (the default) gives one wave64 to a system, 'workgroup' one
+workgroup of hip.LBFGS_WG_THREADS threads (nnhip_cell_lbfgs_step_wg; for one large box), 'auto' the workgroup form to the systems
+of at least wg_min_atoms ATOMS (the chain walks n + 3 rows) and the wave form to the others, decided on the device.
+
+Left out on purpose: Frechet / exponential cell filters; cell relaxation of bands, dimers and reaction paths.
 
 Units: positions in Angstrom, forces and fmax in eV / Angstrom, alpha in eV / Angstrom^2, pressure and stress in bar."""
 from __future__ import annotations
@@ -31,7 +34,7 @@ import torch
 from newtonnet_amd import hip
 from newtonnet_amd.dynamics import _mol_ptr
 from newtonnet_amd.npt import BAR, _per_system
-from newtonnet_amd.relax import check_arguments, check_inputs, check_run_arguments
+from newtonnet_amd.relax import check_arguments, check_form, check_inputs, check_run_arguments
 
 _TRAJ = ('traj_step', 'traj_pos', 'traj_cell', 'traj_force', 'traj_virial', 'traj_energy', 'traj_n_pairs')
 
@@ -100,15 +103,17 @@ class CellRelaxation:
     fmax and maxstep taken over the n + 3 generalised rows of a system.  pressure: bar, a number or [B].  mask, hydrostatic,
     constant_volume: the module docstring.  cell_factor: c; None = the system's atom count (ASE's default; 1 for an empty system).
     fixed: bool [N]; a fixed atom keeps its reference-frame position, so it rides with the cell.  Every system needs
-    det(cell) > 0 (checked once, at construction, with one host read).  Positions stay unwrapped."""
+    det(cell) > 0 (checked once, at construction, with one host read).  Positions stay unwrapped.  form, wg_min_atoms: as for
+    Relaxation ('wave', 'workgroup' or 'auto'; the threshold of 'auto' counts atoms)."""
 
     def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, pressure=0.0, mask=None,
-                 hydrostatic=False, constant_volume=False, cell_factor=None, fixed=None):
+                 hydrostatic=False, constant_volume=False, cell_factor=None, fixed=None, form='wave', wg_min_atoms=None):
         # ---- everything that can be refused without touching the device
         N, B = check_inputs(model, 'CellRelaxation', z, pos, cell, batch, fixed)
         props = check_model(model, 'CellRelaxation')
         fmax, memory, maxstep, alpha = check_arguments(fmax, memory, maxstep, alpha)
         P, bits, flags, cell_factor = check_cell_arguments(B, pressure, mask, hydrostatic, constant_volume, cell_factor)
+        self.form, self._wg_min_atoms = form, check_form(form, wg_min_atoms)
         if not pos.is_cuda:
             raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: move the model and the inputs to '
                                '"cuda"')
@@ -179,7 +184,7 @@ class CellRelaxation:
                             self._mol_ptr, self._p, self._c, self.memory, self._tol2, self._alpha, self._maxstep, self._bits,
                             self._flags | flags, self._converged, self._n_steps, self._n_pairs, self._head, self._S, self._Y,
                             self._rho, self._g_prev, self._work, self._G, self._x[other], self._pos[other], self._cells[other],
-                            self._fmax)
+                            self._fmax, wg_min_atoms=self._wg_min_atoms)
         self._cur = other
 
     def _ensure_state(self):

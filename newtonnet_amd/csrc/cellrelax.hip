@@ -33,6 +33,11 @@
 //   cell_out_ij = dot3 over k of h0_ik F'_jk                       (h0 F'^T)
 //   pos_out_aj  = dot3 over k of q_ak F'_jk                        (q_out F'^T; q_out = the atom rows of X_out)
 // tests/cellrelax_ref.py restates all of it in fp64 with one 2^-24 per operation.
+//
+// A second kernel, cell_lbfgs_step_wg_kernel (nnhip_cell_lbfgs_step_wg), gives a system one workgroup of NNHIP_LBFGS_WG_THREADS
+// threads: the same text (cell_system below) instantiated with lbfgs_chain::BlockTeam (lbfgs_chain.h has the method and the rules).
+// There thread t owns row t, t + 1024, ...; the cell rows of G are stored by their owners, and the epilogue's three cell rows of
+// X_out reach every thread through LDS and a barrier.
 #include "common.h"
 #include "lbfgs_chain.h"
 
@@ -69,12 +74,12 @@ struct CellRelaxArgs {
   float* fmax_out;
   float tol2, alpha, maxstep;
   int flags, strain_mask, n_mol, n_atoms, memory;
+  int wg_min_atoms;      // systems of at least this many atoms belong to cell_lbfgs_step_wg_kernel (<= 0: all)
 };
 
 using lbfgs_chain::dot3;
 using lbfgs_chain::load3;
 using lbfgs_chain::store3;
-using lbfgs_chain::wave_max;
 
 __device__ __forceinline__ void cross3(const float* u, const float* v, float* c) {
   c[0] = __fmaf_rn(u[1], v[2], -__fmul_rn(u[2], v[1]));
@@ -116,194 +121,237 @@ struct CellPolicy {
   __device__ __forceinline__ void store_x(size_t o, const float* x_out, const float*) const { store3(g.x_out, o, x_out); }
 };
 
-__global__ void __launch_bounds__(CR_THREADS)
-cell_lbfgs_step_kernel(CellRelaxArgs g) {
-  const int lane = threadIdx.x & 63;
-  const int waves = CR_THREADS / 64;
+// one system of a launch, by the team that owns it (relax.hip's relax_system, with the prologue and the epilogue of the cell).
+// Every branch is taken on values all members of the team loaded from the same address or formed from such loads, or on a reduced
+// value (the reductions of BlockTeam hold barriers); the state words are loaded before the first reduction, and member 0 stores
+// them after it (converged) or after the reductions of the step (n_steps, n_pairs, head)
+template <class Team>
+__device__ __forceinline__ void cell_system(const CellRelaxArgs& g, Team& team, int b, int a0, int a1, bool bad_ptr) {
   const int m = g.memory;
   const int n_rows = g.n_atoms + 3 * g.n_mol;
+  // state words no step can have left behind (or a mol_ptr that leaves the arrays): the system is not touched, fmax_out = NaN
+  if (bad_ptr) {
+    if (team.first() == 0) g.fmax_out[b] = __builtin_nanf("");
+    return;
+  }
+  const int steps = g.n_steps[b];
+  int np = g.n_pairs[b], head = g.head[b];
+  const bool was = g.converged[b] != 0;
+  if (steps < 0 || np < 0 || np > m || head < 0 || head >= m) {
+    if (team.first() == 0) g.fmax_out[b] = __builtin_nanf("");
+    return;
+  }
+  const int n = a1 - a0, r0 = a0 + 3 * b, rc = a1 + 3 * b, r1 = rc + 3;
+  // ---- prologue: the 3x3 quantities, the same in every lane
+  const float c = g.cell_factor[b], p = g.pressure[b];
+  float F[3][3], h[3][3], W[3][3], C[3][3], FinvT[3][3], Wc[3][3], Gc[3][3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    F[k / 3][k % 3] = __fdiv_rn(g.x_in[3 * (size_t)rc + k], c);
+    h[k / 3][k % 3] = g.cell_in[9 * (size_t)b + k];
+    W[k / 3][k % 3] = g.virial[9 * (size_t)b + k];
+  }
+  const float V = cof3(h, C);
+  const float detF = cof3(F, C);
+  // a cell no step can work with: det F <= 0, F or V not finite (or c, p that the host wrapper cannot see on the device)
+  if (!(detF > 0.f) || !isfinite(detF) || !isfinite(V) || !finite3x3(F) || !(c > 0.f) || !isfinite(c) || !isfinite(p)) {
+    if (team.first() == 0) g.fmax_out[b] = __builtin_nanf("");
+    return;
+  }
+  const float pv = __fmul_rn(p, V);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) FinvT[i][j] = __fdiv_rn(C[i][j], detF);
+    W[i][i] = __fsub_rn(W[i][i], pv);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      Wc[i][j] = __fmaf_rn(W[i][2], FinvT[2][j], __fmaf_rn(W[i][1], FinvT[1][j], __fmul_rn(W[i][0], FinvT[0][j])));
+  if (g.flags & NNHIP_CELL_LBFGS_HYDROSTATIC) {
+    const float t = __fdiv_rn(__fadd_rn(__fadd_rn(Wc[0][0], Wc[1][1]), Wc[2][2]), 3.0f);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Wc[k / 3][k % 3] = k / 3 == k % 3 ? t : 0.f;
+  }
+  {
+    // Voigt order xx, yy, zz, yz, xz, xy: bit k of strain_mask frees that component
+    const int voigt[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      if (!((g.strain_mask >> voigt[k / 3][k % 3]) & 1)) Wc[k / 3][k % 3] = 0.f;
+  }
+  if (g.flags & NNHIP_CELL_LBFGS_CONSTANT_VOLUME) {
+    const float t = __fdiv_rn(__fadd_rn(__fadd_rn(Wc[0][0], Wc[1][1]), Wc[2][2]), 3.0f);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Wc[i][i] = __fsub_rn(Wc[i][i], t);
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Gc[k / 3][k % 3] = __fdiv_rn(Wc[k / 3][k % 3], c);
+  // ---- the lane's own rows of G, first for fmax alone (a frozen system's G buffer is not touched).  The three cell rows are the
+  // same in every lane, so every lane takes them into its maximum (a maximum does not mind) and no lane selects a row by index
+  auto atom_row = [&](int i, float* out) {
+    const int a = i - 3 * b;
+    float f[3];
+    load3(g.force, 3 * (size_t)a, f);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[j] = __fmaf_rn(f[2], F[2][j], __fmaf_rn(f[1], F[1][j], __fmul_rn(f[0], F[0][j])));
+    if (g.free_mask && !g.free_mask[a]) out[0] = out[1] = out[2] = 0.f;
+  };
+  float f2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) f2 = fmaxf(f2, dot3(Gc[k], Gc[k]));
+  for (int i = r0 + team.first(); i < rc; i += Team::STRIDE) {
+    float gr[3];
+    atom_row(i, gr);
+    f2 = fmaxf(f2, dot3(gr, gr));
+  }
+  const float fmax2 = team.max(f2);
+  const bool now = fmax2 < g.tol2;
+  if (team.first() == 0) {
+    g.fmax_out[b] = __fsqrt_rn(fmax2);
+    if (now && !was) g.converged[b] = 1;
+  }
+  if (was || now || (g.flags & NNHIP_CELL_LBFGS_CHECK_ONLY)) {
+    for (int i = r0 + team.first(); i < r1; i += Team::STRIDE) {
+      float x[3];
+      load3(g.x_in, 3 * (size_t)i, x);
+      store3(g.x_out, 3 * (size_t)i, x);
+    }
+    for (int i = a0 + team.first(); i < a1; i += Team::STRIDE) {
+      float x[3];
+      load3(g.pos_in, 3 * (size_t)i, x);
+      store3(g.pos_out, 3 * (size_t)i, x);
+    }
+    if (team.first() < 9) g.cell_out[9 * (size_t)b + team.first()] = g.cell_in[9 * (size_t)b + team.first()];
+    return;
+  }
+  for (int i = r0 + team.first(); i < rc; i += Team::STRIDE) {
+    float gr[3];
+    atom_row(i, gr);
+    store3(g.G, 3 * (size_t)i, gr);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (team.first() == (n + k) % Team::STRIDE) store3(g.G, 3 * (size_t)(rc + k), Gc[k]);   // (by the row's owner in the chain)
+  // ---- the pending pair, the two-loop, the step: on the generalised rows
+  const CellPolicy policy{g, 3 * b, rc};
+  lbfgs_chain::History hist;
+  hist.S = g.S, hist.Y = g.Y, hist.rho = g.rho, hist.f_prev = g.g_prev, hist.work = g.work;
+  hist.alpha = g.alpha, hist.maxstep = g.maxstep, hist.memory = m, hist.n_atoms = n_rows;
+  lbfgs_chain::step(hist, policy, team, b, r0, r1, steps > 0, np, head);
+  if (team.first() == 0) {
+    g.n_steps[b] = steps + 1;
+    g.n_pairs[b] = np;
+    g.head[b] = head;
+  }
+  // ---- epilogue: the new deformation gradient from the owners of the three cell rows, then the cell and the positions
+  // (an owner reads back the row it stored itself; the others get it from the team: __shfl in a wave, LDS and a barrier in a
+  // workgroup -- no member re-reads global memory another one wrote)
+  float Fn[3][3];
+  int owner[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    owner[k] = (n + k) % Team::STRIDE;
+    Fn[k][0] = Fn[k][1] = Fn[k][2] = 0.f;
+    if (team.first() == owner[k]) load3(g.x_out, 3 * (size_t)(rc + k), Fn[k]);
+  }
+  team.share_rows(owner, Fn);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Fn[k / 3][k % 3] = __fdiv_rn(Fn[k / 3][k % 3], c);
+  if (team.first() < 3) {
+    float h0r[3], row[3];
+    load3(g.h0, 9 * (size_t)b + 3 * team.first(), h0r);
+    times_transposed(h0r, Fn, row);
+    store3(g.cell_out, 9 * (size_t)b + 3 * team.first(), row);
+  }
+  for (int i = r0 + team.first(); i < rc; i += Team::STRIDE) {
+    float q[3], x[3];
+    load3(g.x_out, 3 * (size_t)i, q);
+    times_transposed(q, Fn, x);
+    store3(g.pos_out, 3 * (size_t)(i - 3 * b), x);
+  }
+}
+
+// which kernel a system belongs to (relax.hip's rule): the workgroup kernel takes the systems of at least wg_min_atoms ATOMS
+// (<= 0: all of them, and the wave kernel is not launched); a system whose mol_ptr leaves the arrays stays with the wave kernel
+// unless that is not launched.  The two kernels own disjoint systems and touch no word of the other's
+__device__ __forceinline__ bool wave_owns(int wg_min_atoms, int a0, int a1, bool bad_ptr) {
+  return wg_min_atoms > 0 && (bad_ptr || a1 - a0 < wg_min_atoms);
+}
+
+__global__ void __launch_bounds__(CR_THREADS)
+cell_lbfgs_step_kernel(CellRelaxArgs g) {
+  const int waves = CR_THREADS / 64;
+  lbfgs_chain::WaveTeam team{(int)(threadIdx.x & 63)};
   for (int b = blockIdx.x * waves + (threadIdx.x >> 6); b < g.n_mol; b += gridDim.x * waves) {   // (uniform over a wave)
     const int a0 = g.mol_ptr[b], a1 = g.mol_ptr[b + 1];
     const bool bad_ptr = a0 < 0 || a1 < a0 || a1 > g.n_atoms;
-    const int steps = g.n_steps[b];
-    int np = g.n_pairs[b], head = g.head[b];
-    // state words no step can have left behind (or a mol_ptr that leaves the arrays): the system is not touched, fmax_out = NaN
-    if (bad_ptr || steps < 0 || np < 0 || np > m || head < 0 || head >= m) {
-      if (lane == 0) g.fmax_out[b] = __builtin_nanf("");
-      continue;
-    }
-    const int n = a1 - a0, r0 = a0 + 3 * b, rc = a1 + 3 * b, r1 = rc + 3;
-    // ---- prologue: the 3x3 quantities, the same in every lane
-    const float c = g.cell_factor[b], p = g.pressure[b];
-    float F[3][3], h[3][3], W[3][3], C[3][3], FinvT[3][3], Wc[3][3], Gc[3][3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      F[k / 3][k % 3] = __fdiv_rn(g.x_in[3 * (size_t)rc + k], c);
-      h[k / 3][k % 3] = g.cell_in[9 * (size_t)b + k];
-      W[k / 3][k % 3] = g.virial[9 * (size_t)b + k];
-    }
-    const float V = cof3(h, C);
-    const float detF = cof3(F, C);
-    // a cell no step can work with: det F <= 0, F or V not finite (or c, p that the host wrapper cannot see on the device)
-    if (!(detF > 0.f) || !isfinite(detF) || !isfinite(V) || !finite3x3(F) || !(c > 0.f) || !isfinite(c) || !isfinite(p)) {
-      if (lane == 0) g.fmax_out[b] = __builtin_nanf("");
-      continue;
-    }
-    const float pv = __fmul_rn(p, V);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) FinvT[i][j] = __fdiv_rn(C[i][j], detF);
-      W[i][i] = __fsub_rn(W[i][i], pv);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        Wc[i][j] = __fmaf_rn(W[i][2], FinvT[2][j], __fmaf_rn(W[i][1], FinvT[1][j], __fmul_rn(W[i][0], FinvT[0][j])));
-    if (g.flags & NNHIP_CELL_LBFGS_HYDROSTATIC) {
-      const float t = __fdiv_rn(__fadd_rn(__fadd_rn(Wc[0][0], Wc[1][1]), Wc[2][2]), 3.0f);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Wc[k / 3][k % 3] = k / 3 == k % 3 ? t : 0.f;
-    }
-    {
-      // Voigt order xx, yy, zz, yz, xz, xy: bit k of strain_mask frees that component
-      const int voigt[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};
-#pragma unroll
-      for (int k = 0; k < 9; ++k)
-        if (!((g.strain_mask >> voigt[k / 3][k % 3]) & 1)) Wc[k / 3][k % 3] = 0.f;
-    }
-    if (g.flags & NNHIP_CELL_LBFGS_CONSTANT_VOLUME) {
-      const float t = __fdiv_rn(__fadd_rn(__fadd_rn(Wc[0][0], Wc[1][1]), Wc[2][2]), 3.0f);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) Wc[i][i] = __fsub_rn(Wc[i][i], t);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Gc[k / 3][k % 3] = __fdiv_rn(Wc[k / 3][k % 3], c);
-    // ---- the lane's own rows of G, first for fmax alone (a frozen system's G buffer is not touched).  The three cell rows are the
-    // same in every lane, so every lane takes them into its maximum (a maximum does not mind) and no lane selects a row by index
-    auto atom_row = [&](int i, float* out) {
-      const int a = i - 3 * b;
-      float f[3];
-      load3(g.force, 3 * (size_t)a, f);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) out[j] = __fmaf_rn(f[2], F[2][j], __fmaf_rn(f[1], F[1][j], __fmul_rn(f[0], F[0][j])));
-      if (g.free_mask && !g.free_mask[a]) out[0] = out[1] = out[2] = 0.f;
-    };
-    float f2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) f2 = fmaxf(f2, dot3(Gc[k], Gc[k]));
-    for (int i = r0 + lane; i < rc; i += 64) {
-      float gr[3];
-      atom_row(i, gr);
-      f2 = fmaxf(f2, dot3(gr, gr));
-    }
-    const float fmax2 = wave_max(f2);
-    const bool was = g.converged[b] != 0;
-    const bool now = fmax2 < g.tol2;
-    if (lane == 0) {
-      g.fmax_out[b] = __fsqrt_rn(fmax2);
-      if (now && !was) g.converged[b] = 1;
-    }
-    if (was || now || (g.flags & NNHIP_CELL_LBFGS_CHECK_ONLY)) {
-      for (int i = r0 + lane; i < r1; i += 64) {
-        float x[3];
-        load3(g.x_in, 3 * (size_t)i, x);
-        store3(g.x_out, 3 * (size_t)i, x);
-      }
-      for (int i = a0 + lane; i < a1; i += 64) {
-        float x[3];
-        load3(g.pos_in, 3 * (size_t)i, x);
-        store3(g.pos_out, 3 * (size_t)i, x);
-      }
-      if (lane < 9) g.cell_out[9 * (size_t)b + lane] = g.cell_in[9 * (size_t)b + lane];
-      continue;
-    }
-    for (int i = r0 + lane; i < rc; i += 64) {
-      float gr[3];
-      atom_row(i, gr);
-      store3(g.G, 3 * (size_t)i, gr);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      if (lane == ((n + k) & 63)) store3(g.G, 3 * (size_t)(rc + k), Gc[k]);      // (by the lane that owns the row in the chain)
-    // ---- the pending pair, the two-loop, the step: on the generalised rows
-    const CellPolicy policy{g, 3 * b, rc};
-    lbfgs_chain::History hist;
-    hist.S = g.S, hist.Y = g.Y, hist.rho = g.rho, hist.f_prev = g.g_prev, hist.work = g.work;
-    hist.alpha = g.alpha, hist.maxstep = g.maxstep, hist.memory = m, hist.n_atoms = n_rows;
-    lbfgs_chain::step(hist, policy, b, r0, r1, lane, steps > 0, np, head);
-    if (lane == 0) {
-      g.n_steps[b] = steps + 1;
-      g.n_pairs[b] = np;
-      g.head[b] = head;
-    }
-    // ---- epilogue: the new deformation gradient from the owners of the three cell rows, then the cell and the positions
-    float Fn[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int owner = (n + k) & 63;
-      float v[3] = {0.f, 0.f, 0.f};
-      if (lane == owner) load3(g.x_out, 3 * (size_t)(rc + k), v);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Fn[k][j] = __fdiv_rn(__shfl(v[j], owner, 64), c);
-    }
-    if (lane < 3) {
-      float h0r[3], row[3];
-      load3(g.h0, 9 * (size_t)b + 3 * lane, h0r);
-      times_transposed(h0r, Fn, row);
-      store3(g.cell_out, 9 * (size_t)b + 3 * lane, row);
-    }
-    for (int i = r0 + lane; i < rc; i += 64) {
-      float q[3], x[3];
-      load3(g.x_out, 3 * (size_t)i, q);
-      times_transposed(q, Fn, x);
-      store3(g.pos_out, 3 * (size_t)(i - 3 * b), x);
-    }
+    if (!wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
+    cell_system(g, team, b, a0, a1, bad_ptr);
+  }
+}
+
+// The workgroup-per-system form: one workgroup of NNHIP_LBFGS_WG_THREADS threads per system, grid-stride over the systems
+// (lbfgs_chain.h: BlockTeam has the method, the barrier argument and the rules).  The `continue` below is uniform over the
+// workgroup (mol_ptr[b], mol_ptr[b + 1] and the arguments are the same loads in every thread), and so is every return of
+// cell_system.  Thread t owns the generalised rows r0 + t, + 1024, ... of its system
+__global__ void __launch_bounds__(NNHIP_LBFGS_WG_THREADS)
+cell_lbfgs_step_wg_kernel(CellRelaxArgs g) {
+  __shared__ float red[lbfgs_chain::BlockTeam::RED_FLOATS];
+  __shared__ float rows[lbfgs_chain::BlockTeam::ROW_FLOATS];
+  lbfgs_chain::BlockTeam team{red, rows, (int)threadIdx.x, 0};
+  for (int b = blockIdx.x; b < g.n_mol; b += gridDim.x) {
+    const int a0 = g.mol_ptr[b], a1 = g.mol_ptr[b + 1];
+    const bool bad_ptr = a0 < 0 || a1 < a0 || a1 > g.n_atoms;
+    if (wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
+    cell_system(g, team, b, a0, a1, bad_ptr);
   }
 }
 
 }  // namespace
 
-extern "C" int nnhip_cell_lbfgs_step(const float* x_in, const float* pos_in, const float* force, const float* virial,
-                                     const float* cell_in, const float* h0, const uint8_t* free_mask, const int32_t* mol_ptr,
-                                     const float* pressure, const float* cell_factor, int32_t n_mol, int32_t n_atoms, int32_t memory,
-                                     float tol2, float alpha, float maxstep, int32_t strain_mask, int32_t flags, int32_t* converged,
-                                     int32_t* n_steps, int32_t* n_pairs, int32_t* head, float* S, float* Y, float* rho, float* g_prev,
-                                     float* work, float* G, float* x_out, float* pos_out, float* cell_out, float* fmax_out,
-                                     void* stream) {
+// the checks and the launches of both entry points.  wave: launch cell_lbfgs_step_kernel; wg: launch cell_lbfgs_step_wg_kernel
+static int cell_lbfgs_step_launch(const char* who, const float* x_in, const float* pos_in, const float* force, const float* virial,
+                                  const float* cell_in, const float* h0, const uint8_t* free_mask, const int32_t* mol_ptr,
+                                  const float* pressure, const float* cell_factor, int32_t n_mol, int32_t n_atoms, int32_t memory,
+                                  float tol2, float alpha, float maxstep, int32_t strain_mask, int32_t wg_min_atoms, bool wave,
+                                  bool wg, int32_t flags, int32_t* converged, int32_t* n_steps, int32_t* n_pairs, int32_t* head,
+                                  float* S, float* Y, float* rho, float* g_prev, float* work, float* G, float* x_out, float* pos_out,
+                                  float* cell_out, float* fmax_out, void* stream) {
   if (n_mol < 0 || n_atoms < 0 || memory < 1 || memory > NNHIP_LBFGS_MAX_MEMORY || (flags & ~CR_ALL_FLAGS) || strain_mask < 0 ||
       strain_mask > 63) {
-    nnhip_set_error("nnhip_cell_lbfgs_step: bad arguments (n_mol %d, n_atoms %d, memory %d: 1 .. %d, flags %d: bits of "
-                    "NNHIP_CELL_LBFGS_*, strain_mask %d: 0 .. 63)", n_mol, n_atoms, memory, NNHIP_LBFGS_MAX_MEMORY, flags,
+    nnhip_set_error("%s: bad arguments (n_mol %d, n_atoms %d, memory %d: 1 .. %d, flags %d: bits of "
+                    "NNHIP_CELL_LBFGS_*, strain_mask %d: 0 .. 63)", who, n_mol, n_atoms, memory, NNHIP_LBFGS_MAX_MEMORY, flags,
                     strain_mask);
     return NNHIP_E_INVALID;
   }
   if (!(tol2 >= 0.f) || !(alpha > 0.f) || !(maxstep > 0.f) || !(alpha <= 3.402823466e38f) || !(maxstep <= 3.402823466e38f)) {
-    nnhip_set_error("nnhip_cell_lbfgs_step: tol2 >= 0 and finite alpha > 0 and maxstep > 0 expected (got %g, %g, %g)", (double)tol2,
+    nnhip_set_error("%s: tol2 >= 0 and finite alpha > 0 and maxstep > 0 expected (got %g, %g, %g)", who, (double)tol2,
                     (double)alpha, (double)maxstep);
     return NNHIP_E_INVALID;
   }
   if (n_mol == 0) return NNHIP_OK;
   const size_t rows = (size_t)n_atoms + 3 * (size_t)n_mol;
   if (rows > 0x7fffffffu / 3) {
-    nnhip_set_error("nnhip_cell_lbfgs_step: n_atoms + 3 n_mol = %zu rows do not fit the 32-bit row index", rows);
+    nnhip_set_error("%s: n_atoms + 3 n_mol = %zu rows do not fit the 32-bit row index", who, rows);
     return NNHIP_E_INVALID;
   }
   if (!x_in || !virial || !cell_in || !h0 || !mol_ptr || !pressure || !cell_factor || !converged || !n_steps || !n_pairs || !head ||
       !S || !Y || !rho || !g_prev || !G || !x_out || !cell_out || !fmax_out || (rows > 64 && !work)) {
-    nnhip_set_error("nnhip_cell_lbfgs_step: null pointer (x_in, virial, cell_in, h0, mol_ptr, pressure, cell_factor, the state "
-                    "arrays, G, x_out, cell_out and fmax_out are mandatory; work [N + 3 B, 3] when N + 3 B > 64)");
+    nnhip_set_error("%s: null pointer (x_in, virial, cell_in, h0, mol_ptr, pressure, cell_factor, the state "
+                    "arrays, G, x_out, cell_out and fmax_out are mandatory; work [N + 3 B, 3] when N + 3 B > 64)", who);
     return NNHIP_E_INVALID;
   }
   if (n_atoms > 0 && (!pos_in || !force || !pos_out)) {
-    nnhip_set_error("nnhip_cell_lbfgs_step: null pointer (pos_in, force and pos_out are mandatory when n_atoms > 0)");
+    nnhip_set_error("%s: null pointer (pos_in, force and pos_out are mandatory when n_atoms > 0)", who);
     return NNHIP_E_INVALID;
   }
   if (overlap(x_in, x_out, 3 * rows) || overlap(cell_in, cell_out, 9 * (size_t)n_mol) ||
       (n_atoms > 0 && overlap(pos_in, pos_out, 3 * (size_t)n_atoms))) {
-    nnhip_set_error("nnhip_cell_lbfgs_step: x_out, pos_out and cell_out may not alias x_in, pos_in and cell_in (a forward call that "
-                    "has to be repeated reads pos_in and cell_in again)");
+    nnhip_set_error("%s: x_out, pos_out and cell_out may not alias x_in, pos_in and cell_in (a forward call that "
+                    "has to be repeated reads pos_in and cell_in again)", who);
     return NNHIP_E_INVALID;
   }
   CellRelaxArgs g;
@@ -339,10 +387,45 @@ extern "C" int nnhip_cell_lbfgs_step(const float* x_in, const float* pos_in, con
   g.n_mol = n_mol;
   g.n_atoms = n_atoms;
   g.memory = memory;
-  const int waves = CR_THREADS / 64;
-  int blocks = (n_mol + waves - 1) / waves;
-  blocks = blocks > CR_MAX_BLOCKS ? CR_MAX_BLOCKS : blocks;
-  cell_lbfgs_step_kernel<<<blocks, CR_THREADS, 0, (hipStream_t)stream>>>(g);
-  LAUNCH_CHECK();
+  g.wg_min_atoms = wg_min_atoms;
+  if (wave) {
+    const int waves = CR_THREADS / 64;
+    int blocks = (n_mol + waves - 1) / waves;
+    blocks = blocks > CR_MAX_BLOCKS ? CR_MAX_BLOCKS : blocks;
+    cell_lbfgs_step_kernel<<<blocks, CR_THREADS, 0, (hipStream_t)stream>>>(g);
+    LAUNCH_CHECK();
+  }
+  if (wg) {
+    const int blocks = n_mol > CR_MAX_BLOCKS ? CR_MAX_BLOCKS : n_mol;
+    cell_lbfgs_step_wg_kernel<<<blocks, NNHIP_LBFGS_WG_THREADS, 0, (hipStream_t)stream>>>(g);
+    LAUNCH_CHECK();
+  }
   return NNHIP_OK;
+}
+
+extern "C" int nnhip_cell_lbfgs_step(const float* x_in, const float* pos_in, const float* force, const float* virial,
+                                     const float* cell_in, const float* h0, const uint8_t* free_mask, const int32_t* mol_ptr,
+                                     const float* pressure, const float* cell_factor, int32_t n_mol, int32_t n_atoms, int32_t memory,
+                                     float tol2, float alpha, float maxstep, int32_t strain_mask, int32_t flags, int32_t* converged,
+                                     int32_t* n_steps, int32_t* n_pairs, int32_t* head, float* S, float* Y, float* rho, float* g_prev,
+                                     float* work, float* G, float* x_out, float* pos_out, float* cell_out, float* fmax_out,
+                                     void* stream) {
+  // (a threshold no system reaches: the wave kernel takes every system)
+  return cell_lbfgs_step_launch("nnhip_cell_lbfgs_step", x_in, pos_in, force, virial, cell_in, h0, free_mask, mol_ptr, pressure,
+                                cell_factor, n_mol, n_atoms, memory, tol2, alpha, maxstep, strain_mask, 0x7fffffff, true, false, flags,
+                                converged, n_steps, n_pairs, head, S, Y, rho, g_prev, work, G, x_out, pos_out, cell_out, fmax_out,
+                                stream);
+}
+
+extern "C" int nnhip_cell_lbfgs_step_wg(const float* x_in, const float* pos_in, const float* force, const float* virial,
+                                        const float* cell_in, const float* h0, const uint8_t* free_mask, const int32_t* mol_ptr,
+                                        const float* pressure, const float* cell_factor, int32_t n_mol, int32_t n_atoms,
+                                        int32_t memory, float tol2, float alpha, float maxstep, int32_t strain_mask,
+                                        int32_t wg_min_atoms, int32_t flags, int32_t* converged, int32_t* n_steps, int32_t* n_pairs,
+                                        int32_t* head, float* S, float* Y, float* rho, float* g_prev, float* work, float* G,
+                                        float* x_out, float* pos_out, float* cell_out, float* fmax_out, void* stream) {
+  return cell_lbfgs_step_launch("nnhip_cell_lbfgs_step_wg", x_in, pos_in, force, virial, cell_in, h0, free_mask, mol_ptr, pressure,
+                                cell_factor, n_mol, n_atoms, memory, tol2, alpha, maxstep, strain_mask, wg_min_atoms,
+                                wg_min_atoms > 0, true, flags, converged, n_steps, n_pairs, head, S, Y, rho, g_prev, work, G, x_out,
+                                pos_out, cell_out, fmax_out, stream);
 }

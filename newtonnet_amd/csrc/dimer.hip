@@ -458,7 +458,8 @@ dimer_step_kernel(DimerArgs g) {
     lbfgs_chain::History h;
     h.S = g.S, h.Y = g.Y, h.rho = g.rho, h.f_prev = vec(g, NNHIP_DIMER_V_F_PREV), h.work = g.work;
     h.alpha = g.alpha, h.maxstep = g.maxstep, h.memory = m, h.n_atoms = g.n_atoms;
-    lbfgs_chain::step(h, policy, b, a0, a1, lane, concave && pending != 0, np, head);
+    lbfgs_chain::WaveTeam team{lane};
+    lbfgs_chain::step(h, policy, team, b, a0, a1, concave && pending != 0, np, head);
     if (lane == 0) {
       I[NNHIP_DIMER_I_PENDING * B] = concave ? 1 : 0;
       I[NNHIP_DIMER_I_STEPS * B] = steps + 1;

@@ -783,18 +783,30 @@ def md_step_constrained(pos_in: torch.Tensor, vel: torch.Tensor, force: Optional
 LBFGS_CHECK_ONLY = _K['NNHIP_LBFGS_CHECK_ONLY']             # flag of nnhip_lbfgs_step
 LBFGS_MAX_MEMORY = _K['NNHIP_LBFGS_MAX_MEMORY']
 LBFGS_CURVATURE_MIN = 1e-4       # a pair enters the history iff y.s > 0 and cos(y, s) > this (include/newtonnet_hip.h)
+LBFGS_WG_THREADS = _K['NNHIP_LBFGS_WG_THREADS']             # threads of the workgroup-per-system form (nnhip_lbfgs_step_wg)
+
+
+def _wg_min_atoms(wg_min_atoms):
+    if (isinstance(wg_min_atoms, bool) or not hasattr(wg_min_atoms, '__index__') or
+            not -2 ** 31 <= int(wg_min_atoms) < 2 ** 31):
+        raise ValueError(f'wg_min_atoms: None or an int32 expected (got {wg_min_atoms!r})')
+    return int(wg_min_atoms)
 
 
 def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.Tensor], mol_ptr: torch.Tensor, memory: int,
                tol2: float, alpha: float, maxstep: float, flags: int, converged: torch.Tensor, n_steps: torch.Tensor,
                n_pairs: torch.Tensor, head: torch.Tensor, S: torch.Tensor, Y: torch.Tensor, rho: torch.Tensor,
-               f_prev: torch.Tensor, work: Optional[torch.Tensor], pos_out: torch.Tensor, fmax_out: torch.Tensor):
+               f_prev: torch.Tensor, work: Optional[torch.Tensor], pos_out: torch.Tensor, fmax_out: torch.Tensor,
+               wg_min_atoms: Optional[int] = None):
     """One launch of the L-BFGS step (nnhip_lbfgs_step, csrc/relax.hip; the contract is in include/newtonnet_hip.h) on the
     current stream, for the B molecules mol_ptr (int32 [B+1]) delimits.  pos_in, force [N,3] are read; free: bool / uint8 [N]
     (False = fixed atom) or None; the state (converged, n_steps, n_pairs, head int32 [B]; S, Y fp32 [memory,N,3]; rho fp32
     [B,memory]; f_prev fp32 [N,3]) is updated in place, pos_out [N,3] and fmax_out [B] are written: all of these must be contiguous
     tensors of exactly that type (a copy would take the result away).  work: fp32 [N,3] scratch, needed when N > 64.  pos_out may
-    not overlap pos_in."""
+    not overlap pos_in.  wg_min_atoms: None = nnhip_lbfgs_step (one wave64 per molecule); an int = nnhip_lbfgs_step_wg, which
+    gives the molecules of at least that many atoms one workgroup of LBFGS_WG_THREADS threads each (<= 0: every molecule)."""
+    if wg_min_atoms is not None:
+        wg_min_atoms = _wg_min_atoms(wg_min_atoms)
     B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
     if pos_out.dim() != 2 or pos_out.shape[1] != 3:
         raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
@@ -807,10 +819,14 @@ def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.T
             raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
         free = free.contiguous()
     pos_in, force = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N))
-    _check(lib().nnhip_lbfgs_step(_ptr(pos_in), _ptr(force), _ptr(free), _ptr(mol_ptr), B, N, m, float(tol2), float(alpha),
-                                  float(maxstep), int(flags), _ptr(converged), _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S),
-                                  _ptr(Y), _ptr(rho), _ptr(f_prev), _ptr(work), _ptr(pos_out), _ptr(fmax_out), _stream(dev)),
-           'nnhip_lbfgs_step')
+    L = lib()
+    head_args = (_ptr(pos_in), _ptr(force), _ptr(free), _ptr(mol_ptr), B, N, m, float(tol2), float(alpha), float(maxstep))
+    tail_args = (int(flags), _ptr(converged), _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S), _ptr(Y), _ptr(rho), _ptr(f_prev),
+                 _ptr(work), _ptr(pos_out), _ptr(fmax_out), _stream(dev))
+    if wg_min_atoms is None:
+        _check(L.nnhip_lbfgs_step(*head_args, *tail_args), 'nnhip_lbfgs_step')
+    else:
+        _check(L.nnhip_lbfgs_step_wg(*head_args, wg_min_atoms, *tail_args), 'nnhip_lbfgs_step_wg')
 
 
 # flags of nnhip_cell_lbfgs_step
@@ -824,7 +840,8 @@ def cell_lbfgs_step(x_in: torch.Tensor, pos_in: torch.Tensor, force: torch.Tenso
                     cell_factor: torch.Tensor, memory: int, tol2: float, alpha: float, maxstep: float, strain_mask: int, flags: int,
                     converged: torch.Tensor, n_steps: torch.Tensor, n_pairs: torch.Tensor, head: torch.Tensor, S: torch.Tensor,
                     Y: torch.Tensor, rho: torch.Tensor, g_prev: torch.Tensor, work: Optional[torch.Tensor], G: torch.Tensor,
-                    x_out: torch.Tensor, pos_out: torch.Tensor, cell_out: torch.Tensor, fmax_out: torch.Tensor):
+                    x_out: torch.Tensor, pos_out: torch.Tensor, cell_out: torch.Tensor, fmax_out: torch.Tensor,
+                    wg_min_atoms: Optional[int] = None):
     """One launch of the variable-cell L-BFGS step (nnhip_cell_lbfgs_step, csrc/cellrelax.hip; the contract is in
     include/newtonnet_hip.h) on the current stream, for the B periodic systems mol_ptr (int32 [B+1]) delimits.  With R = N + 3 B
     generalised rows (system b: its atom rows, then the three rows of cell_factor x F): x_in [R,3], pos_in, force [N,3], virial,
@@ -832,7 +849,11 @@ def cell_lbfgs_step(x_in: torch.Tensor, pos_in: torch.Tensor, force: torch.Tenso
     None; strain_mask: bit k frees the Voigt component k; the state (converged, n_steps, n_pairs, head int32 [B]; S, Y fp32
     [memory,R,3]; rho fp32 [B,memory]; g_prev fp32 [R,3]) is updated in place, G and x_out [R,3], pos_out [N,3], cell_out [B,3,3]
     and fmax_out [B] are written: all of these must be contiguous tensors of exactly that type (a copy would take the result
-    away).  work: fp32 [R,3] scratch, needed when R > 64.  x_out, pos_out, cell_out may not overlap x_in, pos_in, cell_in."""
+    away).  work: fp32 [R,3] scratch, needed when R > 64.  x_out, pos_out, cell_out may not overlap x_in, pos_in, cell_in.
+    wg_min_atoms: None = nnhip_cell_lbfgs_step (one wave64 per system); an int = nnhip_cell_lbfgs_step_wg, which gives the systems
+    of at least that many atoms one workgroup of LBFGS_WG_THREADS threads each (<= 0: every system)."""
+    if wg_min_atoms is not None:
+        wg_min_atoms = _wg_min_atoms(wg_min_atoms)
     B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
     if pos_out.dim() != 2 or pos_out.shape[1] != 3:
         raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
@@ -849,11 +870,15 @@ def cell_lbfgs_step(x_in: torch.Tensor, pos_in: torch.Tensor, force: torch.Tenso
     x_in, pos_in, force, virial, cell_in, h0, pressure, cell_factor = _read(
         dev, x_in=(x_in, 3 * R), pos_in=(pos_in, 3 * N), force=(force, 3 * N), virial=(virial, 9 * B), cell_in=(cell_in, 9 * B),
         h0=(h0, 9 * B), pressure=(pressure, B), cell_factor=(cell_factor, B))
-    _check(lib().nnhip_cell_lbfgs_step(
-        _ptr(x_in), _ptr(pos_in), _ptr(force), _ptr(virial), _ptr(cell_in), _ptr(h0), _ptr(free), _ptr(mol_ptr), _ptr(pressure),
-        _ptr(cell_factor), B, N, m, float(tol2), float(alpha), float(maxstep), int(strain_mask), int(flags), _ptr(converged),
-        _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S), _ptr(Y), _ptr(rho), _ptr(g_prev), _ptr(work), _ptr(G), _ptr(x_out),
-        _ptr(pos_out), _ptr(cell_out), _ptr(fmax_out), _stream(dev)), 'nnhip_cell_lbfgs_step')
+    L = lib()
+    head_args = (_ptr(x_in), _ptr(pos_in), _ptr(force), _ptr(virial), _ptr(cell_in), _ptr(h0), _ptr(free), _ptr(mol_ptr),
+                 _ptr(pressure), _ptr(cell_factor), B, N, m, float(tol2), float(alpha), float(maxstep), int(strain_mask))
+    tail_args = (int(flags), _ptr(converged), _ptr(n_steps), _ptr(n_pairs), _ptr(head), _ptr(S), _ptr(Y), _ptr(rho), _ptr(g_prev),
+                 _ptr(work), _ptr(G), _ptr(x_out), _ptr(pos_out), _ptr(cell_out), _ptr(fmax_out), _stream(dev))
+    if wg_min_atoms is None:
+        _check(L.nnhip_cell_lbfgs_step(*head_args, *tail_args), 'nnhip_cell_lbfgs_step')
+    else:
+        _check(L.nnhip_cell_lbfgs_step_wg(*head_args, wg_min_atoms, *tail_args), 'nnhip_cell_lbfgs_step_wg')
 
 
 NEB_CHECK_ONLY, NEB_CLIMB =_K['NNHIP_NEB_CHECK_ONLY'], _K['NNHIP_NEB_CLIMB']      # flags of nnhip_neb_step

@@ -868,19 +868,23 @@ class NewtonNet(nn.Module):
                                bias_factor=bias_factor, walkers=walkers, restraint_k=restraint_k, restraint_center=restraint_center,
                                timestep=timestep, masses=masses, fixed=fixed, generator=generator, hill_capacity=hill_capacity)
 
-    def relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
+    def relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None, form='wave',
+                   wg_min_atoms=None):
         """Relaxation of every molecule of the batch to a minimum on the device: a newtonnet_amd.relax.Relaxation whose
         run(max_steps, check_every, record_every) steps them together, one force evaluation and one L-BFGS launch (csrc/relax.hip)
         per step, each molecule with its own history and convergence flag.  L-BFGS without line search in ASE's convention:
         fmax (eV / Angstrom) is the convergence threshold on the largest atomic force, memory the pairs kept, maxstep (Angstrom) the
         cap on the longest atomic displacement, 1 / alpha the initial inverse Hessian; fixed: bool [N], atoms that never move.
+        form: 'wave' (one wave64 per molecule, the default), 'workgroup' (one workgroup per molecule: large systems) or 'auto'
+        (the workgroup form from wg_min_atoms atoms on, None = relax.WG_AUTO_MIN_ATOMS, decided per molecule on the device).
         Eval mode only; needs the 'energy' and 'gradient_force' heads.  The reference leaves optimisation to an outside driver,
         one structure and one calculator call per step."""
         from newtonnet_amd import relax as _r
-        return _r.Relaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, fixed=fixed)
+        return _r.Relaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, fixed=fixed,
+                             form=form, wg_min_atoms=wg_min_atoms)
 
     def cell_relaxation(self, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, pressure=0.0, mask=None,
-                        hydrostatic=False, constant_volume=False, cell_factor=None, fixed=None):
+                        hydrostatic=False, constant_volume=False, cell_factor=None, fixed=None, form='wave', wg_min_atoms=None):
         """Variable-cell relaxation of every periodic system of the batch on the device, atoms and cell together: a
         newtonnet_amd.cellrelax.CellRelaxation whose run(max_steps, check_every, record_every) makes one model call and one launch
         (csrc/cellrelax.hip) per step, each system with its own history and convergence flag.  ASE's UnitCellFilter under the
@@ -888,12 +892,12 @@ class NewtonNet(nn.Module):
         (bar): a number or one per system, the stress the cell is relaxed to; mask: six 0/1 flags (xx, yy, zz, yz, xz, xy) of
         the strain components that may change; hydrostatic: only the volume changes; constant_volume: only the shape changes;
         cell_factor: the weight of the cell rows (None: the atom count); fixed: bool [N], atoms that keep their scaled position
-        and ride with the cell.  Eval mode only; needs the 'energy' and 'gradient_force' heads and a 'virial' or 'stress' head;
+        and ride with the cell; form, wg_min_atoms: as for `relaxation` (the threshold counts atoms).  Eval mode only; needs the 'energy' and 'gradient_force' heads and a 'virial' or 'stress' head;
         every system needs det(cell) > 0."""
         from newtonnet_amd import cellrelax as _c
         return _c.CellRelaxation(self, z, pos, cell, batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha, pressure=pressure,
                                  mask=mask, hydrostatic=hydrostatic, constant_volume=constant_volume, cell_factor=cell_factor,
-                                 fixed=fixed)
+                                 fixed=fixed, form=form, wg_min_atoms=wg_min_atoms)
 
     def band(self, z, pos, cell, batch, n_images, spring=0.1, fmax=0.05, climb=True, climb_below=None, fixed=None, dt=0.1,
              dt_max=1.0, maxstep=0.2):

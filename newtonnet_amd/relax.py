@@ -10,8 +10,15 @@ stated in include/newtonnet_hip.h: a curvature pair enters the history only when
 A molecule that has converged is frozen -- later launches leave every bit of it alone -- but model() keeps evaluating it with the
 rest of the batch: compacting the batch is not done here.  Minima only (saddles: newtonnet_amd.dimer, which takes its translation
 from the same device code, csrc/lbfgs_chain.h) at a fixed cell (the cell is relaxed by newtonnet_amd.cellrelax, again on that
-device code): no Hessian-based steps, no constraint other than fixed atoms.  The launch gives one wave64 to a molecule, whatever its size: it is meant for batches of
-molecules, and one large system pays about 2 memory ceil(n / 64) dependent sweeps of a single wave per step.
+device code): no Hessian-based steps, no constraint other than fixed atoms.
+
+Two forms of the launch, chosen with `form`: 'wave' (the default) gives one wave64 to a molecule, whatever its size -- it is meant
+for batches of molecules, and one large system pays about 2 memory ceil(n / 64) dependent sweeps of a single wave per step;
+'workgroup' gives every molecule one workgroup of hip.LBFGS_WG_THREADS threads (nnhip_lbfgs_step_wg), for large systems; 'auto'
+sends the molecules of at least wg_min_atoms atoms to the workgroup form and the others to the wave form, decided per molecule on
+the device.  Both forms satisfy the same contract; their bits differ from each other because their reductions are ordered
+differently (above 64 atoms; up to 64 they agree).  WG_AUTO_MIN_ATOMS, the default threshold of 'auto', is measured: the smallest
+size of the sweep of tools/bench_relax_large.py from which on the workgroup launch is no slower at 1 and at 64 systems.
 
 Units: positions in Angstrom, forces and fmax in eV / Angstrom, alpha in eV / Angstrom^2."""
 from __future__ import annotations
@@ -24,6 +31,24 @@ import torch
 
 from newtonnet_amd import hip
 from newtonnet_amd.dynamics import _mol_ptr
+
+
+FORMS = ('wave', 'workgroup', 'auto')
+WG_AUTO_MIN_ATOMS = 128          # default wg_min_atoms of form='auto': measured (tools/bench_relax_large.py, profiles/relax_large.json)
+
+
+def check_form(form, wg_min_atoms):
+    """form and wg_min_atoms of a driver, refused without touching the device; returns the wg_min_atoms argument of
+    hip.lbfgs_step / hip.cell_lbfgs_step: None ('wave': the wave entry point), 0 ('workgroup': every system) or the threshold
+    ('auto')"""
+    if not isinstance(form, str) or form not in FORMS:
+        raise ValueError(f"form: one of {', '.join(repr(f) for f in FORMS)} expected (got {form!r})")
+    if wg_min_atoms is None:
+        wg_min_atoms = WG_AUTO_MIN_ATOMS
+    elif (isinstance(wg_min_atoms, (bool, np.bool_)) or not isinstance(wg_min_atoms, (int, np.integer)) or
+          not 1 <= wg_min_atoms < 2 ** 31):
+        raise ValueError(f'wg_min_atoms: None or a positive int expected (got {wg_min_atoms!r})')
+    return {'wave': None, 'workgroup': 0, 'auto': int(wg_min_atoms)}[form]
 
 
 class RelaxResult:
@@ -98,14 +123,18 @@ class Relaxation:
     device; none of them is modified (the positions are copied).  fmax: a molecule has converged when the largest force norm on one
     of its free atoms is below it (compared as squares in fp32: |f|^2 < fl32(fmax^2)).  memory: pairs kept per molecule.  maxstep:
     cap on the longest atomic displacement of a step.  alpha: the initial inverse Hessian is 1 / alpha.  fixed: bool [N], atoms
-    that never move.
+    that never move.  form: 'wave' (one wave64 per molecule, the default), 'workgroup' (one workgroup per molecule, for large
+    systems) or 'auto' (per molecule on the device: the workgroup form from wg_min_atoms atoms on; None = WG_AUTO_MIN_ATOMS);
+    wg_min_atoms means something with 'auto' only.
 
     Periodic molecules: the cell is fixed and positions stay unwrapped; the model's neighbor list takes the minimum image itself."""
 
-    def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None):
+    def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None, form='wave',
+                 wg_min_atoms=None):
         # ---- everything that can be refused without touching the device
         N, B = check_inputs(model, 'Relaxation', z, pos, cell, batch, fixed)
         fmax, memory, maxstep, alpha = check_arguments(fmax, memory, maxstep, alpha)
+        self.form, self._wg_min_atoms = form, check_form(form, wg_min_atoms)
         if not pos.is_cuda:
             raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: move the model and the inputs to '
                                '"cuda"')
@@ -153,7 +182,7 @@ class Relaxation:
         other = 1 - self._cur
         hip.lbfgs_step(self._pos[self._cur], self._force, self._free, self._mol_ptr, self.memory, self._tol2, self._alpha,
                        self._maxstep, flags, self._converged, self._n_steps, self._n_pairs, self._head, self._S, self._Y, self._rho,
-                       self._f_prev, self._work, self._pos[other], self._fmax)
+                       self._f_prev, self._work, self._pos[other], self._fmax, wg_min_atoms=self._wg_min_atoms)
         self._cur = other
 
     def _ensure_state(self):

@@ -500,11 +500,12 @@ class MLAseCalculator(_Base):
         return out
 
     def relax(self, atoms_or_list, fmax: float = 0.01, max_steps: int = 500, memory: int = 16, maxstep: float = 0.2,
-              alpha: float = 70.0, check_every: int = 10, fixed=None):
+              alpha: float = 70.0, check_every: int = 10, fixed=None, form: str = 'wave', wg_min_atoms=None):
         """Relax one structure or a list of equally sized ones to a minimum, all stepped together on the device
         (NewtonNet.relaxation): L-BFGS without line search in ase.optimize.LBFGS's convention, until the largest atomic force of a
         structure is below fmax (eV / Angstrom) or max_steps steps have been taken.  fixed: bool array [n_atoms], the same atoms
-        held in every structure.  Returns a dict of numpy arrays: positions [n_frames, n_atoms, 3], energy, fmax, converged,
+        held in every structure.  form, wg_min_atoms: the launch form of NewtonNet.relaxation ('wave', 'workgroup' for large
+        structures, 'auto').  Returns a dict of numpy arrays: positions [n_frames, n_atoms, 3], energy, fmax, converged,
         n_steps [n_frames]; one structure drops the frame axis.  The Atoms objects are not modified."""
         from newtonnet_amd import relax as _r
         atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
@@ -515,6 +516,7 @@ class MLAseCalculator(_Base):
             raise ValueError('relax: frames of different sizes cannot share one array; use model.relaxation (packed per molecule)')
         _r.check_arguments(fmax, memory, maxstep, alpha)
         _r.check_run_arguments(max_steps, check_every, 0)
+        _r.check_form(form, wg_min_atoms)
         if fixed is not None:
             fixed = np.asarray(fixed)
             if fixed.dtype != np.bool_ or fixed.shape != (n_atoms,):
@@ -524,7 +526,7 @@ class MLAseCalculator(_Base):
         z, pos, cell, batch = self.format_data(atoms)
         held = None if fixed is None else torch.from_numpy(np.tile(fixed, n_frames)).to(pos.device)
         rel = self.model.relaxation(z, pos.float(), cell.float(), batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha,
-                                    fixed=held)
+                                    fixed=held, form=form, wg_min_atoms=wg_min_atoms)
         res = rel.run(int(max_steps), int(check_every))
         out = dict(positions=res.pos.cpu().numpy().reshape(n_frames, n_atoms, 3), energy=res.energy.cpu().numpy(),
                    fmax=res.fmax.cpu().numpy(), converged=res.converged.cpu().numpy(), n_steps=res.n_steps.cpu().numpy())
@@ -534,12 +536,13 @@ class MLAseCalculator(_Base):
 
     def relax_cell(self, atoms_or_list, fmax: float = 0.01, max_steps: int = 500, memory: int = 16, maxstep: float = 0.2,
                    alpha: float = 70.0, pressure=0.0, mask=None, hydrostatic: bool = False, constant_volume: bool = False,
-                   cell_factor=None, check_every: int = 10, fixed=None):
+                   cell_factor=None, check_every: int = 10, fixed=None, form: str = 'wave', wg_min_atoms=None):
         """Relax the atoms and the cell of one periodic structure or a list of equally sized ones, all stepped together on the
         device (NewtonNet.cell_relaxation: ASE's UnitCellFilter under L-BFGS), until the largest generalised force of a structure
         (atoms and cell rows alike) is below fmax (eV / Angstrom) or max_steps steps have been taken.  pressure in bar (a number,
         or one value per structure); mask: six 0/1 flags xx, yy, zz, yz, xz, xy; fixed: bool array [n_atoms], the same atoms held
-        (at their scaled positions) in every structure.  The calculator's model needs a virial or stress head (properties with
+        (at their scaled positions) in every structure; form, wg_min_atoms: the launch form of NewtonNet.cell_relaxation ('wave',
+        'workgroup' for large structures, 'auto').  The calculator's model needs a virial or stress head (properties with
         'stress').  Returns a dict of numpy arrays: positions [n_frames, n_atoms, 3], cell and stress (bar) [n_frames, 3, 3],
         volume, energy, enthalpy, fmax, converged, failed, n_steps [n_frames]; one structure drops the frame axis.  The Atoms
         objects are not modified."""
@@ -558,6 +561,7 @@ class MLAseCalculator(_Base):
             pressure = torch.tensor(np.asarray(pressure, dtype=np.float64))
         _c.check_cell_arguments(n_frames, pressure, mask, hydrostatic, constant_volume, cell_factor)
         _c.check_model(self.model, 'relax_cell')
+        _r.check_form(form, wg_min_atoms)
         if fixed is not None:
             fixed = np.asarray(fixed)
             if fixed.dtype != np.bool_ or fixed.shape != (n_atoms,):
@@ -568,7 +572,7 @@ class MLAseCalculator(_Base):
         held = None if fixed is None else torch.from_numpy(np.tile(fixed, n_frames)).to(pos.device)
         rel = self.model.cell_relaxation(z, pos.float(), cell.float(), batch, fmax=fmax, memory=memory, maxstep=maxstep, alpha=alpha,
                                          pressure=pressure, mask=mask, hydrostatic=hydrostatic, constant_volume=constant_volume,
-                                         cell_factor=cell_factor, fixed=held)
+                                         cell_factor=cell_factor, fixed=held, form=form, wg_min_atoms=wg_min_atoms)
         res = rel.run(int(max_steps), int(check_every))
         out = dict(positions=res.pos.cpu().numpy().reshape(n_frames, n_atoms, 3), cell=res.cell.cpu().numpy(),
                    stress=res.stress.cpu().numpy(), volume=res.volume.cpu().numpy(), energy=res.energy.cpu().numpy(),
