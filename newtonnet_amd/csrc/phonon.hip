@@ -21,7 +21,8 @@
 //   3. rank the eigenvalues by counting (index as tie-break), fix each mode's phase (the component of largest magnitude real and
 //      positive, lowest index on a tie), write.
 // Packing: a crystal with Mp <= 32 gives every problem ONE wave, four problems per workgroup, synchronised by wave barriers
-// only (the waves of a workgroup never meet); a larger one takes the whole workgroup of 256 threads.  The choice is a function
+// only (the waves of a workgroup never meet); a larger one takes the whole workgroup of 256 threads (a crystal that the host
+// offsets left without LDS in either form is flagged for every wave vector and not computed).  The choice is a function
 // of the crystal's own size, and no sum depends on the thread count, so the result of a (b, q) depends neither on the packing
 // nor on what else is in the launch.  No float atomics: two calls are bitwise equal.  modes == null skips W; A's arithmetic does
 // not read W, so the eigenvalues keep every bit.
@@ -240,8 +241,17 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
         const float ab = hypotf(ar, ai);
         float c = 1.f, sn = 0.f, ur = 1.f, ui = 0.f, dl = 0.f;
         if (ab != 0.f) {
-          ur = ar / ab;
-          ui = ai / ab;
+          // |u| = 1 is what keeps W unitary.  A coupling that has converged into the denormal range (a pair that settles sweeps
+          // before the matrix does, as in a graded spectrum) has too few bits left for its modulus to normalise it: scale it
+          // up first (exact).  tau below takes the modulus as it is.
+          float sr = ar, si = ai, sb = ab;
+          if (ab < 0x1p-100f) {
+            sr = ar * 0x1p64f;
+            si = ai * 0x1p64f;
+            sb = hypotf(sr, si);
+          }
+          ur = sr / sb;
+          ui = si / sb;
           const float tau = (Are[q * ld + q] - Are[p * ld + p]) / (2.f * ab);
           const float tn = copysignf(1.f, tau) / (fabsf(tau) + sqrtf(1.f + tau * tau));   // (tau^2 = inf: t = 0, the identity)
           c = 1.f / sqrtf(1.f + tn * tn);
@@ -392,10 +402,18 @@ phonon_kernel(PhArgs g) {
     const int qi = blockIdx.x * (PH_THREADS / 64) + wave;
     if (qi >= g.n_q) return;
     ph_problem<true>(g, b, qi, ph_smem + (size_t)wave * g.slot_wave, g.cap_wave, threadIdx.x & 63);
-  } else {
+  } else if (Mp <= g.cap_big) {   // (cap_big > 0: the grid has a workgroup per wave vector)
     const int qi = blockIdx.x;
     if (qi >= g.n_q) return;
     ph_problem<false>(g, b, qi, ph_smem, g.cap_big, threadIdx.x);
+  } else {
+    // cry_ptr gives the crystal more atoms than cry_ptr_host did and neither form of this launch has the LDS for it.  The grid
+    // may be that of the wave form alone (a workgroup per FOUR wave vectors), so the flags are not left to a workgroup per
+    // problem: whatever the grid, every problem of the crystal is flagged, and nothing else of it is written.
+    for (int qi = blockIdx.x * PH_THREADS + threadIdx.x; qi < g.n_q; qi += gridDim.x * PH_THREADS) {
+      g.sweeps[(size_t)b * g.n_q + qi] = 0;
+      g.status[(size_t)b * g.n_q + qi] = NNHIP_EIG_STATUS_SIZE;
+    }
   }
 }
 

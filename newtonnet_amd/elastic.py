@@ -158,7 +158,11 @@ def fold_force_constants(ph) -> torch.Tensor:
         if n and N % n:
             raise ValueError(f'crystal {b}: {N} supercell atoms are no multiple of its {n} atoms')
     phi0 = torch.zeros(sum(9 * n * n for n in ph.counts), dtype=torch.float32, device=ph.fc.device)
-    status = torch.zeros(len(ph.counts), dtype=torch.int32, device=ph.fc.device)   # the host check above is what reports a misuse here
+    # The library wants a status array (NNHIP_ELASTIC_STATUS_SIZE per crystal whose sc_atoms is no multiple of its atoms).  It is
+    # not read back: ph.sc_atoms and ph.cry_ptr are the device copies of the very counts the loop above has just checked, so the
+    # bit cannot be set here, and reading it would cost a device-to-host wait per call.  The bit is a C caller's; the stage test
+    # (tests/test_hip_crystal_stages.py) produces it through the library directly.
+    status = torch.zeros(len(ph.counts), dtype=torch.int32, device=ph.fc.device)
     hip._check(hip.lib().nnhip_elastic_fold(hip._ptr(ph.fc), hip._ptr(ph.fc_ptr), hip._ptr(ph.cry_ptr), hip._ptr(ph.sc_atoms),
                                             hip._ptr(ph.out_ptr), len(ph.counts), hip._ptr(phi0), hip._ptr(status),
                                             hip._stream(phi0.device)), 'nnhip_elastic_fold')

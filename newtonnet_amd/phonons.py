@@ -180,7 +180,10 @@ class PhononBands:
     modes        complex64 [Q sum d_b^2] or None: per (b, q) a [d_b, d_b] matrix, ROW k = mode k (mass-weighted, unit norm, the
                  component of largest magnitude real and positive)
     dynamical_matrix  complex64, laid out like modes, or None
-    sweeps, status    int32 [B, Q]  Jacobi sweeps used; status bit 0 = the sweep cap was hit, bit 2 = a bad mass
+    sweeps, status    int32 [B, Q]  Jacobi sweeps used; status bit 0 = the sweep cap was hit (a non-finite force constant ends
+                 there too), bit 1 = the device's cry_ptr gives the crystal more atoms than the host copy the launch was sized
+                 from (a C caller's mismatch; a Phonons keeps the two equal), bit 2 = a mass that is not positive and finite.
+                 With bit 1 or 2 nothing else of the problem is written
     q            fp64 numpy [Q, 3]; path (band_structure only): fp64 numpy [B, Q] cumulative length in 1 / Angstrom, ticks
     """
 

@@ -213,6 +213,39 @@ def relaxation_reference(phi0, lam, thr):
     return (p.T / w[keep][None, :]) @ p, int((~keep).sum()), int((w[keep] < 0).sum())
 
 
+def planted_eigenpairs(d, seed, n_zero=3, negative=False, kappa=100.0):
+    """(evals fp32 [d] ascending, Q fp32 [d,d] with ROW m = mode m, Lambda fp32 [d,6]) as nnhip_elastic_relax takes them: Q an
+    orthogonal matrix from a QR rounded to fp32, n_zero exact zeros among the eigenvalues, the others log-spaced over [1, kappa]
+    (the smallest negated with negative=True)"""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+    ev = np.zeros(d)
+    live = d - n_zero
+    if live > 0:
+        ev[n_zero:] = np.logspace(0.0, np.log10(kappa), live) if live > 1 else [1.0]
+        if negative:
+            ev[n_zero] = -ev[n_zero]
+    ev = np.sort(ev)
+    return ev.astype(np.float32), np.ascontiguousarray(Q.T.astype(np.float32)), rng.standard_normal((d, 6)).astype(np.float32)
+
+
+def relaxation_from_eigenpairs(evals, modes, lam, thr):
+    """(R [6,6], n_zero, n_negative, bound [6,6]) fp64 of nnhip_elastic_relax on the eigenpairs GIVEN (evals [d], modes [d,d] with
+    row m = mode m, lam [d,6]; nothing is diagonalised): R = sum over the modes with |lambda| > thr (a NaN is not) of
+    p_m p_m^T / lambda_m, p_m = q_m . Lambda.  bound: the rounding of R to fp32 plus d 2^-52 of the sum of the term magnitudes
+    (sum_c |q| |Lambda_I|)(sum_c |q| |Lambda_J|) / |lambda| -- the kernel sums in fp64."""
+    ev = np.asarray(evals, dtype=np.float64).reshape(-1)
+    Q = np.asarray(modes, dtype=np.float64).reshape(len(ev), len(ev))
+    L = np.asarray(lam, dtype=np.float64).reshape(len(ev), 6)
+    keep = np.abs(ev) > float(thr)                     # False for a NaN
+    R, T = np.zeros((6, 6)), np.zeros((6, 6))
+    for m in np.nonzero(keep)[0]:
+        p, a = Q[m] @ L, np.abs(Q[m]) @ np.abs(L)
+        R += np.outer(p, p) / ev[m]
+        T += np.outer(a, a) / abs(ev[m])
+    return R, int((~keep).sum()), int((ev[keep] < 0).sum()), EPS32 * np.abs(R) + len(ev) * 2.0 ** -52 * T
+
+
 def cubic_moduli(c11, c12, c44):
     """(K, G_V, G_R) of a cubic crystal"""
     return (c11 + 2.0 * c12) / 3.0, (c11 - c12 + 3.0 * c44) / 5.0, 5.0 * (c11 - c12) * c44 / (4.0 * c44 + 3.0 * (c11 - c12))

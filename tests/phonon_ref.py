@@ -191,3 +191,144 @@ def random_crystal(n, S, seed, scale=1.0):
 def supercell_eigenvalues(H, masses, nR):
     """sorted eigenvalues of the supercell's mass-weighted matrix (masses of the primitive cell, repeated per copy)"""
     return np.linalg.eigvalsh(vr.mass_weighted(H, np.tile(np.asarray(masses, dtype=np.float64), nR)))
+
+
+# ---- planted crystals and the density-of-states yardstick of the stage tests (tests/test_hip_crystal_stages.py) ----------------
+
+_T27 = np.array(list(itertools.product((-1, 0, 1), repeat=3)), dtype=np.float64)
+
+
+def image_table_fast(pos, cell, S):
+    """image_table without the loops over the pairs: the same keys, the same candidates in the same (lexicographic) order and the
+    same tie rule, so the same lists (tests/test_phonon_host.py holds the two to each other)"""
+    pos, cell = np.asarray(pos, dtype=np.float64), np.asarray(cell, dtype=np.float64)
+    inv = np.linalg.inv(cell)
+    n = len(pos)
+    offs = np.array(lattice_offsets(S), dtype=np.float64).reshape(-1, 3)
+    frac = pos @ inv
+    fJ = (frac[None, :, :] + offs[:, None, :]).reshape(-1, 3)                                   # J = r n + j
+    x = fJ[None, :, None, :] - frac[:, None, None, :] + (_T27 * np.asarray(S, dtype=np.float64))[None, None, :, :]
+    dist = np.linalg.norm(x @ cell, axis=-1)
+    keep = dist <= dist.min(axis=-1, keepdims=True) * (1.0 + TIE_TOL)
+    return {(i, J): list(x[i, J][keep[i, J]]) for i in range(n) for J in range(fJ.shape[0])}
+
+
+STAGE_CELL = np.array([[7.9, 0.0, 0.0], [0.6, 8.3, 0.0], [-0.4, 0.7, 8.1]])      # mildly triclinic
+STAGE_SUPERCELLS = {1: (1, 1, 1), 8: (2, 2, 2), 9: (3, 1, 3), 12: (2, 3, 2), 27: (3, 3, 3)}
+STAGE_Q = np.array([[0.0, 0.0, 0.0], [0.5, 0.0, 0.0], [0.31, -0.17, 0.44], [-0.4375, 0.21, 0.093],
+                    [1e5 + 0.31, -3e4 - 0.17, 0.44]])     # the last: far outside the first zone (the fp64 phase reduction)
+GAUGE_Q = np.array([0.31, -0.17, 0.44])
+
+
+def stage_case(d, n_copies, seed=None):
+    """(fc fp32 [n,3,N,3], pos, cell, S, masses fp32) of a planted crystal with d = 3 n coordinates on a supercell of n_copies
+    cells: random force constants (not translation invariant: D is symmetrised), mixed masses, atoms anywhere in the cell"""
+    n, S = d // 3, STAGE_SUPERCELLS[n_copies]
+    rng = np.random.default_rng(1000 * d + n_copies if seed is None else seed)
+    fc = rng.standard_normal((n, 3, n * n_copies, 3)).astype(np.float32)
+    pos = rng.uniform(0.0, 1.0, (n, 3)) @ STAGE_CELL
+    m = rng.choice([1.008, 12.011, 15.999, 126.90], n).astype(np.float32)
+    return fc, pos, STAGE_CELL.copy(), S, m
+
+
+def gauge_case(A32):
+    """The symmetric fp32 matrix A32 [3n,3n] as the force constants of n atoms on S = (1,1,1) with unit masses, the atoms inside
+    [0, 0.4) of a cubic cell: every nearest image has T = 0, so D(q) = P^H A P with P = diag(exp(2 pi i q . f_i)) -- the spectrum
+    of A at every q, in a matrix that is genuinely complex."""
+    n = A32.shape[0] // 3
+    rng = np.random.default_rng(31 * n)
+    cell = 8.0 * np.eye(3)
+    pos = rng.uniform(0.0, 0.4, (n, 3)) @ cell
+    return np.ascontiguousarray(A32, dtype=np.float32).reshape(n, 3, n, 3), pos, cell, (1, 1, 1), np.ones(n, dtype=np.float32)
+
+
+def gauge_matrix(A, pos, cell, q):
+    """P^H A P of gauge_case, fp64"""
+    f = np.asarray(pos, dtype=np.float64) @ np.linalg.inv(cell)
+    p = np.repeat(np.exp(2j * np.pi * (f @ np.asarray(q, dtype=np.float64))), 3)
+    return p.conj()[:, None] * np.asarray(A, dtype=np.float64) * p[None, :]
+
+
+TIE_S = (2, 2, 2)
+TIE_CELL = np.diag([4.0, 8.0, 2.0])
+
+
+def tie_crystal():
+    """(fc, pos, cell, S, masses) of 11 atoms on a 2 x 2 x 2 supercell of an orthogonal cell with power-of-two lattice constants,
+    the positions exact binary fractions.  The copy of an atom one cell along k axes is exactly half a supercell vector away along
+    each of them (2, 4, 8 equally near images); atoms that share one, two coordinates do the same among themselves."""
+    frac = np.array([[1, 2, 3], [1, 9, 5], [1, 9, 12], [4, 2, 7], [6, 11, 7], [9, 4, 1], [9, 13, 1], [12, 6, 10], [14, 15, 2],
+                     [3, 8, 14], [7, 1, 9]], dtype=np.float64) / 16.0
+    rng = np.random.default_rng(811)
+    fc = rng.standard_normal((11, 3, 88, 3)).astype(np.float32)
+    m = rng.choice([1.008, 12.011, 15.999], 11).astype(np.float32)
+    return fc, frac @ TIE_CELL, TIE_CELL.copy(), TIE_S, m
+
+
+def multiplicities(table):
+    return sorted({len(v) for v in table.values()})
+
+
+def dos_counts(values, lo, hi, n_bins):
+    """int64 [n_bins]: the histogram of nnhip_phonon_dos in fp64 -- n_bins equal bins of [lo, hi], a value equal to hi in the last
+    bin, values outside (and NaN) not counted"""
+    f = np.asarray(values, dtype=np.float64).reshape(-1)
+    lo, hi = float(lo), float(hi)
+    out = np.zeros(n_bins, dtype=np.int64)
+    wbin = (hi - lo) / n_bins
+    for x in f:
+        if not (x >= lo and x <= hi):
+            continue
+        out[min(int(np.floor((x - lo) / wbin)), n_bins - 1)] += 1
+    return out
+
+
+def dos_quotient_margin(values, lo, hi, n_bins):
+    """smallest distance of a counted value's fp64 quotient (f - lo) / wbin from an integer"""
+    f = np.asarray(values, dtype=np.float64).reshape(-1)
+    f = f[(f >= float(lo)) & (f <= float(hi))]
+    k = (f - float(lo)) / ((float(hi) - float(lo)) / n_bins)
+    return float(np.abs(k - np.round(k)).min()) if f.size else np.inf
+
+
+def dos_values(n, lo, hi, n_bins, seed):
+    """n fp32 values, most inside [lo, hi], some outside either end, none whose quotient (f - lo) / wbin (fp64) lies within
+    8 eps32 n_bins of an integer (the fp32 rounding of the difference, the bin width and the quotient is 4 eps32 n_bins at most):
+    those are drawn again.  Returns (values, the margin asked for)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    margin = 8.0 * EPS32 * n_bins
+    wbin = (hi - lo) / n_bins
+    pad = 0.05 * (hi - lo)
+    v = rng.uniform(lo - pad, hi + pad, n).astype(np.float32)
+    for _ in range(100):
+        k = (v.astype(np.float64) - lo) / wbin
+        near = (np.abs(k - np.round(k)) <= margin) & (v >= lo) & (v <= hi)
+        if not near.any():
+            return v, margin
+        v[near] = rng.uniform(lo - pad, hi + pad, int(near.sum())).astype(np.float32)
+    raise RuntimeError('dos_values: no draw with the margin')
+
+
+def dos_gaussian(values, lo, hi, n_bins, width, with_model=False):
+    """fp64 [n_bins]: sum over the values of the unit Gaussian of standard deviation width at the bin centres lo + (k + 1/2) wbin.
+    with_model: also the elementwise fp32 error model of the kernel, in units of eps32 --
+        centre: 4 max(|lo|, |hi|) (the difference, the quotient, the product and the sum each round once);
+        u = (centre - x) / width: d_centre / width + 3 |u| (the difference, 1 / width, the product);
+        the exponent -u^2 / 2: |u| d_u + 2 u^2;  expf: 2 (its own error, relative), and the exponent's error times the term;
+        the fp64 sum rounded to fp32 once: 1 --
+    so per value  term (|u| d_centre / width + 5 u^2 + 2), summed, plus the result itself; and, not in units of eps32, the
+    smallest normal fp32 number per value and for the result (a term or a result below it may be flushed to zero)."""
+    f = np.asarray(values, dtype=np.float64).reshape(-1)
+    lo, hi, width = float(lo), float(hi), float(width)
+    wbin = (hi - lo) / n_bins
+    centres = lo + (np.arange(n_bins) + 0.5) * wbin
+    u = (centres[:, None] - f[None, :]) / width
+    norm = 1.0 / (width * np.sqrt(2.0 * np.pi))
+    terms = np.exp(-0.5 * u * u) * norm
+    out = terms.sum(axis=1)
+    if not with_model:
+        return out
+    dc = 4.0 * max(abs(lo), abs(hi))
+    model = EPS32 * ((terms * (np.abs(u) * dc / width + 5.0 * u * u + 2.0)).sum(axis=1) + out) + 2.0 ** -126 * (f.size * norm + 1.0)
+    return out, model

@@ -298,3 +298,33 @@ def test_planted_inputs_of_the_stage_test():
     phi0, lam = er.planted_phi0(3, seed=1)
     R, nz, nn = er.relaxation_reference(phi0, lam, 1e-6)
     assert np.abs(R - lam.T @ np.linalg.pinv(phi0, rcond=1e-9, hermitian=True) @ lam).max() <= 1e-10 * np.abs(R).max() and nn == 0
+
+
+def test_planted_eigenpairs_and_their_reference():
+    """tests/test_hip_crystal_stages.py hands nnhip_elastic_relax eigenpairs it planted: the reference that takes them as given
+    agrees with the one that diagonalises Q^T diag(lambda) Q (to the fp32 rounding of Q), counts what the kernel counts, and its
+    bound is dominated by the rounding of R"""
+    for d, kw in ((3, dict(n_zero=3)), (63, {}), (66, dict(negative=True)), (96, {})):
+        ev, Q, lam = er.planted_eigenpairs(d, seed=d, **kw)
+        assert ev.dtype == Q.dtype == lam.dtype == np.float32 and Q.shape == (d, d) and lam.shape == (d, 6)
+        assert np.all(np.diff(ev) >= 0) and np.abs(Q.astype(np.float64) @ Q.astype(np.float64).T - np.eye(d)).max() <= 4 * d * er.EPS32
+        R, nz, nn, bound = er.relaxation_from_eigenpairs(ev, Q, lam, 1e-3)
+        assert nz == 3 and nn == (1 if kw.get('negative') else 0) and np.array_equal(R, R.T)
+        assert np.all(bound >= er.EPS32 * np.abs(R)) and np.all(bound <= er.EPS32 * np.abs(R) + 1e-11 * max(np.abs(R).max(), 1e-300))
+        if d > 3:
+            phi0 = (Q.astype(np.float64).T * ev.astype(np.float64)[None, :]) @ Q.astype(np.float64)
+            R2, nz2, nn2 = er.relaxation_reference(0.5 * (phi0 + phi0.T), lam, 1e-3)
+            assert (nz2, nn2) == (nz, nn) and np.abs(R - R2).max() <= 100.0 * 8 * d * er.EPS32 * np.abs(R).max()
+        else:
+            assert np.count_nonzero(R) == 0
+    ev, Q, lam = er.planted_eigenpairs(63, seed=63)
+    base = er.relaxation_from_eigenpairs(ev, Q, lam, 1e-3)
+    # a mode exactly at the threshold, and a NaN eigenvalue, are left out and counted as zero
+    at = er.relaxation_from_eigenpairs(ev, Q, lam, float(ev[10]))
+    assert at[1] == 11 and at[2] == 0
+    bad = ev.copy()
+    bad[20] = np.nan
+    nan = er.relaxation_from_eigenpairs(bad, Q, lam, 1e-3)
+    p = Q[20].astype(np.float64) @ lam.astype(np.float64)
+    assert nan[1] == 4 and np.isfinite(nan[0]).all() and np.allclose(base[0] - nan[0], np.outer(p, p) / float(ev[20]), rtol=0, atol=1e-12)
+    assert er.relaxation_from_eigenpairs(np.zeros(0), np.zeros((0, 0)), np.zeros((0, 6)), 0.0)[:3:1][1:] == (0, 0)

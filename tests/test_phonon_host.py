@@ -252,3 +252,118 @@ def test_kernel_symbols_are_declared_listed_and_exported():
     one = ctypes.c_void_p(8)        # never dereferenced: the size check comes first
     rc = lib.nnhip_phonon_bands(one, one, one, host, one, one, one, one, None, one, 1, one, 1, one, None, None, one, one, None)
     assert rc == 2 and str(ph.max_dim()) in lib.nnhip_last_error().decode()
+
+
+# ---- the yardstick functions of tests/test_hip_crystal_stages.py --------------------------------------------------------------
+
+def test_vectorised_image_table_is_the_loop_version():
+    cases = [(pr.TRICLINIC_POS, pr.TRICLINIC_CELL, (3, 2, 3)), (pr.cubic_lattice()[1], pr.cubic_lattice()[2], pr.CUBIC_S),
+             pr.tie_crystal()[1:4], pr.stage_case(9, 12)[1:4], pr.stage_case(27, 8)[1:4]]
+    for pos, cell, S in cases:
+        slow, fast = pr.image_table(pos, cell, S), pr.image_table_fast(pos, cell, S)
+        assert list(slow) == list(fast)
+        for key in slow:
+            assert len(slow[key]) == len(fast[key]) >= 1
+            assert np.array_equal(np.array(slow[key]), np.array(fast[key])), key
+    # ... and the product's own table holds the same images for a large cell
+    fc, pos, cell, S, _ = pr.stage_case(ph.max_dim(), 9)
+    start, off = ph.image_table(pos, cell, S)
+    want = pr.image_table_fast(pos, cell, S)
+    N = fc.shape[2]
+    assert all(np.allclose(off[start[i * N + J]:start[i * N + J + 1]], np.array(want[(i, J)]), rtol=0, atol=1e-13) for (i, J) in want)
+
+
+def test_stage_grid_cases():
+    """the planted crystals of the dimension and copy grid: the shapes, the supercells' copy counts, and a far wave vector whose
+    phase the reference still resolves (q and q minus a reciprocal lattice vector give the same spectrum to 1e-9 of its scale:
+    the two D differ by the gauge exp(2 pi i G . (f_j - f_i)))"""
+    for nR, S in pr.STAGE_SUPERCELLS.items():
+        assert int(np.prod(S)) == nR == len(pr.lattice_offsets(S))
+    for d, nR in ((27, 8), (30, 9), (33, 12)):
+        fc, pos, cell, S, m = pr.stage_case(d, nR)
+        assert fc.shape == (d // 3, 3, d // 3 * nR, 3) and fc.dtype == np.float32 and m.dtype == np.float32 and len(set(m.tolist())) > 1
+        assert np.abs(cell - np.diag(np.diag(cell))).max() > 0.3
+    assert pr.STAGE_Q.shape == (5, 3) and np.abs(pr.STAGE_Q[4]).max() > 1e4
+    fc, pos, cell, S, m = pr.stage_case(9, 12)
+    table = pr.image_table_fast(pos, cell, S)
+    far = pr.dynamical_matrix(fc.astype(np.float64), pos, cell, S, m.astype(np.float64), pr.STAGE_Q[4], table)
+    near = pr.dynamical_matrix(fc.astype(np.float64), pos, cell, S, m.astype(np.float64), pr.STAGE_Q[4] - np.array([1e5, -3e4, 0.0]), table)
+    assert np.abs(np.linalg.eigvalsh(far) - np.linalg.eigvalsh(near)).max() <= 1e-9 * np.abs(near).max()
+    assert np.abs(far - near).max() > 0.1          # ... in another gauge
+
+
+@pytest.mark.parametrize('M', [30, 33])
+def test_hard_spectra_in_the_gauge_of_a_crystal(M):
+    """tests/vib_ref.hard_spectra as force constants (phonon_ref.gauge_case): the reference D(q) is P^H A P, so its spectrum is that
+    of A at every q, and at the generic q the planted full matrices have a large imaginary part"""
+    from tests import vib_ref as vr
+    for name, (lam, A64, A32) in vr.hard_spectra(M).items():
+        fc, pos, cell, S, m = pr.gauge_case(A32)
+        f = pos @ np.linalg.inv(cell)
+        assert f.min() >= 0.0 and f.max() < 0.4
+        table = pr.image_table(pos, cell, S)
+        assert all(len(v) == 1 and np.array_equal(v[0], f[J] - f[i]) for (i, J), v in table.items())          # T = 0 everywhere
+        A = A32.astype(np.float64)
+        scale = max(np.abs(A).max(), 1.0)
+        for q in (np.zeros(3), pr.GAUGE_Q):
+            D = pr.dynamical_matrix(fc.astype(np.float64), pos, cell, S, m.astype(np.float64), q, table)
+            assert np.abs(D - pr.gauge_matrix(A, pos, cell, q)).max() <= 1e-14 * scale
+            assert np.abs(np.linalg.eigvalsh(D) - np.linalg.eigvalsh(A)).max() <= 1e-13 * scale, name
+        if lam is not None:
+            print(f'M = {M} {name}: max |Im D| = {np.abs(D.imag).max():.3f}')
+            off = np.abs(A - np.diag(np.diag(A))).max()
+            assert np.abs(D.imag).max() >= 0.25 * off, name         # the gauge turns the couplings well away from the real axis
+            assert name in ('cluster', 'graded') or np.abs(D.imag).max() >= 0.1, name     # (those two have small couplings)
+            assert np.abs(pr.dynamical_matrix(fc.astype(np.float64), pos, cell, S, m.astype(np.float64), np.zeros(3), table).imag).max() == 0.0
+
+
+def test_tie_crystal_has_every_multiplicity():
+    fc, pos, cell, S, m = pr.tie_crystal()
+    assert fc.shape == (11, 3, 88, 3) and np.array_equal(pos @ np.linalg.inv(cell) * 16.0, np.round(pos @ np.linalg.inv(cell) * 16.0))
+    table = pr.image_table(pos, cell, S)
+    assert pr.multiplicities(table) == [1, 2, 4, 8] == pr.multiplicities(pr.image_table_fast(pos, cell, S))
+    offs = pr.lattice_offsets(S)
+    assert len(table[(0, 11 * offs.index((1, 0, 0)))]) == 2 and len(table[(0, 11 * offs.index((1, 1, 0)))]) == 4
+    assert len(table[(0, 11 * offs.index((1, 1, 1)))]) == 8
+    assert len(table[(0, 11 * offs.index((1, 0, 0)) + 1)]) == 2          # atoms 0 and 1 share their x: a tie between DIFFERENT atoms
+    assert len(table[(1, 11 * offs.index((1, 1, 0)) + 2)]) == 4          # atoms 1 and 2 share x and y
+    start, off = ph.image_table(pos, cell, S)
+    assert sorted(set(np.diff(start).tolist())) == [1, 2, 4, 8]
+    for (i, J), v in table.items():
+        assert np.array_equal(off[start[i * 88 + J]:start[i * 88 + J + 1]], np.array(v))
+
+
+def test_dos_yardstick_and_the_margin_of_its_inputs():
+    # exact cases: width 1/4, every edge exact
+    for n_bins in (1, 4, 257):
+        hi = n_bins / 4.0
+        v = np.array([0.0, hi, np.nextafter(np.float32(0.0), np.float32(-1.0)), np.nextafter(np.float32(hi), np.float32(np.inf)),
+                      np.nan, np.inf, -np.inf] + [k / 4.0 for k in range(n_bins)], dtype=np.float32)
+        c = pr.dos_counts(v, 0.0, hi, n_bins)
+        want = np.ones(n_bins, dtype=np.int64)
+        want[0] += 1
+        want[-1] += 1
+        assert np.array_equal(c, want)
+    rng = np.random.default_rng(0)
+    x = rng.uniform(-3.0, 7.0, 500)
+    edges = -3.0 + 10.0 / 50 * np.arange(51)
+    assert np.array_equal(pr.dos_counts(x, -3.0, 7.0, 50), np.histogram(x, bins=edges)[0])
+    for n_bins in (1, 255, 256, 257, 1000):
+        v, margin = pr.dos_values(600, -37.3, 912.7, n_bins, seed=n_bins)
+        lo, hi = np.float32(-37.3), np.float32(912.7)
+        assert v.dtype == np.float32 and margin == 8 * pr.EPS32 * n_bins
+        assert pr.dos_quotient_margin(v, lo, hi, n_bins) > margin
+        assert (v < lo).sum() >= 5 and (v > hi).sum() >= 5 and ((v >= lo) & (v <= hi)).sum() >= 400
+        assert pr.dos_counts(v, lo, hi, n_bins).sum() == ((v >= lo) & (v <= hi)).sum()
+    # the Gaussian form integrates to the number of values when the range holds them, and its error model is positive
+    g, model = pr.dos_gaussian(x, -13.0, 17.0, 3000, 0.5, with_model=True)
+    assert abs(g.sum() * 0.01 - 500) <= 1e-6 * 500 and (model > 0).all() and model.max() <= 1e-4 * g.max()
+
+
+def test_wrapper_takes_a_crystal_slot_without_atoms():
+    a, b = pr.stage_case(3, 1), pr.stage_case(6, 8)
+    p = ph.Phonons.from_force_constants([a[0], np.zeros((0, 3, 0, 3), np.float32), b[0]], np.ones(3, dtype=np.int64),
+                                        np.concatenate([a[1], b[1]]), np.stack([a[2], a[2], b[2]]), np.array([a[3], (2, 2, 2), b[3]]),
+                                        masses=np.concatenate([a[4], b[4]]), batch=np.array([0, 2, 2]), device='cpu')
+    assert p.counts == [1, 0, 2] and p.sc_counts == [1, 0, 16] and p.cry_ptr.tolist() == [0, 1, 1, 3]
+    assert p.img_ptr.tolist() == [0, 2, 3] and p.out_ptr.tolist() == [0, 9, 9]
