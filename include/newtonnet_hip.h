@@ -710,6 +710,36 @@ int nnhip_head_seed_tan(const float* e2, const float* de2, const float* w4, cons
 /* rb[p][0:nb] = rbf_e, rb[p][32:32+nb] = drbf_e dx_e for the owner edge of pair p ([P][64], zero padded) */
 int nnhip_pair_rbf(const float* rbf, const float* drbf, const float* tgeo, const int64_t* edge_index, const int32_t* pid,
                    int32_t n_edges, int32_t n_basis, float* rb, void* stream);
+/* ---- the last stage of "tangent over reverse" (csrc/hessian.hip; the strain seed and sum: csrc/elastic.hip), as nnhip_hessian_vp,
+ * nnhip_hessian_blocks and nnhip_strain_vp run them.  Each call checks its arguments before any launch (a refused call writes
+ * nothing); a zero size is NNHIP_OK without a launch. ---- */
+/* dg_u[e] = (< dgf[i][k], phi1[p] > + < gf[i][k], dphi1[p] >, 0) for every directed edge e of receiver i, p = pid[e]; zeros for a
+ * masked candidate (xg[e].x == the table's zero row; xg NULL: nothing is masked) */
+int nnhip_hvp_dgu(const float* gf, const float* dgf, const float* phi1, const float* dphi1, const int32_t* row_ptr,
+                  const int32_t* pid, const int32_t* xg, int32_t n_atoms, float* dg_u, void* stream);
+/* dg_x[e] = sum_f dg_eps[p][f] eps'_f(x) + g_eps[p][f] eps''_f(x) tgeo[e][3] on the owner edge (edge_index[0][e] < edge_index[1][e])
+ * of an unmasked pair with x = geo[e][3] / cutoff < 1, else 0; eps_f = sum_n edge_w[f][n] env(x) sin(freq_n x) / x evaluated
+ * analytically in fp64.  n_basis outside 1..NNHIP_MAX_NB: NNHIP_E_UNSUPPORTED. */
+int nnhip_hvp_dgx(const int64_t* edge_index, const int32_t* pid, const float* geo, const float* tgeo, const int32_t* xg,
+                  const float* g_eps, const float* dg_eps, const float* edge_w, const float* freq, int32_t n_basis, int32_t envelope,
+                  float cutoff, int32_t n_edges, float* dg_x, void* stream);
+/* dg_d[e] = the tangent of g_d = a u + g_u / r, a = g_x / cutoff - (g_u . u) / r (g_x [L][E], g_u [L][E][4] and their tangents summed
+ * over the n_layers layers) along tgeo = (du, dx = dr / cutoff), fourth component 0;  hv[i] = sum_{e in row i} dg_d[e] - dg_d[rev e] */
+int nnhip_hvp_out(const float* g_x, const float* g_u, const float* dg_x, const float* dg_u, const float* geo, const float* tgeo,
+                  const int32_t* row_ptr, const int32_t* rev, int32_t n_atoms, int32_t n_edges, int32_t n_layers, float cutoff,
+                  float* dg_d, float* hv, void* stream);
+/* pass k of nnhip_hessian_blocks: v[i] = e_(dir % 3) where atom i is local atom dir / 3 of its molecule b and dir < 3 n_b, else 0,
+ * dir = k n_rep + b / n_mol0;  blocks[blk_ptr[b % n_mol0] + (3 a + c) 3 n_b + dir] = hv[i][c] (nothing where dir >= 3 n_b) */
+int nnhip_hess_dirs(const int64_t* batch, const int32_t* mol_ptr, int32_t n_atoms, int32_t k, int32_t n_rep, int32_t n_mol0, float* v,
+                    void* stream);
+int nnhip_hess_scatter(const float* hv, const int64_t* batch, const int32_t* mol_ptr, const int64_t* blk_ptr, int32_t n_atoms,
+                       int32_t k, int32_t n_rep, int32_t n_mol0, float* blocks, void* stream);
+/* the seed of nnhip_strain_vp: tgeo[e] = (du, dx) of dd = eta (r u), eta = the strain eta6[batch[edge_index[0][e]]] as a matrix */
+int nnhip_strain_tan_geom(const int64_t* edge_index, const int64_t* batch, const float* geo, const float* eta6, int32_t n_edges,
+                          float cutoff, float* tgeo, void* stream);
+/* d2[b][I] = sum_ab (d eps_ab / d e_I) S_ab, S_ab = sum_e dg_d[e]_a r_e u_e,b over the edges of system b's rows (fp64 sums) */
+int nnhip_strain_born(const float* dg_d, const float* geo, const int32_t* row_ptr, const int32_t* mol_ptr, int32_t n_mol, float* d2,
+                      void* stream);
 /* Per-element sums of the first `width` (<= 128) columns of x[N][ldx], two deterministic passes through `scratch`
  * (nnhip_species_scratch_bytes(width)).  Up to two outputs, each a column range of the element table, and a plain total:
  *   out_k[zz][0:cols_k] (pitch ldo_k) = sum_{i: z_i = zz} x[i][c_k : c_k + cols_k];   total[0] = sum_i x[i][c_total]

@@ -213,6 +213,21 @@ int launch_strain_born(const float* dg_d, const float* geo, const int* row_ptr, 
   return NNHIP_OK;
 }
 
+// ---- per-stage exports (include/newtonnet_hip.h, "Per-stage entry points"): nnhip_strain_vp keeps calling the launchers ----
+extern "C" int nnhip_strain_tan_geom(const int64_t* edge_index, const int64_t* batch, const float* geo, const float* eta6,
+                                     int32_t n_edges, float cutoff, float* tgeo, void* stream) {
+  ARG_CHECK(n_edges >= 0 && cutoff > 0.f && (n_edges == 0 || (edge_index && batch && geo && eta6 && tgeo)), "nnhip_strain_tan_geom");
+  if (n_edges == 0) return NNHIP_OK;
+  return launch_strain_tan_geom(edge_index, batch, geo, eta6, n_edges, cutoff, tgeo, (hipStream_t)stream);
+}
+
+extern "C" int nnhip_strain_born(const float* dg_d, const float* geo, const int32_t* row_ptr, const int32_t* mol_ptr, int32_t n_mol,
+                                 float* d2, void* stream) {
+  ARG_CHECK(n_mol >= 0 && (n_mol == 0 || (dg_d && geo && row_ptr && mol_ptr && d2)), "nnhip_strain_born");
+  if (n_mol == 0) return NNHIP_OK;
+  return launch_strain_born(dg_d, geo, row_ptr, mol_ptr, n_mol, d2, (hipStream_t)stream);
+}
+
 extern "C" int nnhip_elastic_fold(const float* fc, const int64_t* fc_ptr, const int32_t* cry_ptr, const int32_t* sc_atoms,
                                   const int64_t* out_ptr, int32_t n_cry, float* phi0, int32_t* status, void* stream) {
   ARG_CHECK(n_cry >= 0 && (n_cry == 0 || (fc && fc_ptr && cry_ptr && sc_atoms && out_ptr && phi0 && status)), "nnhip_elastic_fold");

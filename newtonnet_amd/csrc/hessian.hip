@@ -289,3 +289,54 @@ int launch_hess_scatter(const float* hv, const int64_t* batch, const int* mol_pt
   LAUNCH_CHECK();
   return NNHIP_OK;
 }
+
+// ---- per-stage exports (include/newtonnet_hip.h, "Per-stage entry points"): thin wrappers over the launchers above; the drivers in
+// csrc/train_step.hip keep calling the launchers ----
+extern "C" int nnhip_hvp_dgu(const float* gf, const float* dgf, const float* phi1, const float* dphi1, const int32_t* row_ptr,
+                             const int32_t* pid, const int32_t* xg, int32_t n_atoms, float* dg_u, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && (n_atoms == 0 || (gf && dgf && phi1 && dphi1 && row_ptr && pid && dg_u)), "nnhip_hvp_dgu");
+  if (n_atoms == 0) return NNHIP_OK;
+  return launch_hvp_dgu(gf, dgf, phi1, dphi1, row_ptr, pid, xg, n_atoms, dg_u, (hipStream_t)stream);
+}
+
+extern "C" int nnhip_hvp_dgx(const int64_t* edge_index, const int32_t* pid, const float* geo, const float* tgeo, const int32_t* xg,
+                             const float* g_eps, const float* dg_eps, const float* edge_w, const float* freq, int32_t n_basis,
+                             int32_t envelope, float cutoff, int32_t n_edges, float* dg_x, void* stream) {
+  ARG_CHECK(n_edges >= 0 && cutoff > 0.f && envelope >= NNHIP_ENVELOPE_COSINE &&
+                (n_edges == 0 || (edge_index && pid && geo && tgeo && g_eps && dg_eps && edge_w && freq && dg_x)),
+            "nnhip_hvp_dgx");
+  if (n_basis < 1 || n_basis > NNHIP_MAX_NB) {
+    nnhip_set_error("nnhip_hvp_dgx: n_basis %d outside 1..%d", n_basis, NNHIP_MAX_NB);
+    return NNHIP_E_UNSUPPORTED;
+  }
+  if (n_edges == 0) return NNHIP_OK;
+  return launch_hvp_dgx(edge_index, pid, geo, tgeo, xg, g_eps, dg_eps, edge_w, freq, n_basis, envelope, cutoff, n_edges, dg_x,
+                        (hipStream_t)stream);
+}
+
+extern "C" int nnhip_hvp_out(const float* g_x, const float* g_u, const float* dg_x, const float* dg_u, const float* geo,
+                             const float* tgeo, const int32_t* row_ptr, const int32_t* rev, int32_t n_atoms, int32_t n_edges,
+                             int32_t n_layers, float cutoff, float* dg_d, float* hv, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && n_edges >= 0 && (n_edges == 0 || n_atoms > 0) && n_layers >= 1 && n_layers <= NNHIP_MAX_LAYERS &&
+                cutoff > 0.f && (n_edges == 0 || (g_x && g_u && dg_x && dg_u && geo && tgeo && rev && dg_d)) &&
+                (n_atoms == 0 || (row_ptr && hv)),
+            "nnhip_hvp_out");
+  if (n_atoms == 0) return NNHIP_OK;
+  return launch_hvp_out(g_x, g_u, dg_x, dg_u, geo, tgeo, row_ptr, rev, n_atoms, n_edges, n_layers, cutoff, dg_d, hv,
+                        (hipStream_t)stream);
+}
+
+extern "C" int nnhip_hess_dirs(const int64_t* batch, const int32_t* mol_ptr, int32_t n_atoms, int32_t k, int32_t n_rep,
+                               int32_t n_mol0, float* v, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && k >= 0 && n_rep >= 1 && n_mol0 >= 1 && (n_atoms == 0 || (batch && mol_ptr && v)), "nnhip_hess_dirs");
+  if (n_atoms == 0) return NNHIP_OK;
+  return launch_hess_dirs(batch, mol_ptr, n_atoms, k, n_rep, n_mol0, v, (hipStream_t)stream);
+}
+
+extern "C" int nnhip_hess_scatter(const float* hv, const int64_t* batch, const int32_t* mol_ptr, const int64_t* blk_ptr,
+                                  int32_t n_atoms, int32_t k, int32_t n_rep, int32_t n_mol0, float* blocks, void* stream) {
+  ARG_CHECK(n_atoms >= 0 && k >= 0 && n_rep >= 1 && n_mol0 >= 1 && (n_atoms == 0 || (hv && batch && mol_ptr && blk_ptr && blocks)),
+            "nnhip_hess_scatter");
+  if (n_atoms == 0) return NNHIP_OK;
+  return launch_hess_scatter(hv, batch, mol_ptr, blk_ptr, n_atoms, k, n_rep, n_mol0, blocks, (hipStream_t)stream);
+}

@@ -52,8 +52,10 @@ def _scat(src, index, n):
     return src.new_zeros((n,) + tuple(src.shape[1:])).index_add_(0, index, src)
 
 
-def train_grads(sd, z, pos, cell, batch, g_energy, g_forces, cutoff=5.0, activation='swish', keep=False):
-    """dL/dtheta for dL/dE = g_energy [B], dL/dF = g_forces [N,3].  Returns (energy, forces, {name: grad}[, stages])."""
+def train_grads(sd, z, pos, cell, batch, g_energy, g_forces, cutoff=5.0, activation='swish', keep=False, edge_dd=None):
+    """dL/dtheta for dL/dE = g_energy [B], dL/dF = g_forces [N,3].  Returns (energy, forces, {name: grad}[, stages]).
+    edge_dd [E,3]: the tangent of every edge's displacement vector in place of v_i - v_j (a homogeneous strain moves the
+    displacements, periodic shifts included, not the positions: csrc/elastic.hip)."""
     act, dact, d2act = ACTS[activation]
     dt = pos.dtype
     N, B = pos.shape[0], cell.shape[0]
@@ -137,6 +139,7 @@ def train_grads(sd, z, pos, cell, batch, g_energy, g_forces, cutoff=5.0, activat
         st['g_m'] = _scat(G * st['eps'] * m[j], i, N) + _scat(G * st['eps'] * m[i], j, N)
         st['g_eps'] = G * m[i] * m[j]
         g_x = (st['g_eps'] * st['deps']).sum(1, keepdim=True)
+        st['g_u'], st['g_x'] = g_u, g_x
         st['t_n'] = st['g_m'] @ P(l, 'message_nodepart.2.weight')
         st['g_hn'] = st['t_n'] * dact(st['hn'])
         GA = GA + st['g_hn'] @ P(l, 'message_nodepart.0.weight')
@@ -146,7 +149,7 @@ def train_grads(sd, z, pos, cell, batch, g_energy, g_forces, cutoff=5.0, activat
 
     # ---------------------------------------------------------------- sweep 3: tangent forward along v = -dL/dF
     v = -g_forces.to(dt)
-    dd = v[i] - v[j]
+    dd = v[i] - v[j] if edge_dd is None else edge_dd.to(dt)
     dr = (u * dd).sum(1, keepdim=True)
     du = (dd - u * dr) / r
     dx = dr / cutoff
@@ -230,7 +233,7 @@ def train_grads(sd, z, pos, cell, batch, g_energy, g_forces, cutoff=5.0, activat
     grads['embedding_layers.node_embedding.weight'] = _scat(dGA, z, 119)
     out = (energy, forces, grads)
     if keep:
-        S.update(layers=Ls, edge_index=ei, u=u, du=du, dx=dx, rbf=rbf, drbf=drbf, e1=e1, e2=e2, de1=de1, de2=de2,
+        S.update(layers=Ls, edge_index=ei, u=u, r=r, x=x, disp=disp, du=du, dx=dx, rbf=rbf, drbf=drbf, e1=e1, e2=e2, de1=de1, de2=de2,
                  g_e2=g_e2, dg_e2=dg_e2, g_e1=g_e1, dg_e1=dg_e1, GA0=GA0, dGA0=dGA, v=v)
         out = out + (S,)
     return out
