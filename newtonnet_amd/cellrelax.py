@@ -34,9 +34,12 @@ import torch
 from newtonnet_amd import hip
 from newtonnet_amd.dynamics import _mol_ptr
 from newtonnet_amd.npt import BAR, _per_system
-from newtonnet_amd.relax import check_arguments, check_form, check_inputs, check_run_arguments
+from newtonnet_amd.relax import check_arguments, check_form, check_inputs
+from newtonnet_amd.stepper import Stepper
 
-_TRAJ = ('traj_step', 'traj_pos', 'traj_cell', 'traj_force', 'traj_virial', 'traj_energy', 'traj_n_pairs')
+_F32 = torch.float32
+_TRAJ = (('pos', ('n_atoms', 3), _F32), ('cell', ('n_mol', 3, 3), _F32), ('force', ('n_atoms', 3), _F32),
+         ('virial', ('n_mol', 3, 3), _F32), ('energy', ('n_mol',), _F32), ('n_pairs', ('n_mol',), torch.int64))
 
 
 class CellRelaxResult:
@@ -58,8 +61,9 @@ class CellRelaxResult:
     def __init__(self, pos, cell, volume, energy, enthalpy, stress, fmax, converged, failed, n_steps):
         self.pos, self.cell, self.volume, self.energy, self.enthalpy = pos, cell, volume, energy, enthalpy
         self.stress, self.fmax, self.converged, self.failed, self.n_steps = stress, fmax, converged, failed, n_steps
-        for name in _TRAJ:
-            setattr(self, name, None)
+        self.traj_step = None
+        for name, _, _ in _TRAJ:
+            setattr(self, 'traj_' + name, None)
 
 
 def check_model(model, who):
@@ -95,7 +99,7 @@ def check_cell_arguments(n_mol, pressure, mask, hydrostatic, constant_volume, ce
     return P, bits, flags, cell_factor
 
 
-class CellRelaxation:
+class CellRelaxation(Stepper):
     """B periodic systems relaxed together on the device, atoms and cells.
 
     model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads and a 'virial' or 'stress' head.  z, pos, cell,
@@ -105,6 +109,7 @@ class CellRelaxation:
     fixed: bool [N]; a fixed atom keeps its reference-frame position, so it rides with the cell.  Every system needs
     det(cell) > 0 (checked once, at construction, with one host read).  Positions stay unwrapped.  form, wg_min_atoms: as for
     Relaxation ('wave', 'workgroup' or 'auto'; the threshold of 'auto' counts atoms)."""
+    NOUN, CHECK_ONLY, TRAJ = 'relaxations', hip.CELL_LBFGS_CHECK_ONLY, _TRAJ
 
     def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, pressure=0.0, mask=None,
                  hydrostatic=False, constant_volume=False, cell_factor=None, fixed=None, form='wave', wg_min_atoms=None):
@@ -114,13 +119,7 @@ class CellRelaxation:
         fmax, memory, maxstep, alpha = check_arguments(fmax, memory, maxstep, alpha)
         P, bits, flags, cell_factor = check_cell_arguments(B, pressure, mask, hydrostatic, constant_volume, cell_factor)
         self.form, self._wg_min_atoms = form, check_form(form, wg_min_atoms)
-        if not pos.is_cuda:
-            raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: move the model and the inputs to '
-                               '"cuda"')
-        dev = pos.device
-        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('fixed', fixed)):
-            if t is not None and t.device != dev:
-                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        dev = self._check_device(pos, z=z, cell=cell, batch=batch, fixed=fixed)
         if B and not bool((torch.linalg.det(cell.detach().double()) > 0).all().cpu()):       # (the one host read)
             raise ValueError('CellRelaxation needs periodic systems with det(cell) > 0 (a right-handed cell of positive volume)')
         # ---- state
@@ -131,7 +130,6 @@ class CellRelaxation:
         self._tol2 = float(np.float32(fmax * fmax))
         self._maxstep, self._alpha = float(np.float32(maxstep)), float(np.float32(alpha))
         self._bits, self._flags = bits, flags
-        self.step_count = 0
         R = N + 3 * B
         with torch.no_grad():
             f32 = dict(dtype=torch.float32, device=dev)
@@ -141,9 +139,8 @@ class CellRelaxation:
             self._c = torch.full((B,), cell_factor, **f32) if cell_factor is not None else counts.clamp(min=1.0)
             self._p = (P.to(dev) * BAR).to(torch.float32).contiguous()
             self._h0 = cell.detach().clone().contiguous()
-            # two buffers each of X, pos and cell: a step reads one set and writes the other, so the forward call queued on the
-            # set it read can still be repeated from it (NewtonNet._forward_deferred)
-            self._pos = [pos.detach().clone().contiguous(), torch.empty(N, 3, **f32)]
+            # two buffers each of X, pos and cell: a step reads one set and writes the other (Stepper._init_buffers)
+            self._init_buffers(pos.detach().clone().contiguous())
             self._cells = [self._h0.clone(), torch.empty(B, 3, 3, **f32)]
             # X = [q ; c F] per system with F = I: system b's rows are [mol_ptr[b] + 3 b, mol_ptr[b+1] + 3 b + 3)
             shift = 3 * batch.long()
@@ -153,11 +150,11 @@ class CellRelaxation:
             x0[self._atom_rows] = self._pos[0]
             x0[cell_rows.reshape(-1)] = (self._c[:, None, None] * torch.eye(3, **f32)).reshape(-1, 3)
             self._x = [x0, torch.empty(R, 3, **f32)]
-            self._cur = 0
 
             def ints():
                 return torch.zeros(B, dtype=torch.int32, device=dev)
             self._converged, self._n_steps, self._n_pairs, self._head = ints(), ints(), ints(), ints()
+            self._active = self._converged
             self._S = torch.zeros(memory, R, 3, **f32)
             self._Y = torch.zeros(memory, R, 3, **f32)
             self._rho = torch.zeros(B, memory, **f32)
@@ -165,7 +162,7 @@ class CellRelaxation:
             self._G = torch.zeros(R, 3, **f32)
             self._work = torch.empty(R, 3, **f32) if R > 64 else None
             self._fmax = torch.zeros(B, **f32)
-            self._force = self._energy = self._virial = None
+            self._virial = None
 
     # ------------------------------------------------------------------------------------------
     def _evaluate(self):
@@ -187,23 +184,9 @@ class CellRelaxation:
                             self._fmax, wg_min_atoms=self._wg_min_atoms)
         self._cur = other
 
-    def _ensure_state(self):
-        if self._force is None:
-            with torch.no_grad():
-                self._evaluate()
-
-    @property
-    def positions(self):
-        return self._pos[self._cur].detach().clone()
-
     @property
     def cell(self):
         return self._cells[self._cur].detach().clone()
-
-    @property
-    def forces(self):
-        self._ensure_state()
-        return self._force
 
     @property
     def virial(self):
@@ -211,65 +194,20 @@ class CellRelaxation:
         return self._virial
 
     @property
-    def potential_energy(self):
-        self._ensure_state()
-        return self._energy
-
-    @property
-    def n_steps(self):
-        return self._n_steps.long()
-
-    @property
     def n_pairs(self):
         return self._n_pairs.long()
 
     # ------------------------------------------------------------------------------------------
-    def run(self, max_steps: int, check_every: int = 10, record_every: int = 0) -> CellRelaxResult:
-        """Up to max_steps variable-cell L-BFGS steps of every system that has not converged, then the result at the state
-        reached.  check_every and record_every as for Relaxation.run: every check_every steps the host reads ONE number (0:
-        never); a converged system is frozen bit for bit, so check_every changes no bit of any result; record_every > 0 records
-        the steps record_every, 2 record_every, ... of this call that were taken, and the last one.  run(a); run(b) leaves the
-        bits of run(a + b)."""
-        max_steps, check_every, every = check_run_arguments(max_steps, check_every, record_every)
-        B, N, dev = self.n_mol, self.n_atoms, self._fmax.device
-        frames = []
-        with torch.no_grad():
-            self._ensure_state()
-            taken = 0
-            for k in range(1, max_steps + 1):
-                self._launch()
-                self._evaluate()
-                taken = k
-                if every and k % every == 0:
-                    frames.append(self._frame(k))
-                if check_every and k % check_every == 0 and int((self._converged == 0).sum()) == 0:
-                    break
-            if every and taken and (not frames or frames[-1][0] != self.step_count + taken):
-                frames.append(self._frame(taken))
-            self.step_count += taken
-            # the state reached: its forces and virial are evaluated already; a check-only launch measures fmax and marks what has
-            # converged there, and moves nothing (it copies X, positions and cells into the other buffers)
-            self._launch(hip.CELL_LBFGS_CHECK_ONLY)
-            cell = self._cells[self._cur].clone()
-            volume = torch.linalg.det(cell.double()).float() if B else torch.zeros(0, dtype=torch.float32, device=dev)
-            energy = self._energy.clone()
-            stress = -self._virial / volume[:, None, None] * (1.0 / BAR)
-            result = CellRelaxResult(self._pos[self._cur].clone(), cell, volume, energy, energy + self._p * volume, stress,
-                                     self._fmax.clone(), self._converged != 0, torch.isnan(self._fmax), self._n_steps.long())
-            if every:
-                if frames:
-                    result.traj_step = torch.tensor([f[0] for f in frames], dtype=torch.int64, device=dev)
-                    for j, name in enumerate(_TRAJ[1:], start=1):
-                        setattr(result, name, torch.stack([f[j] for f in frames]))
-                else:
-                    f32 = dict(dtype=torch.float32, device=dev)
-                    result.traj_step = torch.zeros(0, dtype=torch.int64, device=dev)
-                    result.traj_pos, result.traj_force = torch.zeros(0, N, 3, **f32), torch.zeros(0, N, 3, **f32)
-                    result.traj_cell, result.traj_virial = torch.zeros(0, B, 3, 3, **f32), torch.zeros(0, B, 3, 3, **f32)
-                    result.traj_energy = torch.zeros(0, B, **f32)
-                    result.traj_n_pairs = torch.zeros(0, B, dtype=torch.int64, device=dev)
-        return result
+    # run (Stepper.run): variable-cell L-BFGS steps of every system that has not converged; the check-only launch measures fmax
+    # at the state reached and marks what has converged there (it copies X, positions and cells into the other buffers)
+    def _frame(self):
+        return (self._pos[self._cur].clone(), self._cells[self._cur].clone(), self._force.clone(), self._virial.clone(),
+                self._energy.clone(), self._n_pairs.long())
 
-    def _frame(self, k):
-        return (self.step_count + k, self._pos[self._cur].clone(), self._cells[self._cur].clone(), self._force.clone(),
-                self._virial.clone(), self._energy.clone(), self._n_pairs.long())
+    def _result(self):
+        cell = self._cells[self._cur].clone()
+        volume = torch.linalg.det(cell.double()).float() if self.n_mol else torch.zeros(0, dtype=torch.float32, device=cell.device)
+        energy = self._energy.clone()
+        stress = -self._virial / volume[:, None, None] * (1.0 / BAR)
+        return CellRelaxResult(self._pos[self._cur].clone(), cell, volume, energy, energy + self._p * volume, stress,
+                               self._fmax.clone(), self._converged != 0, torch.isnan(self._fmax), self._n_steps.long())

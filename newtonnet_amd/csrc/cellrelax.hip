@@ -77,9 +77,6 @@ struct CellRelaxArgs {
   int wg_min_atoms;      // systems of at least this many atoms belong to cell_lbfgs_step_wg_kernel (<= 0: all)
 };
 
-using lbfgs_chain::dot3;
-using lbfgs_chain::load3;
-using lbfgs_chain::store3;
 
 __device__ __forceinline__ void cross3(const float* u, const float* v, float* c) {
   c[0] = __fmaf_rn(u[1], v[2], -__fmul_rn(u[2], v[1]));
@@ -115,7 +112,7 @@ struct CellPolicy {
   int atom_shift, cell_row0;      // 3 b;  the system's first cell row
   __device__ __forceinline__ void force(int i, float* f) const { load3(g.G, 3 * (size_t)i, f); }
   __device__ __forceinline__ bool is_free(int i) const {
-    return i >= cell_row0 || !g.free_mask || g.free_mask[i - atom_shift];
+    return i >= cell_row0 || ::is_free(g, i - atom_shift);
   }
   __device__ __forceinline__ void load_x(size_t o, float* x) const { load3(g.x_in, o, x); }
   __device__ __forceinline__ void store_x(size_t o, const float* x_out, const float*) const { store3(g.x_out, o, x_out); }
@@ -274,13 +271,7 @@ __device__ __forceinline__ void cell_system(const CellRelaxArgs& g, Team& team, 
   }
 }
 
-// which kernel a system belongs to (relax.hip's rule): the workgroup kernel takes the systems of at least wg_min_atoms ATOMS
-// (<= 0: all of them, and the wave kernel is not launched); a system whose mol_ptr leaves the arrays stays with the wave kernel
-// unless that is not launched.  The two kernels own disjoint systems and touch no word of the other's
-__device__ __forceinline__ bool wave_owns(int wg_min_atoms, int a0, int a1, bool bad_ptr) {
-  return wg_min_atoms > 0 && (bad_ptr || a1 - a0 < wg_min_atoms);
-}
-
+// (which of the two kernels below a system belongs to: lbfgs_chain::wave_owns; wg_min_atoms counts ATOMS, not generalised rows)
 __global__ void __launch_bounds__(CR_THREADS)
 cell_lbfgs_step_kernel(CellRelaxArgs g) {
   const int waves = CR_THREADS / 64;
@@ -288,7 +279,7 @@ cell_lbfgs_step_kernel(CellRelaxArgs g) {
   for (int b = blockIdx.x * waves + (threadIdx.x >> 6); b < g.n_mol; b += gridDim.x * waves) {   // (uniform over a wave)
     const int a0 = g.mol_ptr[b], a1 = g.mol_ptr[b + 1];
     const bool bad_ptr = a0 < 0 || a1 < a0 || a1 > g.n_atoms;
-    if (!wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
+    if (!lbfgs_chain::wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
     cell_system(g, team, b, a0, a1, bad_ptr);
   }
 }
@@ -305,7 +296,7 @@ cell_lbfgs_step_wg_kernel(CellRelaxArgs g) {
   for (int b = blockIdx.x; b < g.n_mol; b += gridDim.x) {
     const int a0 = g.mol_ptr[b], a1 = g.mol_ptr[b + 1];
     const bool bad_ptr = a0 < 0 || a1 < a0 || a1 > g.n_atoms;
-    if (wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
+    if (lbfgs_chain::wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
     cell_system(g, team, b, a0, a1, bad_ptr);
   }
 }

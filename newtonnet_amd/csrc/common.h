@@ -192,6 +192,9 @@ __device__ __forceinline__ float wave_sum(float v) {          // the total in ev
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_lane63(v)), 63));
 }
 
+// (host) a float argument of an entry point that must be a positive finite number
+inline bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
+
 // Block b is observed to run on XCD b % 8 (each XCD has a private 4 MiB L2).  Give every XCD a
 // contiguous range of tiles so that the rows a molecule's atoms gather from stay in one L2.
 // Bijective for any n_blocks.  A speed choice only: correctness never depends on placement.

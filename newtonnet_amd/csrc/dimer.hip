@@ -68,13 +68,6 @@ struct DimerArgs {
   int max_rotations, flags, n_mol, n_atoms, memory;
 };
 
-using lbfgs_chain::dot3;
-using lbfgs_chain::load3;
-using lbfgs_chain::store3;
-using lbfgs_chain::wave_max;
-using lbfgs_chain::wave_sum;
-
-__device__ __forceinline__ bool is_free(const DimerArgs& g, int i) { return !g.free_mask || g.free_mask[i]; }
 
 __device__ __forceinline__ float* vec(const DimerArgs& g, int row) { return g.vstate + row * (3 * (size_t)g.n_atoms); }
 
@@ -198,7 +191,7 @@ dimer_step_kernel(DimerArgs g) {
       masked_force(g, i, f);
       f2 = fmaxf(f2, dot3(f, f));
     }
-    const float fmax2 = wave_max(f2);
+    const float fmax2 = bfly_max(f2);
     const bool frozen = status != 0 || a1 == a0 || (g.flags & NNHIP_DIMER_CHECK_ONLY);
     if (phase == 0 && lane == 0) {                           // the probe is the centre: its fmax and energy
       g.fmax_out[b] = __fsqrt_rn(fmax2);
@@ -254,7 +247,7 @@ dimer_step_kernel(DimerArgs g) {
         for (int k = 0; k < 3; ++k) d[k] = __fsub_rn(f0[k], f[k]);
         acc = __fadd_rn(acc, dot3(d, t));
       }
-      const float Cs = __fdiv_rn(wave_sum(acc), g.delta);
+      const float Cs = __fdiv_rn(bfly_sum(acc), g.delta);
       const float a1c = __fdiv_rn(__fmaf_rn(b1, s2, __fsub_rn(C, Cs)), __fmul_rn(2.f, __fmul_rn(s1, s1)));   // 1 - c2 = 2 s1^2
       const float root = __fsqrt_rn(__fmaf_rn(a1c, a1c, __fmul_rn(b1, b1)));
       float cm2 = 1.f, sm2 = 0.f;
@@ -295,7 +288,7 @@ dimer_step_kernel(DimerArgs g) {
         storev(g, NNHIP_DIMER_V_THETA_ROT, i, tr);
         storev(g, NNHIP_DIMER_V_MODE, i, nw);
       }
-      const float norm = __fsqrt_rn(wave_sum(nn));
+      const float norm = __fsqrt_rn(bfly_sum(nn));
       if (norm > 0.f) {
         for (int i = a0 + lane; i < a1; i += 64) {
           if (!is_free(g, i)) continue;
@@ -324,7 +317,7 @@ dimer_step_kernel(DimerArgs g) {
       for (int k = 0; k < 3; ++k) gg[k] = __fsub_rn(f1[k], f0[k]);
       acc = __fadd_rn(acc, dot3(gg, n));
     }
-    const float gN = wave_sum(acc);
+    const float gN = bfly_sum(acc);
     C = __fdiv_rn(-gN, g.delta);
     // G of atom i from the stored rows: fma(-gN, N, F1 - F0)
     auto perp = [&](int i, float* gg, float* G) {
@@ -351,8 +344,8 @@ dimer_step_kernel(DimerArgs g) {
         num = __fadd_rn(num, dot3(G, d));
         den = __fadd_rn(den, dot3(go, go));
       }
-      num = wave_sum(num);
-      den = wave_sum(den);
+      num = bfly_sum(num);
+      den = bfly_sum(den);
       const float beta = den > 0.f ? fmaxf(0.f, __fdiv_rn(num, den)) : 0.f;
       const float bd = __fmul_rn(beta, R[NNHIP_DIMER_F_DNORM * B]);
       float dn = 0.f;
@@ -367,7 +360,7 @@ dimer_step_kernel(DimerArgs g) {
         dn = __fadd_rn(dn, dot3(D, n));
         storev(g, NNHIP_DIMER_V_THETA, i, D);
       }
-      dn = wave_sum(dn);
+      dn = bfly_sum(dn);
       float dg = 0.f;
       for (int i = a0 + lane; i < a1; i += 64) {
         if (!is_free(g, i)) continue;
@@ -381,7 +374,7 @@ dimer_step_kernel(DimerArgs g) {
         dd = __fadd_rn(dd, dot3(D, D));
         storev(g, NNHIP_DIMER_V_THETA, i, D);
       }
-      dg = wave_sum(dg);
+      dg = bfly_sum(dg);
       plain = !(dg > 0.f);
     }
     if (plain) {
@@ -394,7 +387,7 @@ dimer_step_kernel(DimerArgs g) {
         storev(g, NNHIP_DIMER_V_THETA, i, G);
       }
     }
-    const float d_norm = __fsqrt_rn(wave_sum(dd));
+    const float d_norm = __fsqrt_rn(bfly_sum(dd));
     float b1 = 0.f, r = 0.f, c2 = 1.f, s2 = 0.f;
     if (d_norm > 0.f) {
       float gt = 0.f;
@@ -408,7 +401,7 @@ dimer_step_kernel(DimerArgs g) {
         gt = __fadd_rn(gt, dot3(gg, th));
         storev(g, NNHIP_DIMER_V_THETA, i, th);
       }
-      b1 = __fdiv_rn(-wave_sum(gt), g.delta);
+      b1 = __fdiv_rn(-bfly_sum(gt), g.delta);
       r = __fdiv_rn(-b1, fabsf(C));
       const float t = __fmaf_rn(r, r, 1.f);
       if (C == 0.f || !(t <= 3.402823466e38f)) {
@@ -454,7 +447,7 @@ dimer_step_kernel(DimerArgs g) {
     // no pending pair
     const bool concave = C < 0.f;
     if (!concave) np = 0;
-    const TranslatePolicy policy{g, wave_sum(pa), concave};
+    const TranslatePolicy policy{g, bfly_sum(pa), concave};
     lbfgs_chain::History h;
     h.S = g.S, h.Y = g.Y, h.rho = g.rho, h.f_prev = vec(g, NNHIP_DIMER_V_F_PREV), h.work = g.work;
     h.alpha = g.alpha, h.maxstep = g.maxstep, h.memory = m, h.n_atoms = g.n_atoms;
@@ -469,8 +462,6 @@ dimer_step_kernel(DimerArgs g) {
     }
   }
 }
-
-__host__ bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
 
 }  // namespace
 

@@ -23,6 +23,7 @@
 //   scalars  arc += sqrt(M);  Delta = sqrt(D2);  Delta > 0:  dt_next = dt cbrt(Delta0 / Delta) clamped into [0.5 dt, 2 dt], then
 //            into [dt_min, dt_max];  otherwise dt_next = dt
 #include "common.h"
+#include "optim_rows.h"
 
 namespace {
 
@@ -50,36 +51,6 @@ struct IrcArgs {
   float v0, delta0, dt_min, dt_max, tol2;
   int flags, n_mol, n_atoms;
 };
-
-__device__ __forceinline__ float dot3(const float* a, const float* b) {
-  return __fmaf_rn(a[2], b[2], __fmaf_rn(a[1], b[1], __fmul_rn(a[0], b[0])));
-}
-
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s = __fadd_rn(s, __shfl_xor(s, d, 64));
-  return s;
-}
-
-__device__ __forceinline__ float wave_max(float s) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s = fmaxf(s, __shfl_xor(s, d, 64));
-  return s;
-}
-
-__device__ __forceinline__ void load3(const float* p, size_t o, float* v) {
-  v[0] = p[o];
-  v[1] = p[o + 1];
-  v[2] = p[o + 2];
-}
-
-__device__ __forceinline__ void store3(float* p, size_t o, const float* v) {
-  p[o] = v[0];
-  p[o + 1] = v[1];
-  p[o + 2] = v[2];
-}
-
-__device__ __forceinline__ bool is_free(const IrcArgs& g, int i) { return !g.free_mask || g.free_mask[i]; }
 
 // a = (c f) / m of a FREE atom from its force f and mass m and, when `finish`, w = the velocity before damping (else w = vel)
 __device__ __forceinline__ void accel_and_velocity(const IrcArgs& g, size_t o, const float* f, float m, const float* vel,
@@ -133,9 +104,9 @@ irc_step_kernel(IrcArgs g) {
         vv_acc = __fadd_rn(vv_acc, dot3(w, w));
       }
     }
-    const float fmax2 = wave_max(f2);
-    const float P = wave_sum(p_acc);
-    const float vv = wave_sum(vv_acc);
+    const float fmax2 = bfly_max(f2);
+    const float P = bfly_sum(p_acc);
+    const float vv = bfly_sum(vv_acc);
     // state words no step can have left behind, a mol_ptr that leaves the arrays or a free atom without a usable mass: the
     // molecule is not touched, fmax_out = NaN
     const bool bad = bad_ptr || __any(bad_mass) || status < 0 || status > 2 || steps < 0 || !(dt >= g.dt_min && dt <= g.dt_max);
@@ -210,8 +181,8 @@ irc_step_kernel(IrcArgs g) {
       store3(g.v_prev, o, v);
       store3(g.a_prev, o, a);
     }
-    const float ds = __fsqrt_rn(wave_sum(m_acc));
-    const float delta = __fsqrt_rn(wave_sum(d_acc));
+    const float ds = __fsqrt_rn(bfly_sum(m_acc));
+    const float delta = __fsqrt_rn(bfly_sum(d_acc));
     float dt_next = dt;
     if (finish && delta > 0.f) {
       dt_next = __fmul_rn(dt, cbrtf(__fdiv_rn(g.delta0, delta)));
@@ -226,8 +197,6 @@ irc_step_kernel(IrcArgs g) {
     }
   }
 }
-
-__host__ bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }
 
 }  // namespace
 

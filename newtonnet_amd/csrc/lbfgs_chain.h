@@ -26,6 +26,7 @@
 //   void store_x(size_t o, const float* x_out, const float* x) const     where the new point goes
 #pragma once
 #include "common.h"
+#include "optim_rows.h"
 
 namespace lbfgs_chain {
 
@@ -39,22 +40,6 @@ struct History {
   int memory, n_atoms;
 };
 
-__device__ __forceinline__ float dot3(const float* a, const float* b) {
-  return __fmaf_rn(a[2], b[2], __fmaf_rn(a[1], b[1], __fmul_rn(a[0], b[0])));
-}
-
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s = __fadd_rn(s, __shfl_xor(s, d, 64));
-  return s;
-}
-
-__device__ __forceinline__ float wave_max(float s) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s = fmaxf(s, __shfl_xor(s, d, 64));
-  return s;
-}
-
 // ---- the teams.  A team gives: STRIDE (its size; member `first()` owns the rows a0 + first(), + STRIDE, ... in EVERY sweep),
 // lane() (the place in the wave: the first loop's coefficient a_j lives in lane j of every wave), sum / sum3 / max (the reductions;
 // every member holds the same bits afterwards) and share_rows (three rows of three floats from their owners to every member).
@@ -65,13 +50,13 @@ struct WaveTeam {
   int l;
   __device__ __forceinline__ int first() const { return l; }
   __device__ __forceinline__ int lane() const { return l; }
-  __device__ __forceinline__ float sum(float s) { return wave_sum(s); }
+  __device__ __forceinline__ float sum(float s) { return bfly_sum(s); }
   __device__ __forceinline__ void sum3(float& a, float& b, float& c) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_sum(c);
+    a = bfly_sum(a);
+    b = bfly_sum(b);
+    c = bfly_sum(c);
   }
-  __device__ __forceinline__ float max(float s) { return wave_max(s); }
+  __device__ __forceinline__ float max(float s) { return bfly_max(s); }
   __device__ __forceinline__ void share_rows(const int* owner, float (*v)[3]) {
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -124,7 +109,7 @@ struct BlockTeam {
   }
   __device__ __forceinline__ float sum(float s) {
     float* buf = red + phase * 3 * WAVES;
-    s = wave_sum(s);
+    s = bfly_sum(s);
     if (lane() == 0) buf[tid >> 6] = s;
     __syncthreads();
     phase ^= 1;
@@ -132,9 +117,9 @@ struct BlockTeam {
   }
   __device__ __forceinline__ void sum3(float& a, float& b, float& c) {
     float* buf = red + phase * 3 * WAVES;
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_sum(c);
+    a = bfly_sum(a);
+    b = bfly_sum(b);
+    c = bfly_sum(c);
     if (lane() == 0) {
       buf[tid >> 6] = a;
       buf[WAVES + (tid >> 6)] = b;
@@ -148,7 +133,7 @@ struct BlockTeam {
   }
   __device__ __forceinline__ float max(float s) {
     float* buf = red + phase * 3 * WAVES;
-    s = wave_max(s);
+    s = bfly_max(s);
     if (lane() == 0) buf[tid >> 6] = s;
     __syncthreads();
     phase ^= 1;
@@ -170,16 +155,12 @@ struct BlockTeam {
   }
 };
 
-__device__ __forceinline__ void load3(const float* p, size_t o, float* v) {
-  v[0] = p[o];
-  v[1] = p[o + 1];
-  v[2] = p[o + 2];
-}
-
-__device__ __forceinline__ void store3(float* p, size_t o, const float* v) {
-  p[o] = v[0];
-  p[o + 1] = v[1];
-  p[o + 2] = v[2];
+// which kernel a system [a0, a1) belongs to when a launch is the pair of a WaveTeam kernel and a BlockTeam kernel (relax.hip,
+// cellrelax.hip): the workgroup kernel takes the systems of at least wg_min_atoms atoms (wg_min_atoms <= 0: all of them, and the
+// wave kernel is not launched); a system whose mol_ptr leaves the arrays has no atom count and stays with the wave kernel unless
+// that is not launched.  The two kernels own disjoint systems and touch no word of the other's
+__device__ __forceinline__ bool wave_owns(int wg_min_atoms, int a0, int a1, bool bad_ptr) {
+  return wg_min_atoms > 0 && (bad_ptr || a1 - a0 < wg_min_atoms);
 }
 
 // the two-loop work vector of one team member: its single atom's three values in registers (REG: molecules of up to Team::STRIDE

@@ -37,6 +37,7 @@
 //     v = fma(dt, F, v)  -> vel;   dr = dt v;   DD = SUM_i sum_l dot3(dr, dr);  nd = sqrt(DD);  nd > maxstep:  dr = dr (maxstep / nd)
 //     pos_out = pos_in + dr   (endpoints and fixed atoms: pos_in itself)
 #include "common.h"
+#include "optim_rows.h"
 
 namespace {
 
@@ -65,36 +66,6 @@ struct NebArgs {
   float spring, tol2, climb2, dt_start, dt_max, f_inc, f_dec, a_start, f_a, maxstep;
   int n_min, flags, n_bands, n_mol, n_atoms;
 };
-
-__device__ __forceinline__ float dot3(const float* a, const float* b) {
-  return __fmaf_rn(a[2], b[2], __fmaf_rn(a[1], b[1], __fmul_rn(a[0], b[0])));
-}
-
-__device__ __forceinline__ float bfly_sum(float s) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s = __fadd_rn(s, __shfl_xor(s, d, 64));
-  return s;
-}
-
-__device__ __forceinline__ float bfly_max(float s) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s = fmaxf(s, __shfl_xor(s, d, 64));
-  return s;
-}
-
-__device__ __forceinline__ void load3(const float* p, size_t o, float* v) {
-  v[0] = p[o];
-  v[1] = p[o + 1];
-  v[2] = p[o + 2];
-}
-
-__device__ __forceinline__ void store3(float* p, size_t o, const float* v) {
-  p[o] = v[0];
-  p[o + 1] = v[1];
-  p[o + 2] = v[2];
-}
-
-__device__ __forceinline__ bool is_free(const NebArgs& g, int i) { return !g.free_mask || g.free_mask[i]; }
 
 __global__ void __launch_bounds__(NEB_THREADS)
 neb_step_kernel(NebArgs g) {

@@ -59,9 +59,6 @@ struct RelaxArgs {
   int wg_min_atoms;      // systems of at least this many atoms belong to lbfgs_step_wg_kernel (<= 0: all)
 };
 
-using lbfgs_chain::dot3;
-using lbfgs_chain::load3;
-using lbfgs_chain::store3;
 
 // the optimiser's view of this launch (lbfgs_chain.h): the model's forces, masked; the step goes from pos_in to pos_out
 struct RelaxPolicy {
@@ -70,7 +67,7 @@ struct RelaxPolicy {
     load3(g.force, 3 * (size_t)i, f);
     if (g.free_mask && !g.free_mask[i]) f[0] = f[1] = f[2] = 0.f;
   }
-  __device__ __forceinline__ bool is_free(int i) const { return !g.free_mask || g.free_mask[i]; }
+  __device__ __forceinline__ bool is_free(int i) const { return ::is_free(g, i); }
   __device__ __forceinline__ void load_x(size_t o, float* x) const { load3(g.pos_in, o, x); }
   __device__ __forceinline__ void store_x(size_t o, const float* x_out, const float*) const { store3(g.pos_out, o, x_out); }
 };
@@ -120,13 +117,6 @@ __device__ __forceinline__ void relax_system(const RelaxArgs& g, const RelaxPoli
   }
 }
 
-// which kernel a system belongs to: the workgroup kernel takes the systems of at least wg_min_atoms atoms (wg_min_atoms <= 0: all of
-// them, and the wave kernel is not launched); a system whose mol_ptr leaves the arrays has no atom count and stays with the wave
-// kernel unless that is not launched.  The two kernels own disjoint systems and touch no word of the other's
-__device__ __forceinline__ bool wave_owns(int wg_min_atoms, int a0, int a1, bool bad_ptr) {
-  return wg_min_atoms > 0 && (bad_ptr || a1 - a0 < wg_min_atoms);
-}
-
 __global__ void __launch_bounds__(RX_THREADS)
 lbfgs_step_kernel(RelaxArgs g) {
   const int waves = RX_THREADS / 64;
@@ -135,7 +125,7 @@ lbfgs_step_kernel(RelaxArgs g) {
   for (int b = blockIdx.x * waves + (threadIdx.x >> 6); b < g.n_mol; b += gridDim.x * waves) {   // (uniform over a wave)
     const int a0 = g.mol_ptr[b], a1 = g.mol_ptr[b + 1];
     const bool bad_ptr = a0 < 0 || a1 < a0 || a1 > g.n_atoms;
-    if (!wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
+    if (!lbfgs_chain::wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
     relax_system(g, policy, team, b, a0, a1, bad_ptr);
   }
 }
@@ -153,7 +143,7 @@ lbfgs_step_wg_kernel(RelaxArgs g) {
   for (int b = blockIdx.x; b < g.n_mol; b += gridDim.x) {
     const int a0 = g.mol_ptr[b], a1 = g.mol_ptr[b + 1];
     const bool bad_ptr = a0 < 0 || a1 < a0 || a1 > g.n_atoms;
-    if (wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
+    if (lbfgs_chain::wave_owns(g.wg_min_atoms, a0, a1, bad_ptr)) continue;
     relax_system(g, policy, team, b, a0, a1, bad_ptr);
   }
 }

@@ -25,11 +25,11 @@ import math
 import numpy as np
 import torch
 
-from newtonnet_amd import hip
+from newtonnet_amd import hip, stepper
 from newtonnet_amd.dynamics import _mol_ptr, _molecule_sums
 from newtonnet_amd.relax import check_arguments as check_lbfgs_arguments
 from newtonnet_amd.relax import check_inputs
-from newtonnet_amd.vibrations import _check_solver, table_masses
+from newtonnet_amd.vibrations import _check_solver, lowest_mode_direction, table_masses
 
 CENTER, ENDPOINT, TRIAL = 0, 1, 2          # what a molecule's probe is (the `phase` of the kernel's contract)
 
@@ -70,13 +70,10 @@ def check_arguments(fmax, dimer_length, rotation_tolerance, max_rotations, memor
 
 
 def check_run_arguments(max_evaluations, check_every, record_every):
-    for name, v in (('max_evaluations', max_evaluations), ('check_every', check_every), ('record_every', record_every)):
-        if int(v) != v or v < 0:
-            raise ValueError(f'{name}: an integer >= 0 expected (got {v!r})')
-    return int(max_evaluations), int(check_every), int(record_every)
+    return stepper.check_run_arguments(max_evaluations, check_every, record_every, 'max_evaluations')
 
 
-class SaddleSearch:
+class SaddleSearch(stepper.Stepper):
     """The dimers of B molecules, searching together on the device.
 
     model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads.  z, pos, cell, batch: as for model(...), on the
@@ -95,6 +92,10 @@ class SaddleSearch:
 
     Periodic molecules: the cell is fixed and positions stay unwrapped; the model's neighbor list takes the minimum image itself,
     the dimer's endpoints are plain Cartesian displacements."""
+    NOUN, CHECK_ONLY = 'saddle searches', hip.DIMER_CHECK_ONLY
+    TRAJ = (('pos', ('n_atoms', 3), torch.float32), ('force', ('n_atoms', 3), torch.float32), ('energy', ('n_mol',), torch.float32),
+            ('center', ('n_atoms', 3), torch.float32), ('mode', ('n_atoms', 3), torch.float32), ('phase', ('n_mol',), torch.int64),
+            ('curvature', ('n_mol',), torch.float32))
 
     def __init__(self, model, z, pos, cell, batch, direction=None, fmax=0.001, dimer_length=0.01, rotation_tolerance=5.0,
                  max_rotations=8, memory=16, maxstep=0.2, alpha=70.0, fixed=None, solver='lds'):
@@ -106,13 +107,7 @@ class SaddleSearch:
         fmax, dimer_length, rotation_tolerance, max_rotations, memory, maxstep, alpha = check_arguments(
             fmax, dimer_length, rotation_tolerance, max_rotations, memory, maxstep, alpha)
         solver = _check_solver(solver)
-        if not pos.is_cuda:
-            raise RuntimeError('newtonnet_amd saddle searches run on an MI355X (ROCm) device only: move the model and the inputs '
-                               'to "cuda"')
-        dev = pos.device
-        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('fixed', fixed), ('direction', direction)):
-            if t is not None and t.device != dev:
-                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        dev = self._check_device(pos, z=z, cell=cell, batch=batch, fixed=fixed, direction=direction)
         # ---- state
         f32 = np.float32
         self.model, self.z, self.cell, self.batch = model, z, cell, batch
@@ -123,16 +118,10 @@ class SaddleSearch:
         self._delta = float(f32(dimer_length))
         self._rot_tol = float(f32(math.tan(2.0 * math.radians(rotation_tolerance))))
         self._maxstep, self._alpha = float(f32(maxstep)), float(f32(alpha))
-        self.step_count = 0                                  # evaluations consumed since the search was made
         with torch.no_grad():
             free = torch.ones(N, dtype=torch.bool, device=dev) if fixed is None else ~fixed
             if direction is None:
-                m = table_masses(z)
-                nm = model.normal_modes(z, pos.detach(), cell, batch, masses=m, solver=solver)
-                ptr = _mol_ptr(batch, B).long()
-                local = torch.arange(N, device=dev) - ptr[batch.long()]
-                q = nm.modes[(nm.blk_ptr[batch.long()] + 3 * local)[:, None] + torch.arange(3, device=dev)]
-                u = q.double() / m.double().sqrt()[:, None]
+                u, _ = lowest_mode_direction(model, z, pos, cell, batch, table_masses(z), solver)
             else:
                 u = direction.detach().double()
             u = u * free[:, None]
@@ -144,12 +133,10 @@ class SaddleSearch:
                 raise ValueError('direction: a molecule has a direction that vanishes on its free atoms (or is not finite)')
             mode = (u / norm2.clamp_min(1e-300).sqrt()[batch.long()][:, None]).float()
             self._free = None if fixed is None else free.contiguous()
-            # two probe buffers: a launch reads one and writes the other, so the forward call queued on the one it read can still
-            # be repeated from it (NewtonNet._forward_deferred)
-            self._pos = [pos.detach().clone().contiguous(), torch.empty(N, 3, dtype=torch.float32, device=dev)]
-            self._cur = 0
+            self._init_buffers(pos.detach().clone().contiguous())     # (the probes; step_count counts evaluations consumed)
             self._mol_ptr = _mol_ptr(batch, B)
             self._istate = torch.zeros(hip.DIMER_N_INT, B, dtype=torch.int32, device=dev)
+            self._active = self._istate[hip.DIMER_I['status']]
             self._fstate = torch.zeros(hip.DIMER_N_FLOAT, B, dtype=torch.float32, device=dev)
             self._vstate = torch.zeros(hip.DIMER_N_VEC, N, 3, dtype=torch.float32, device=dev)
             self._vstate[hip.DIMER_V['center']] = self._pos[0]
@@ -160,16 +147,8 @@ class SaddleSearch:
             self._work = torch.empty(N, 3, dtype=torch.float32, device=dev) if N > 64 else None
             self._fmax = torch.zeros(B, dtype=torch.float32, device=dev)
             self._e_center = torch.zeros(B, dtype=torch.float32, device=dev)
-            self._force = self._energy = None
 
     # ------------------------------------------------------------------------------------------
-    def _evaluate(self):
-        """forces and energies at the current probes.  Touching gradient_force settles the deferred record of the call -- a
-        repeat, if one is needed, happens HERE, from the buffer the call was queued with and before any kernel writes a buffer"""
-        out = self.model(self.z, self._pos[self._cur], self.cell, self.batch)
-        self._force = out.gradient_force
-        self._energy = out.energy
-
     def _launch(self, flags=0):
         """one launch: reads the current probes and their forces, writes the next probes into the other buffer, the buffers swap"""
         other = 1 - self._cur
@@ -178,11 +157,6 @@ class SaddleSearch:
                        self._fstate, self._vstate, self._S, self._Y, self._rho, self._work, self._pos[other], self._fmax,
                        self._e_center)
         self._cur = other
-
-    def _ensure_state(self):
-        if self._force is None:
-            with torch.no_grad():
-                self._evaluate()
 
     def _int(self, name):
         return self._istate[hip.DIMER_I[name]].long()
@@ -214,48 +188,15 @@ class SaddleSearch:
 
     # ------------------------------------------------------------------------------------------
     def run(self, max_evaluations: int, check_every: int = 10, record_every: int = 0) -> SaddleResult:
-        """Up to max_evaluations force evaluations (launches) of every molecule that has not converged, then the result at the
-        centres reached.  Every check_every evaluations the host reads ONE number, the count of molecules still searching, and
-        stops when it is 0 (check_every = 0: never reads, always max_evaluations launches).  A converged molecule is frozen bit for
-        bit, so check_every changes no bit of any result.  record_every > 0 records the evaluations record_every, 2 record_every,
-        ... of this call that were made, and the last one; recording changes no bit either.  May be called again to continue:
-        run(a); run(b) leaves the bits of run(a + b)."""
-        max_evaluations, check_every, every = check_run_arguments(max_evaluations, check_every, record_every)
-        B, N, dev = self.n_mol, self.n_atoms, self._fmax.device
-        status = self._istate[hip.DIMER_I['status']]
-        frames = []
-        with torch.no_grad():
-            self._ensure_state()
-            taken = 0
-            for k in range(1, max_evaluations + 1):
-                self._launch()
-                self._evaluate()
-                taken = k
-                if every and k % every == 0:
-                    frames.append(self._frame(k))
-                if check_every and k % check_every == 0 and int((status == 0).sum()) == 0:
-                    break
-            if every and taken and (not frames or frames[-1][0] != self.step_count + taken):
-                frames.append(self._frame(taken))
-            self.step_count += taken
-            # the state at the probes reached: their forces are evaluated already; a check-only launch measures fmax and the energy
-            # of every molecule whose probe is its centre, sets no flag and moves nothing (it copies the probes into the other buffer)
-            self._launch(hip.DIMER_CHECK_ONLY)
-            result = SaddleResult(self.positions, self.mode, self._e_center.clone(), self._fmax.clone(), self.curvature,
-                                  status != 0, self.n_steps, self.n_evaluations, self.n_rotations)
-            if every:
-                if frames:
-                    result.traj_step = torch.tensor([f[0] for f in frames], dtype=torch.int64, device=dev)
-                    (result.traj_pos, result.traj_force, result.traj_energy, result.traj_center, result.traj_mode, result.traj_phase,
-                     result.traj_curvature) = (torch.stack([f[j] for f in frames]) for j in range(1, 8))
-                else:
-                    result.traj_step = torch.zeros(0, dtype=torch.int64, device=dev)
-                    result.traj_pos, result.traj_force, result.traj_center, result.traj_mode = (
-                        torch.zeros(0, N, 3, dtype=torch.float32, device=dev) for _ in range(4))
-                    result.traj_energy, result.traj_curvature = (torch.zeros(0, B, dtype=torch.float32, device=dev) for _ in range(2))
-                    result.traj_phase = torch.zeros(0, B, dtype=torch.int64, device=dev)
-        return result
+        """Stepper.run with a step being one force evaluation (launch): up to max_evaluations of every molecule that has not
+        converged, then the result at the centres reached; check_every and record_every count evaluations.  The check-only launch
+        measures fmax and the energy of every molecule whose probe is its centre, sets no flag and moves nothing."""
+        return self._run(*check_run_arguments(max_evaluations, check_every, record_every))
 
-    def _frame(self, k):
-        return (self.step_count + k, self._pos[self._cur].clone(), self._force.clone(), self._energy.reshape(-1).clone(),
-                self.positions, self.mode, self._int('phase'), self.curvature)
+    def _frame(self):
+        return (self._pos[self._cur].clone(), self._force.clone(), self._energy.reshape(-1).clone(), self.positions, self.mode,
+                self._int('phase'), self.curvature)
+
+    def _result(self):
+        return SaddleResult(self.positions, self.mode, self._e_center.clone(), self._fmax.clone(), self.curvature,
+                            self._active != 0, self.n_steps, self.n_evaluations, self.n_rotations)

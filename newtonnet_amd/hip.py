@@ -793,6 +793,22 @@ def _wg_min_atoms(wg_min_atoms):
     return int(wg_min_atoms)
 
 
+def _n_rows3(pos_out) -> int:
+    """N of the pos_out [N,3] of an optimiser step, refused when it is not of that form"""
+    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
+        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
+    return pos_out.shape[0]
+
+
+def _free_mask(free, N: int, dev):
+    """the `free` argument of an optimiser step as the kernel reads it: None, or N contiguous bytes on dev"""
+    if free is None:
+        return None
+    if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
+        raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
+    return free.contiguous()
+
+
 def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.Tensor], mol_ptr: torch.Tensor, memory: int,
                tol2: float, alpha: float, maxstep: float, flags: int, converged: torch.Tensor, n_steps: torch.Tensor,
                n_pairs: torch.Tensor, head: torch.Tensor, S: torch.Tensor, Y: torch.Tensor, rho: torch.Tensor,
@@ -808,16 +824,11 @@ def lbfgs_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.T
     if wg_min_atoms is not None:
         wg_min_atoms = _wg_min_atoms(wg_min_atoms)
     B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
-    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
-        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
-    N, rows = pos_out.shape[0], max(m, 0)
+    N, rows = _n_rows3(pos_out), max(m, 0)
     _written(dev, optional=('work',), converged=(converged, B, i32), n_steps=(n_steps, B, i32), n_pairs=(n_pairs, B, i32),
              head=(head, B, i32), S=(S, rows * N * 3), Y=(Y, rows * N * 3), rho=(rho, B * rows), f_prev=(f_prev, 3 * N),
              work=(work, 3 * N), pos_out=(pos_out, 3 * N), fmax_out=(fmax_out, B))
-    if free is not None:
-        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
-            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
-        free = free.contiguous()
+    free = _free_mask(free, N, dev)
     pos_in, force = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N))
     L = lib()
     head_args = (_ptr(pos_in), _ptr(force), _ptr(free), _ptr(mol_ptr), B, N, m, float(tol2), float(alpha), float(maxstep))
@@ -855,18 +866,13 @@ def cell_lbfgs_step(x_in: torch.Tensor, pos_in: torch.Tensor, force: torch.Tenso
     if wg_min_atoms is not None:
         wg_min_atoms = _wg_min_atoms(wg_min_atoms)
     B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
-    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
-        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
-    N, slots = pos_out.shape[0], max(m, 0)
+    N, slots = _n_rows3(pos_out), max(m, 0)
     R = N + 3 * B
     _written(dev, optional=('work',), converged=(converged, B, i32), n_steps=(n_steps, B, i32), n_pairs=(n_pairs, B, i32),
              head=(head, B, i32), S=(S, slots * R * 3), Y=(Y, slots * R * 3), rho=(rho, B * slots), g_prev=(g_prev, 3 * R),
              work=(work, 3 * R), G=(G, 3 * R), x_out=(x_out, 3 * R), pos_out=(pos_out, 3 * N), cell_out=(cell_out, 9 * B),
              fmax_out=(fmax_out, B))
-    if free is not None:
-        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
-            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
-        free = free.contiguous()
+    free = _free_mask(free, N, dev)
     x_in, pos_in, force, virial, cell_in, h0, pressure, cell_factor = _read(
         dev, x_in=(x_in, 3 * R), pos_in=(pos_in, 3 * N), force=(force, 3 * N), virial=(virial, 9 * B), cell_in=(cell_in, 9 * B),
         h0=(h0, 9 * B), pressure=(pressure, B), cell_factor=(cell_factor, B))
@@ -901,16 +907,11 @@ def neb_step(pos_in: torch.Tensor, force: torch.Tensor, energy: torch.Tensor, fr
     pos_out may not overlap pos_in."""
     B, dev, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, torch.int32
     K = _offsets('band_ptr', band_ptr, dev, band_ptr_host)
-    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
-        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
-    N = pos_out.shape[0]
+    N = _n_rows3(pos_out)
     _written(dev, converged=(converged, K, i32), climbing=(climbing, K, i32), n_steps=(n_steps, K, i32), n_pos=(n_pos, K, i32),
              dt=(dt, K), a=(a, K), vel=(vel, 3 * N), pos_out=(pos_out, 3 * N), neb_force_out=(neb_force_out, 3 * N),
              tangent_out=(tangent_out, 3 * N), fmax_out=(fmax_out, K), saddle_out=(saddle_out, K, i32))
-    if free is not None:
-        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
-            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
-        free = free.contiguous()
+    free = _free_mask(free, N, dev)
     pos_in, force, energy = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), energy=(energy, B))
     dt0, dt_max, n_min, f_inc, f_dec, a_start, f_a, maxstep = fire
     _check(lib().nnhip_neb_step(_ptr(pos_in), _ptr(force), _ptr(energy), _ptr(free), _ptr(mol_ptr), _ptr(band_ptr),
@@ -936,16 +937,11 @@ def irc_step(pos_in: torch.Tensor, force: torch.Tensor, free: Optional[torch.Ten
     v_prev, a_prev fp32 [N,3]) is updated in place, pos_out [N,3] and fmax_out [B] are written: all of these must be contiguous
     tensors of exactly that type (a copy would take the result away).  pos_out may not overlap pos_in."""
     B, dev, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, torch.int32
-    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
-        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
-    N = pos_out.shape[0]
+    N = _n_rows3(pos_out)
     _written(dev, status=(status, B, i32), armed=(armed, B, i32), n_steps=(n_steps, B, i32), dt=(dt, B), dt_prev=(dt_prev, B),
              arc=(arc, B), vel=(vel, 3 * N), x_prev=(x_prev, 3 * N), v_prev=(v_prev, 3 * N), a_prev=(a_prev, 3 * N),
              pos_out=(pos_out, 3 * N), fmax_out=(fmax_out, B))
-    if free is not None:
-        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
-            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
-        free = free.contiguous()
+    free = _free_mask(free, N, dev)
     pos_in, force, masses = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), masses=(masses, N))
     _check(lib().nnhip_irc_step(_ptr(pos_in), _ptr(force), _ptr(free), _ptr(masses), _ptr(mol_ptr), B, N, float(v0), float(delta0),
                                 float(dt_min), float(dt_max), float(tol2), int(flags), _ptr(status), _ptr(armed), _ptr(n_steps),
@@ -974,16 +970,11 @@ def dimer_step(pos_in: torch.Tensor, force: torch.Tensor, energy: Optional[torch
     exactly that type (a copy would take the result away).  work: fp32 [N,3] scratch, needed when N > 64.  pos_out may not overlap
     pos_in."""
     B, dev, m, i32 = _offsets('mol_ptr', mol_ptr), mol_ptr.device, int(memory), torch.int32
-    if pos_out.dim() != 2 or pos_out.shape[1] != 3:
-        raise ValueError(f'pos_out: [N,3] expected (got {tuple(pos_out.shape)})')
-    N, rows = pos_out.shape[0], max(m, 0)
+    N, rows = _n_rows3(pos_out), max(m, 0)
     _written(dev, optional=('work', 'energy_out'), istate=(istate, DIMER_N_INT * B, i32), fstate=(fstate, DIMER_N_FLOAT * B),
              vstate=(vstate, DIMER_N_VEC * N * 3), S=(S, rows * N * 3), Y=(Y, rows * N * 3), rho=(rho, B * rows), work=(work, 3 * N),
              pos_out=(pos_out, 3 * N), fmax_out=(fmax_out, B), energy_out=(energy_out, B))
-    if free is not None:
-        if free.dtype not in (torch.bool, torch.uint8) or free.numel() != N or free.device != dev:
-            raise ValueError(f'free: a bool or uint8 tensor of {N} values on {dev} expected')
-        free = free.contiguous()
+    free = _free_mask(free, N, dev)
     pos_in, force, energy = _read(dev, pos_in=(pos_in, 3 * N), force=(force, 3 * N), energy=(energy, B))
     _check(lib().nnhip_dimer_step(_ptr(pos_in), _ptr(force), _ptr(energy), _ptr(free), _ptr(mol_ptr), B, N, m, float(delta),
                                   float(rot_tol), int(max_rotations), float(tol2), float(alpha), float(maxstep), int(flags),

@@ -19,8 +19,9 @@ import torch
 
 from newtonnet_amd import hip
 from newtonnet_amd.dynamics import _mol_ptr, _molecule_sums
-from newtonnet_amd.relax import check_run_arguments
-from newtonnet_amd.vibrations import table_masses
+from newtonnet_amd.relax import check_inputs
+from newtonnet_amd.stepper import Stepper, check_run_arguments
+from newtonnet_amd.vibrations import lowest_mode_direction, table_masses
 
 RUNNING, MINIMUM, TURNED = 0, 1, 2
 
@@ -92,7 +93,7 @@ def check_arguments(speed, error_target, timestep, timestep_min, timestep_max, i
     return tuple(vals)
 
 
-class ReactionPath:
+class ReactionPath(Stepper):
     """The IRC paths from the saddles of B molecules, followed together on the device.
 
     model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads.  z, pos, cell, batch: as for model(...), on the
@@ -108,30 +109,15 @@ class ReactionPath:
     never move.  masses: fp32 [N] amu (None: standard atomic weights of z).
 
     Periodic molecules: the cell is fixed and positions stay unwrapped; the model's neighbor list takes the minimum image itself."""
+    NOUN, CHECK_ONLY = 'reaction paths', hip.IRC_CHECK_ONLY
+    TRAJ = (('pos', ('n_atoms', 3), torch.float32), ('force', ('n_atoms', 3), torch.float32), ('vel', ('n_atoms', 3), torch.float32),
+            ('energy', ('n_mol',), torch.float32), ('arc', ('n_mol',), torch.float32), ('dt', ('n_mol',), torch.float32),
+            ('status', ('n_mol',), torch.int64))
 
     def __init__(self, model, z, pos, cell, batch, direction=None, masses=None, both=True, speed=0.02, error_target=1.5e-3,
                  timestep=0.25, timestep_min=0.01, timestep_max=2.0, initial_displacement=0.1, fmax=0.01, fixed=None):
         # ---- everything that can be refused without touching the device
-        if getattr(model, 'training', False):
-            raise ValueError('ReactionPath needs the model in eval mode: call model.eval()')
-        props = list(getattr(model, 'output_properties', []))
-        if 'energy' not in props or 'gradient_force' not in props:
-            raise ValueError(f"ReactionPath needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
-        for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
-        if pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
-        N = pos.shape[0]
-        if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
-            raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
-        B = cell.shape[0]
-        if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
-            raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
-        if pos.dtype != torch.float32 or cell.dtype != torch.float32:
-            raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
-        if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
-            raise ValueError(f'fixed: a bool tensor [{N}] expected')
+        N, B = check_inputs(model, 'ReactionPath', z, pos, cell, batch, fixed)
         if direction is not None and (not isinstance(direction, torch.Tensor) or direction.dtype != torch.float32
                                       or tuple(direction.shape) != (N, 3)):
             raise ValueError(f'direction: a float32 tensor [{N},3] expected')
@@ -139,13 +125,7 @@ class ReactionPath:
             raise ValueError(f'masses: a tensor of {N} values expected')
         speed, error_target, timestep, timestep_min, timestep_max, initial_displacement, fmax = check_arguments(
             speed, error_target, timestep, timestep_min, timestep_max, initial_displacement, fmax)
-        if not pos.is_cuda:
-            raise RuntimeError('newtonnet_amd reaction paths run on an MI355X (ROCm) device only: move the model and the inputs to '
-                               '"cuda"')
-        dev = pos.device
-        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('fixed', fixed), ('direction', direction), ('masses', masses)):
-            if t is not None and t.device != dev:
-                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        dev = self._check_device(pos, z=z, cell=cell, batch=batch, fixed=fixed, direction=direction, masses=masses)
         # ---- state
         f32 = np.float32
         self.model, self.both, self.fmax = model, bool(both), fmax
@@ -154,18 +134,13 @@ class ReactionPath:
         self._v0, self._delta0 = float(f32(speed)), float(f32(error_target))
         self._dt_min, self._dt_max = float(f32(timestep_min)), float(f32(timestep_max))
         self._tol2 = float(f32(fmax * fmax))
-        self.step_count = 0
         with torch.no_grad():
             m = table_masses(z) if masses is None else masses.detach().float().reshape(-1).clone()
             free = torch.ones(N, dtype=torch.bool, device=dev) if fixed is None else ~fixed
             imaginary = torch.ones(B, dtype=torch.bool, device=dev)
             if direction is None:
-                nm = model.normal_modes(z, pos.detach(), cell, batch, masses=m, solver='auto')
-                ptr = _mol_ptr(batch, B).long()
-                local = torch.arange(N, device=dev) - ptr[batch.long()]
-                q = nm.modes[(nm.blk_ptr[batch.long()] + 3 * local)[:, None] + torch.arange(3, device=dev)]
-                u = q.double() / m.double().sqrt()[:, None]
-                imaginary = nm.n_imaginary > 0
+                u, n_imaginary = lowest_mode_direction(model, z, pos, cell, batch, m, 'auto')
+                imaginary = n_imaginary > 0
             else:
                 u = direction.detach().double()
             u = u * free[:, None]
@@ -216,32 +191,22 @@ class ReactionPath:
             self.n_atoms, self.n_mol = Np, P
             self.masses = m.contiguous()
             self._free = None if fixed is None else free.contiguous()
-            # two position buffers: a step reads one and writes the other, so the forward call queued on the one it read can still
-            # be repeated from it (NewtonNet._forward_deferred)
-            self._pos = [start.float().contiguous(), torch.empty(Np, 3, dtype=torch.float32, device=dev)]
-            self._cur = 0
+            self._init_buffers(start.float().contiguous())
             self._mol_ptr = _mol_ptr(self.batch, P)
             self._mol_ptr_host = None
 
             def ints():
                 return torch.zeros(P, dtype=torch.int32, device=dev)
             self._status, self._armed, self._n_steps = ints(), ints(), ints()
+            self._active = self._status
             self._dt = torch.full((P,), float(f32(timestep)), dtype=torch.float32, device=dev)
             self._dt_prev = torch.zeros(P, dtype=torch.float32, device=dev)
             self._arc = torch.full((P,), float(f32(initial_displacement)), dtype=torch.float32, device=dev)
             self._vel = vel.float().contiguous()
             self._x_prev, self._v_prev, self._a_prev = (torch.zeros(Np, 3, dtype=torch.float32, device=dev) for _ in range(3))
             self._fmax = torch.zeros(P, dtype=torch.float32, device=dev)
-            self._force = self._energy = None
 
     # ------------------------------------------------------------------------------------------
-    def _evaluate(self):
-        """forces and energies at the current positions.  Touching gradient_force settles the deferred record of the call -- a
-        repeat, if one is needed, happens HERE, from the buffer the call was queued with and before any kernel writes a buffer"""
-        out = self.model(self.z, self._pos[self._cur], self.cell, self.batch)
-        self._force = out.gradient_force
-        self._energy = out.energy
-
     def _launch(self, flags=0):
         """one launch: reads the current buffer and the current forces, writes the other buffer, and the buffers swap"""
         other = 1 - self._cur
@@ -257,31 +222,11 @@ class ReactionPath:
                 out = self.model(z, pos, cell, batch)
                 out.gradient_force                        # (settles the deferred record of the call, as _evaluate says)
                 self._saddle_energy = out.energy.clone()
-        if self._force is None:
-            with torch.no_grad():
-                self._evaluate()
-
-    @property
-    def positions(self):
-        return self._pos[self._cur].detach().clone()
+        super()._ensure_state()
 
     @property
     def velocities(self):
         return self._vel.clone()
-
-    @property
-    def forces(self):
-        self._ensure_state()
-        return self._force
-
-    @property
-    def potential_energy(self):
-        self._ensure_state()
-        return self._energy
-
-    @property
-    def n_steps(self):
-        return self._n_steps.long()
 
     @property
     def status(self):
@@ -297,53 +242,22 @@ class ReactionPath:
 
     # ------------------------------------------------------------------------------------------
     def run(self, max_steps: int, check_every: int = 10, record_every: int = 1) -> PathResult:
-        """Up to max_steps steps of every path that has not stopped, then the result at the positions reached.  Every check_every
-        steps the host reads ONE number, the count of paths still running, and stops when it is 0 (check_every = 0: never reads,
-        always max_steps launches).  A stopped path is frozen bit for bit, so check_every changes no bit of any result.
-        record_every > 0 records the steps record_every, 2 record_every, ... of this call that were taken, and the last one;
-        recording changes no bit either.  May be called again to continue: run(a); run(b) leaves the bits of run(a + b)."""
-        max_steps, check_every, every = check_run_arguments(max_steps, check_every, record_every)
-        P, Np, dev = self.n_mol, self.n_atoms, self._fmax.device
-        frames = []
-        with torch.no_grad():
-            self._ensure_state()
-            first = None
-            if self.step_count == 0:
-                first = (self._pos[self._cur].clone(), self._energy.clone(), self._arc.clone())
-            taken = 0
-            for k in range(1, max_steps + 1):
-                self._launch()
-                self._evaluate()
-                taken = k
-                if every and k % every == 0:
-                    frames.append(self._frame(k))
-                if check_every and k % check_every == 0 and int((self._status == 0).sum()) == 0:
-                    break
-            if every and taken and (not frames or frames[-1][0] != self.step_count + taken):
-                frames.append(self._frame(taken))
-            self.step_count += taken
-            # the state at the positions reached: their forces are evaluated already; a check-only launch measures fmax there and
-            # moves nothing (it copies the positions into the other buffer)
-            self._launch(hip.IRC_CHECK_ONLY)
-            if self._mol_ptr_host is None:
-                self._mol_ptr_host = self._mol_ptr.tolist()
-            result = PathResult(self._pos[self._cur].clone(), self._energy.clone(), self._fmax.clone(), self._status.long(),
-                                self._n_steps.long(), self._arc.clone(), self.both, self._mol_ptr_host,
-                                (self._saddle_inputs[1].detach(), self._saddle_energy), first)
-            if every:
-                if frames:
-                    result.traj_step = torch.tensor([f[0] for f in frames], dtype=torch.int64, device=dev)
-                    (result.traj_pos, result.traj_force, result.traj_vel, result.traj_energy, result.traj_arc, result.traj_dt,
-                     result.traj_status) = (torch.stack([f[j] for f in frames]) for j in range(1, 8))
-                else:
-                    result.traj_step = torch.zeros(0, dtype=torch.int64, device=dev)
-                    result.traj_pos, result.traj_force, result.traj_vel = (
-                        torch.zeros(0, Np, 3, dtype=torch.float32, device=dev) for _ in range(3))
-                    result.traj_energy, result.traj_arc, result.traj_dt = (
-                        torch.zeros(0, P, dtype=torch.float32, device=dev) for _ in range(3))
-                    result.traj_status = torch.zeros(0, P, dtype=torch.int64, device=dev)
-        return result
+        """Stepper.run, recording every step unless told otherwise: steps of every path that has not stopped, then the result at
+        the positions reached.  The check-only launch measures fmax there and moves nothing."""
+        return self._run(*check_run_arguments(max_steps, check_every, record_every))
 
-    def _frame(self, k):
-        return (self.step_count + k, self._pos[self._cur].clone(), self._force.clone(), self._vel.clone(), self._energy.clone(),
-                self._arc.clone(), self._dt.clone(), self._status.long())
+    def _begin(self):
+        self._first = None
+        if self.step_count == 0:
+            self._first = (self._pos[self._cur].clone(), self._energy.clone(), self._arc.clone())
+
+    def _frame(self):
+        return (self._pos[self._cur].clone(), self._force.clone(), self._vel.clone(), self._energy.clone(), self._arc.clone(),
+                self._dt.clone(), self._status.long())
+
+    def _result(self):
+        if self._mol_ptr_host is None:
+            self._mol_ptr_host = self._mol_ptr.tolist()
+        return PathResult(self._pos[self._cur].clone(), self._energy.clone(), self._fmax.clone(), self._status.long(),
+                          self._n_steps.long(), self._arc.clone(), self.both, self._mol_ptr_host,
+                          (self._saddle_inputs[1].detach(), self._saddle_energy), self._first)

@@ -27,7 +27,8 @@ import torch
 
 from newtonnet_amd import hip
 from newtonnet_amd.dynamics import _mol_ptr
-from newtonnet_amd.relax import check_run_arguments
+from newtonnet_amd.relax import check_inputs
+from newtonnet_amd.stepper import Stepper
 
 FIRE_N_MIN, FIRE_F_INC, FIRE_F_DEC, FIRE_A_START, FIRE_F_A = hip.NEB_FIRE_DEFAULTS[2:7]
 
@@ -105,7 +106,7 @@ def interpolate(pos_a: torch.Tensor, pos_b: torch.Tensor, n_images: int) -> torc
     return out
 
 
-class Band:
+class Band(Stepper):
     """K bands optimised together on the device.
 
     model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads.  z, pos, cell, batch: as for model(...), on the
@@ -115,39 +116,17 @@ class Band:
     it (compared as squares in fp32).  climb: use a climbing image, switched on below climb_below (None: 5 fmax).  fixed: bool
     [N], atoms that never move.  dt, dt_max, maxstep: FIRE's first and largest step length and the cap on the length of a band's
     step; its other constants are ASE's."""
+    NOUN, CHECK_ONLY = 'band searches', hip.NEB_CHECK_ONLY
+    TRAJ = (('pos', ('n_atoms', 3), torch.float32), ('force', ('n_atoms', 3), torch.float32), ('energy', ('n_mol',), torch.float32),
+            ('dt', ('n_bands',), torch.float32))
 
     def __init__(self, model, z, pos, cell, batch, n_images, spring=0.1, fmax=0.05, climb=True, climb_below=None, fixed=None,
                  dt=0.1, dt_max=1.0, maxstep=0.2):
         # ---- everything that can be refused without touching the device
-        if getattr(model, 'training', False):
-            raise ValueError('Band needs the model in eval mode: call model.eval()')
-        props = list(getattr(model, 'output_properties', []))
-        if 'energy' not in props or 'gradient_force' not in props:
-            raise ValueError(f"Band needs a model with the 'energy' and 'gradient_force' heads (it has {props})")
-        for name, t in (('z', z), ('pos', pos), ('cell', cell), ('batch', batch)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f'{name}: a tensor expected (got {type(t).__name__})')
-        if pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError(f'pos: [N,3] expected (got {tuple(pos.shape)})')
-        N = pos.shape[0]
-        if cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
-            raise ValueError(f'cell: [B,3,3] expected (got {tuple(cell.shape)})')
-        B = cell.shape[0]
-        if tuple(z.shape) != (N,) or tuple(batch.shape) != (N,):
-            raise ValueError(f'z and batch: [{N}] expected (got {tuple(z.shape)}, {tuple(batch.shape)})')
-        if pos.dtype != torch.float32 or cell.dtype != torch.float32:
-            raise ValueError(f'pos and cell: float32 expected (got {pos.dtype}, {cell.dtype})')
-        if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (N,)):
-            raise ValueError(f'fixed: a bool tensor [{N}] expected')
+        N, B = check_inputs(model, 'Band', z, pos, cell, batch, fixed)
         counts = band_counts(n_images, B)
         spring, fmax, climb_below, dt, dt_max, maxstep = check_arguments(spring, fmax, climb_below, dt, dt_max, maxstep)
-        if not pos.is_cuda:
-            raise RuntimeError('newtonnet_amd band searches run on an MI355X (ROCm) device only: move the model and the inputs to '
-                               '"cuda"')
-        dev = pos.device
-        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('fixed', fixed)):
-            if t is not None and t.device != dev:
-                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        dev = self._check_device(pos, z=z, cell=cell, batch=batch, fixed=fixed)
         # ---- state
         self.model, self.z, self.cell, self.batch = model, z, cell, batch
         self.n_atoms, self.n_mol, self.n_bands = N, B, len(counts)
@@ -158,7 +137,6 @@ class Band:
         self._fire = (float(f32(dt)), float(f32(dt_max)), int(FIRE_N_MIN), float(f32(FIRE_F_INC)), float(f32(FIRE_F_DEC)),
                       float(f32(FIRE_A_START)), float(f32(FIRE_F_A)), float(f32(maxstep)))
         self._flags = hip.NEB_CLIMB if climb else 0
-        self.step_count = 0
         K = self.n_bands
         with torch.no_grad():
             self._band_ptr_host = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32)
@@ -170,31 +148,20 @@ class Band:
                 if (s != s[0]).any():
                     raise ValueError(f'band {k}: its images have different atom counts ({s.tolist()})')
             self._free = None if fixed is None else (~fixed).contiguous()
-            # two position buffers: a step reads one and writes the other, so the forward call queued on the one it read can still
-            # be repeated from it (NewtonNet._forward_deferred)
-            self._pos = [pos.detach().clone().contiguous(), torch.empty(N, 3, dtype=torch.float32, device=dev)]
-            self._cur = 0
+            self._init_buffers(pos.detach().clone().contiguous())
 
             def ints():
                 return torch.zeros(K, dtype=torch.int32, device=dev)
             self._converged, self._climbing, self._n_steps, self._n_pos, self._saddle = ints(), ints(), ints(), ints(), ints()
+            self._active = self._converged
             self._dt = torch.zeros(K, dtype=torch.float32, device=dev)
             self._a = torch.zeros(K, dtype=torch.float32, device=dev)
             self._vel = torch.zeros(N, 3, dtype=torch.float32, device=dev)
             self._neb_force = torch.zeros(N, 3, dtype=torch.float32, device=dev)
             self._tangent = torch.zeros(N, 3, dtype=torch.float32, device=dev)
             self._fmax = torch.zeros(K, dtype=torch.float32, device=dev)
-            self._force = self._energy = None
 
     # ------------------------------------------------------------------------------------------
-    def _evaluate(self):
-        """forces and energies at the current positions.  Touching gradient_force and energy settles the deferred record of the
-        call -- a repeat, if one is needed, happens HERE, from the buffer the call was queued with and before any kernel writes a
-        buffer"""
-        out = self.model(self.z, self._pos[self._cur], self.cell, self.batch)
-        self._force = out.gradient_force
-        self._energy = out.energy
-
     def _launch(self, flags=0):
         """one launch: reads the current buffer, forces and energies, writes the other buffer, and the buffers swap"""
         other = 1 - self._cur
@@ -204,75 +171,17 @@ class Band:
                      self._fmax, self._saddle)
         self._cur = other
 
-    def _ensure_state(self):
-        if self._force is None:
-            with torch.no_grad():
-                self._evaluate()
-
-    @property
-    def positions(self):
-        return self._pos[self._cur].detach().clone()
-
-    @property
-    def forces(self):
-        self._ensure_state()
-        return self._force
-
-    @property
-    def potential_energy(self):
-        self._ensure_state()
-        return self._energy
-
-    @property
-    def n_steps(self):
-        return self._n_steps.long()
-
     # ------------------------------------------------------------------------------------------
-    def run(self, max_steps: int, check_every: int = 10, record_every: int = 0) -> BandResult:
-        """Up to max_steps steps of every band that has not converged, then the result at the positions reached.  Every
-        check_every steps the host reads ONE number, the count of bands that have not converged, and stops when it is 0
-        (check_every = 0: never reads, always max_steps launches).  A converged band is frozen bit for bit, so check_every changes
-        no bit of any result.  record_every > 0 records the steps record_every, 2 record_every, ... of this call that were taken,
-        and the last one.  May be called again to continue: run(a); run(b) leaves the bits of run(a + b)."""
-        max_steps, check_every, every = check_run_arguments(max_steps, check_every, record_every)
-        B, K, N, dev = self.n_mol, self.n_bands, self.n_atoms, self._fmax.device
-        frames = []
-        with torch.no_grad():
-            self._ensure_state()
-            taken = 0
-            for k in range(1, max_steps + 1):
-                self._launch()
-                self._evaluate()
-                taken = k
-                if every and k % every == 0:
-                    frames.append(self._frame(k))
-                if check_every and k % check_every == 0 and int((self._converged == 0).sum()) == 0:
-                    break
-            if every and taken and (not frames or frames[-1][0] != self.step_count + taken):
-                frames.append(self._frame(taken))
-            self.step_count += taken
-            # the state at the positions reached: their forces are evaluated already; a check-only launch forms the NEB forces,
-            # the tangents and fmax there, moves nothing and sets no flag
-            self._launch(hip.NEB_CHECK_ONLY)
-            saddle = self._saddle.long()
-            first, last = self._band_ptr[:-1].long(), self._band_ptr[1:].long() - 1
-            e = self._energy
-            result = BandResult(pos=self._pos[self._cur].clone(), energy=e.clone(), neb_force=self._neb_force.clone(),
-                                tangent=self._tangent.clone(), fmax=self._fmax.clone(), converged=self._converged != 0,
-                                climbing=self._climbing != 0, n_steps=self._n_steps.long(), saddle_image=saddle,
-                                barrier_forward=e[saddle] - e[first], barrier_reverse=e[saddle] - e[last])
-            if every:
-                if frames:
-                    result.traj_step = torch.tensor([f[0] for f in frames], dtype=torch.int64, device=dev)
-                    result.traj_pos, result.traj_force, result.traj_energy, result.traj_dt = (
-                        torch.stack([f[j] for f in frames]) for j in (1, 2, 3, 4))
-                else:
-                    result.traj_step = torch.zeros(0, dtype=torch.int64, device=dev)
-                    result.traj_pos = torch.zeros(0, N, 3, dtype=torch.float32, device=dev)
-                    result.traj_force = torch.zeros(0, N, 3, dtype=torch.float32, device=dev)
-                    result.traj_energy = torch.zeros(0, B, dtype=torch.float32, device=dev)
-                    result.traj_dt = torch.zeros(0, K, dtype=torch.float32, device=dev)
-        return result
+    # run (Stepper.run): FIRE steps of every band that has not converged; the check-only launch forms the NEB forces, the tangents
+    # and fmax at the positions reached, moves nothing and sets no flag
+    def _frame(self):
+        return self._pos[self._cur].clone(), self._force.clone(), self._energy.clone(), self._dt.clone()
 
-    def _frame(self, k):
-        return (self.step_count + k, self._pos[self._cur].clone(), self._force.clone(), self._energy.clone(), self._dt.clone())
+    def _result(self):
+        saddle = self._saddle.long()
+        first, last = self._band_ptr[:-1].long(), self._band_ptr[1:].long() - 1
+        e = self._energy
+        return BandResult(pos=self._pos[self._cur].clone(), energy=e.clone(), neb_force=self._neb_force.clone(),
+                          tangent=self._tangent.clone(), fmax=self._fmax.clone(), converged=self._converged != 0,
+                          climbing=self._climbing != 0, n_steps=self._n_steps.long(), saddle_image=saddle,
+                          barrier_forward=e[saddle] - e[first], barrier_reverse=e[saddle] - e[last])

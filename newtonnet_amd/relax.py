@@ -31,6 +31,7 @@ import torch
 
 from newtonnet_amd import hip
 from newtonnet_amd.dynamics import _mol_ptr
+from newtonnet_amd.stepper import Stepper, check_run_arguments          # noqa: F401 (check_run_arguments: callers import it from here)
 
 
 FORMS = ('wave', 'workgroup', 'auto')
@@ -109,14 +110,7 @@ def check_inputs(model, who, z, pos, cell, batch, fixed):
     return N, B
 
 
-def check_run_arguments(max_steps, check_every, record_every):
-    for name, v in (('max_steps', max_steps), ('check_every', check_every), ('record_every', record_every)):
-        if int(v) != v or v < 0:
-            raise ValueError(f'{name}: an integer >= 0 expected (got {v!r})')
-    return int(max_steps), int(check_every), int(record_every)
-
-
-class Relaxation:
+class Relaxation(Stepper):
     """B molecules relaxed together on the device.
 
     model: a NewtonNet in eval mode with the 'energy' and 'gradient_force' heads.  z, pos, cell, batch: as for model(...), on the
@@ -128,6 +122,9 @@ class Relaxation:
     wg_min_atoms means something with 'auto' only.
 
     Periodic molecules: the cell is fixed and positions stay unwrapped; the model's neighbor list takes the minimum image itself."""
+    NOUN, CHECK_ONLY = 'relaxations', hip.LBFGS_CHECK_ONLY
+    TRAJ = (('pos', ('n_atoms', 3), torch.float32), ('force', ('n_atoms', 3), torch.float32), ('energy', ('n_mol',), torch.float32),
+            ('n_pairs', ('n_mol',), torch.int64))
 
     def __init__(self, model, z, pos, cell, batch, fmax=0.01, memory=16, maxstep=0.2, alpha=70.0, fixed=None, form='wave',
                  wg_min_atoms=None):
@@ -135,13 +132,7 @@ class Relaxation:
         N, B = check_inputs(model, 'Relaxation', z, pos, cell, batch, fixed)
         fmax, memory, maxstep, alpha = check_arguments(fmax, memory, maxstep, alpha)
         self.form, self._wg_min_atoms = form, check_form(form, wg_min_atoms)
-        if not pos.is_cuda:
-            raise RuntimeError('newtonnet_amd relaxations run on an MI355X (ROCm) device only: move the model and the inputs to '
-                               '"cuda"')
-        dev = pos.device
-        for name, t in (('z', z), ('cell', cell), ('batch', batch), ('fixed', fixed)):
-            if t is not None and t.device != dev:
-                raise ValueError(f'{name} is on {t.device}, pos on {dev}')
+        dev = self._check_device(pos, z=z, cell=cell, batch=batch, fixed=fixed)
         # ---- state
         self.model, self.z, self.cell, self.batch = model, z, cell, batch
         self.n_atoms, self.n_mol = N, B
@@ -149,34 +140,23 @@ class Relaxation:
         # the numbers the kernel gets, as the Python floats of their fp32 values
         self._tol2 = float(np.float32(fmax * fmax))
         self._maxstep, self._alpha = float(np.float32(maxstep)), float(np.float32(alpha))
-        self.step_count = 0
         with torch.no_grad():
             self._free = None if fixed is None else (~fixed).contiguous()
-            # two position buffers: a step reads one and writes the other, so the forward call queued on the one it read can still
-            # be repeated from it (NewtonNet._forward_deferred)
-            self._pos = [pos.detach().clone().contiguous(), torch.empty(N, 3, dtype=torch.float32, device=dev)]
-            self._cur = 0
+            self._init_buffers(pos.detach().clone().contiguous())
             self._mol_ptr = _mol_ptr(batch, B)
 
             def ints():
                 return torch.zeros(B, dtype=torch.int32, device=dev)
             self._converged, self._n_steps, self._n_pairs, self._head = ints(), ints(), ints(), ints()
+            self._active = self._converged
             self._S = torch.zeros(memory, N, 3, dtype=torch.float32, device=dev)
             self._Y = torch.zeros(memory, N, 3, dtype=torch.float32, device=dev)
             self._rho = torch.zeros(B, memory, dtype=torch.float32, device=dev)
             self._f_prev = torch.zeros(N, 3, dtype=torch.float32, device=dev)
             self._work = torch.empty(N, 3, dtype=torch.float32, device=dev) if N > 64 else None
             self._fmax = torch.zeros(B, dtype=torch.float32, device=dev)
-            self._force = self._energy = None
 
     # ------------------------------------------------------------------------------------------
-    def _evaluate(self):
-        """forces and energies at the current positions.  Touching gradient_force settles the deferred record of the call -- a
-        repeat, if one is needed, happens HERE, from the buffer the call was queued with and before any kernel writes a buffer"""
-        out = self.model(self.z, self._pos[self._cur], self.cell, self.batch)
-        self._force = out.gradient_force
-        self._energy = out.energy
-
     def _launch(self, flags=0):
         """one launch: reads the current buffer and the current forces, writes the other buffer, and the buffers swap"""
         other = 1 - self._cur
@@ -185,75 +165,16 @@ class Relaxation:
                        self._f_prev, self._work, self._pos[other], self._fmax, wg_min_atoms=self._wg_min_atoms)
         self._cur = other
 
-    def _ensure_state(self):
-        if self._force is None:
-            with torch.no_grad():
-                self._evaluate()
-
-    @property
-    def positions(self):
-        return self._pos[self._cur].detach().clone()
-
-    @property
-    def forces(self):
-        self._ensure_state()
-        return self._force
-
-    @property
-    def potential_energy(self):
-        self._ensure_state()
-        return self._energy
-
-    @property
-    def n_steps(self):
-        return self._n_steps.long()
-
     @property
     def n_pairs(self):
         return self._n_pairs.long()
 
     # ------------------------------------------------------------------------------------------
-    def run(self, max_steps: int, check_every: int = 10, record_every: int = 0) -> RelaxResult:
-        """Up to max_steps L-BFGS steps of every molecule that has not converged, then the result at the positions reached.
-        Every check_every steps the host reads ONE number, the count of molecules that have not converged, and stops when it is 0
-        (check_every = 0: never reads, always max_steps launches).  A converged molecule is frozen bit for bit, so check_every
-        changes no bit of any result.  record_every > 0 records the steps record_every, 2 record_every, ... of this call that were
-        taken, and the last one.  May be called again to continue: run(a); run(b) leaves the bits of run(a + b)."""
-        max_steps, check_every, every = check_run_arguments(max_steps, check_every, record_every)
-        B, dev = self.n_mol, self._fmax.device
-        frames = []
-        with torch.no_grad():
-            self._ensure_state()
-            taken = 0
-            for k in range(1, max_steps + 1):
-                self._launch()
-                self._evaluate()
-                taken = k
-                if every and k % every == 0:
-                    frames.append(self._frame(k))
-                if check_every and k % check_every == 0 and int((self._converged == 0).sum()) == 0:
-                    break
-            if every and taken and (not frames or frames[-1][0] != self.step_count + taken):
-                frames.append(self._frame(taken))
-            self.step_count += taken
-            # the state at the positions reached: their forces are evaluated already; a check-only launch measures fmax and
-            # marks what has converged there, and moves nothing (it copies the positions into the other buffer)
-            self._launch(hip.LBFGS_CHECK_ONLY)
-            result = RelaxResult(self._pos[self._cur].clone(), self._energy.clone(), self._fmax.clone(), self._converged != 0,
-                                 self._n_steps.long())
-            if every:
-                if frames:
-                    result.traj_step = torch.tensor([f[0] for f in frames], dtype=torch.int64, device=dev)
-                    result.traj_pos, result.traj_force, result.traj_energy, result.traj_n_pairs = (
-                        torch.stack([f[j] for f in frames]) for j in (1, 2, 3, 4))
-                else:
-                    N = self.n_atoms
-                    result.traj_step = torch.zeros(0, dtype=torch.int64, device=dev)
-                    result.traj_pos = torch.zeros(0, N, 3, dtype=torch.float32, device=dev)
-                    result.traj_force = torch.zeros(0, N, 3, dtype=torch.float32, device=dev)
-                    result.traj_energy = torch.zeros(0, B, dtype=torch.float32, device=dev)
-                    result.traj_n_pairs = torch.zeros(0, B, dtype=torch.int64, device=dev)
-        return result
+    # run (Stepper.run): L-BFGS steps of every molecule that has not converged; the check-only launch measures fmax at the
+    # positions reached and marks what has converged there
+    def _frame(self):
+        return self._pos[self._cur].clone(), self._force.clone(), self._energy.clone(), self._n_pairs.long()
 
-    def _frame(self, k):
-        return (self.step_count + k, self._pos[self._cur].clone(), self._force.clone(), self._energy.clone(), self._n_pairs.long())
+    def _result(self):
+        return RelaxResult(self._pos[self._cur].clone(), self._energy.clone(), self._fmax.clone(), self._converged != 0,
+                           self._n_steps.long())

@@ -70,6 +70,19 @@ def table_masses(z: torch.Tensor) -> torch.Tensor:
     return m
 
 
+def lowest_mode_direction(model, z, pos, cell, batch, masses: torch.Tensor, solver: str):
+    """(u fp64 [N,3], n_imaginary [B]): every molecule's lowest normal mode as a Cartesian direction -- its mass-weighted
+    eigenvector divided by sqrt(m), not normalised -- and the molecule's count of imaginary modes.  The start direction of a
+    SaddleSearch or a ReactionPath that was given none."""
+    from newtonnet_amd.dynamics import _mol_ptr          # (dynamics imports this module)
+    B, dev = cell.shape[0], pos.device
+    nm = model.normal_modes(z, pos.detach(), cell, batch, masses=masses, solver=solver)
+    ptr = _mol_ptr(batch, B).long()
+    local = torch.arange(pos.shape[0], device=dev) - ptr[batch.long()]
+    q = nm.modes[(nm.blk_ptr[batch.long()] + 3 * local)[:, None] + torch.arange(3, device=dev)]
+    return q.double() / masses.double().sqrt()[:, None], nm.n_imaginary
+
+
 def max_dim() -> int:
     """Largest 3 n_b the one-workgroup solver serves (nnhip_eig_max_dim): the bound of solver='lds' and of
     NormalModes.sample(kernel='lds')."""
