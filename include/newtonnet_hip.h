@@ -1730,7 +1730,8 @@ int nnhip_npt_step(const float* pos_in, float* vel, const float* force, const fl
  * A crystal with d <= 32 gives each problem one wave (four problems per workgroup), a larger one a whole workgroup; the result of
  * a (b, q) does not depend on that, nor on the other problems of the launch.  No float atomics: bitwise repeatable.
  * Checked from cry_ptr_host BEFORE any launch: NNHIP_E_UNSUPPORTED above nnhip_phonon_max_dim (96: 32 atoms; A and the modes of a
- * problem take 16 d (d + 1) bytes of the 160 KiB of LDS), the message names the bound and the crystal.
+ * problem take 16 d (d + 1) bytes of the 160 KiB of LDS), the message names the bound and the crystal; nnhip_phonon_bands_large
+ * below serves larger crystals.
  *   nnhip_phonon_dos: density of states of values [val_ptr[b], val_ptr[b + 1]) per crystal over n_bins equal bins of [lo, hi]: one
  *     thread per bin walks the values in order.  counts (int32 [n_cry][n_bins], may be null): the histogram, integers only
  *     (a value equal to hi falls into the last bin, values outside are not counted).  density (fp32 [n_cry][n_bins], may be null;
@@ -1743,6 +1744,30 @@ int nnhip_phonon_bands(const float* fc, const int64_t* fc_ptr, const int32_t* cr
                        float* modes, float* dmat, int32_t* sweeps, int32_t* status, void* stream);
 int nnhip_phonon_dos(const float* values, const int64_t* val_ptr, int32_t n_cry, float lo, float hi, int32_t n_bins, float width,
                      int32_t* counts, float* density, void* stream);
+
+/* --------------------------------------------------------------------------
+ * The same dispersion above nnhip_phonon_max_dim (csrc/phonon_large.hip), opt-in: a two-sided BLOCK Jacobi for the complex Hermitian
+ * D(q) spread over many workgroups by kernel boundaries (no cooperative launch, no grid barrier, no spin-wait), D(q) and the modes of
+ * every (crystal, q) problem in the caller's workspace.  Arguments, layouts, stopping rule and status bits as nnhip_phonon_bands; an
+ * element of D(q) is formed by the same device functions, so dmat is bitwise that of nnhip_phonon_bands where both serve a crystal.
+ *   select_host [n_cry] (host, may be null = all): the crystals to compute; nothing of another crystal is touched in any output.
+ *   ws / ws_bytes: device workspace, 256-byte aligned, at least nnhip_phonon_large_ws_bytes(cry_ptr_host, n_cry, n_q, modes != null,
+ *     select_host): about 16 Mp^2 bytes per problem with modes, 8 Mp^2 without, Mp = d rounded up to a multiple of 64
+ *     (NNHIP_E_WORKSPACE).  A caller short of memory splits the wave vectors over several calls: a problem's result does not depend
+ *     on the other problems of the call.
+ * Checked from cry_ptr_host BEFORE any launch, for the selected crystals: NNHIP_E_UNSUPPORTED above nnhip_phonon_large_max_dim (768:
+ * 256 atoms -- the size the accuracy bound has been verified at), the message names the bound and the crystal.  The host reads one
+ * done flag per problem once per sweep (a stream synchronisation per sweep).  No float atomics: bitwise repeatable; modes == null
+ * leaves the eigenvalues bitwise the same.
+ * ------------------------------------------------------------------------ */
+int nnhip_phonon_large_max_dim(void);
+size_t nnhip_phonon_large_ws_bytes(const int32_t* cry_ptr_host, int32_t n_cry, int32_t n_q, int32_t want_modes,
+                                   const uint8_t* select_host);
+int nnhip_phonon_bands_large(const float* fc, const int64_t* fc_ptr, const int32_t* cry_ptr, const int32_t* cry_ptr_host,
+                             const int32_t* sc_atoms, const int64_t* img_ptr, const int32_t* img_start, const double* img_off,
+                             const float* masses, const int64_t* out_ptr, int32_t n_cry, const double* q, int32_t n_q, float* evals,
+                             float* modes, float* dmat, int32_t* sweeps, int32_t* status, const uint8_t* select_host, void* ws,
+                             size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * Analytic elastic constants of crystals.  The kernels, nnhip_elastic_fold and nnhip_elastic_relax are in csrc/elastic.hip;

@@ -26,11 +26,12 @@
 // of the crystal's own size, and no sum depends on the thread count, so the result of a (b, q) depends neither on the packing
 // nor on what else is in the launch.  No float atomics: two calls are bitwise equal.  modes == null skips W; A's arithmetic does
 // not read W, so the eigenvalues keep every bit.
+// The weight, the element and the Jacobi are device functions of csrc/phonon_common.h, which csrc/phonon_large.hip (primitive cells
+// above this file's bound) calls too.
 // LDS of a problem with modes: 4 planes of Mp (Mp + 1) floats + 48 Mp bytes of vectors + the tile table: 155 952 bytes at
 // d = 96 (32 atoms), the largest multiple of 3 that fits the 160 KiB of a CU (d = 99 needs 168 950).
-#include "eig_common.h"   // rr_pair, EIG_EPS2, EIG_MAX_SWEEPS: one statement of the ordering and of the stopping rule
+#include "phonon_common.h"   // the weight, the element and the complex Jacobi, shared with csrc/phonon_large.hip
 
-#define PH_THREADS 256
 #define PH_MAX_DIM 96
 #define PH_WAVE_DIM 32     // Mp up to which a problem is served by one wave
 #define PH_RCHUNK 8        // supercell copies whose phase factors are staged at a time
@@ -73,16 +74,6 @@ __host__ __device__ inline size_t ph_slot_bytes(int cap, bool want_v) {
                    + 8 * (size_t)cap * (cap + 1)   // Are, Aim
                    + ph_x_bytes(cap, want_v) + 2 * (size_t)(p * (p + 1) / 2);
   return (b + 15) & ~(size_t)15;
-}
-
-template <bool ONE_WAVE>
-__device__ __forceinline__ void ph_sync() {
-  if (ONE_WAVE) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the wave's LDS writes are done and not moved across
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
-  }
 }
 
 // one problem (crystal b, wave vector qi) on T = 64 (ONE_WAVE) or PH_THREADS threads, thread index t, in the LDS slot `smem` sized for cap
@@ -140,7 +131,7 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
     Are[i * ld + j] = 0.f;
     Aim[i * ld + j] = 0.f;
   }
-  for (int i = t; i < n; i += T) rowo[i] = 1.0 / sqrt((double)(g.masses ? g.masses[a0 + i] : 1.f));
+  for (int i = t; i < n; i += T) rowo[i] = ph_rsm(g.masses, a0 + i);
   ph_sync<ONE_WAVE>();
   const int N = g.sc_atoms[b];
   const int nR = N / n;
@@ -153,18 +144,7 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
       const int r = x / (n * n), rem = x - r * n * n;
       const int i = rem / n, j = rem - i * n;
       const size_t ij = (size_t)i * N + (size_t)(R0 + r) * n + j;
-      const int k0 = ist[ij], k1 = ist[ij + 1];
-      double sr = 0.0, si = 0.0;
-      for (int k = k0; k < k1; ++k) {
-        double ph = q0 * g.img_off[3 * (size_t)k] + q1 * g.img_off[3 * (size_t)k + 1] + q2 * g.img_off[3 * (size_t)k + 2];
-        ph -= rint(ph);   // [-1/2, 1/2]
-        double s, c;
-        sincospi(2.0 * ph, &s, &c);
-        sr += c;
-        si += s;
-      }
-      const double inv = k1 > k0 ? 1.0 / (double)(k1 - k0) : 0.0;
-      wch[x] = make_float2((float)(sr * inv), (float)(si * inv));
+      wch[x] = ph_weight(ist, g.img_off, ij, q0, q1, q2);
     }
     ph_sync<ONE_WAVE>();
     for (int e = t; e < M * M; e += T) {
@@ -172,12 +152,7 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
       const int i = a / 3, j = c / 3, beta = c - 3 * j;
       float are = Are[a * ld + c], aim = Aim[a * ld + c];
       const float* f = fc + ((size_t)a * N + (size_t)R0 * n + j) * 3 + beta;
-      for (int r = 0; r < rc; ++r) {
-        const float phi = f[(size_t)r * n * 3];
-        const float2 w = wch[(r * n + i) * n + j];
-        are = fmaf(phi, w.x, are);
-        aim = fmaf(phi, w.y, aim);
-      }
+      ph_accumulate(f, n, wch + i * n + j, n * n, rc, are, aim);
       Are[a * ld + c] = are;
       Aim[a * ld + c] = aim;
     }
@@ -187,8 +162,8 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
     const int a = e / M, c = e - a * M;
     if (a > c) continue;   // the thread of (a, c), a <= c, writes both halves: D is exactly Hermitian from here on
     const float f = (float)(rowo[a / 3] * rowo[c / 3]);
-    const float re = 0.5f * (Are[a * ld + c] + Are[c * ld + a]) * f;
-    const float im = a == c ? 0.f : 0.5f * (Aim[a * ld + c] - Aim[c * ld + a]) * f;
+    float re, im;
+    ph_hermitian(Are[a * ld + c], Aim[a * ld + c], Are[c * ld + a], Aim[c * ld + a], f, a == c, re, im);
     Are[a * ld + c] = re;
     Are[c * ld + a] = re;
     Aim[a * ld + c] = im;
@@ -204,147 +179,9 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
   }
 
   // ---- 2. Jacobi ------------------------------------------------------------------------------------------------------------
-  if (want_v) {
-    for (int e = t; e < Mp * Mp; e += T) {
-      const int i = e / Mp, j = e - i * Mp;
-      Wre[i * ld + j] = i == j ? 1.f : 0.f;
-      Wim[i * ld + j] = 0.f;
-    }
-  }
-  const int n_tiles = P * (P + 1) / 2;
-  int n_sweeps = 0;
-  bool converged = false;
-  for (;;) {
-    for (int i = t; i < Mp; i += T) {
-      double o = 0.0, dd = 0.0;
-      for (int j = 0; j < Mp; ++j) {
-        const double re = (double)Are[i * ld + j], im = (double)Aim[i * ld + j];
-        const double v = re * re + im * im;
-        if (i == j) dd += v; else o += v;
-      }
-      rowo[i] = o;
-      rowd[i] = dd;
-    }
-    ph_sync<ONE_WAVE>();
-    double off = 0.0, diag = 0.0;
-    for (int i = 0; i < Mp; ++i) {
-      off += rowo[i];
-      diag += rowd[i];
-    }
-    converged = off <= EIG_EPS2 * (off + diag) && off + diag <= 1.7976931348623157e308;
-    if (converged || n_sweeps == EIG_MAX_SWEEPS) break;   // (uniform: every thread holds the same sums)
-    for (int s = 0; s < Mp - 1; ++s) {
-      for (int k = t; k < P; k += T) {
-        int p, q;
-        rr_pair(k, s, Mp, p, q);
-        const float ar = Are[p * ld + q], ai = Aim[p * ld + q];
-        const float ab = hypotf(ar, ai);
-        float c = 1.f, sn = 0.f, ur = 1.f, ui = 0.f, dl = 0.f;
-        if (ab != 0.f) {
-          // |u| = 1 is what keeps W unitary.  A coupling that has converged into the denormal range (a pair that settles sweeps
-          // before the matrix does, as in a graded spectrum) has too few bits left for its modulus to normalise it: scale it
-          // up first (exact).  tau below takes the modulus as it is.
-          float sr = ar, si = ai, sb = ab;
-          if (ab < 0x1p-100f) {
-            sr = ar * 0x1p64f;
-            si = ai * 0x1p64f;
-            sb = hypotf(sr, si);
-          }
-          ur = sr / sb;
-          ui = si / sb;
-          const float tau = (Are[q * ld + q] - Are[p * ld + p]) / (2.f * ab);
-          const float tn = copysignf(1.f, tau) / (fabsf(tau) + sqrtf(1.f + tau * tau));   // (tau^2 = inf: t = 0, the identity)
-          c = 1.f / sqrtf(1.f + tn * tn);
-          sn = tn * c;
-          dl = tn * ab;
-        }
-        cst[k] = make_float4(c, sn, ur, ui);
-        dlt[k] = dl;
-      }
-      ph_sync<ONE_WAVE>();
-      for (int e = t; e < n_tiles; e += T) {
-        const int kl = tab[e];
-        const int k = kl & 255, l = kl >> 8;
-        int pk, qk, pl, ql;
-        rr_pair(k, s, Mp, pk, qk);
-        const float4 rk = cst[k];
-        if (k == l) {
-          const float dl = dlt[k];
-          Are[pk * ld + pk] -= dl;
-          Are[qk * ld + qk] += dl;
-          Are[pk * ld + qk] = 0.f;
-          Aim[pk * ld + qk] = 0.f;
-          Are[qk * ld + pk] = 0.f;
-          Aim[qk * ld + pk] = 0.f;
-          continue;
-        }
-        rr_pair(l, s, Mp, pl, ql);
-        const float4 rl = cst[l];
-        const float b00r = Are[pk * ld + pl], b00i = Aim[pk * ld + pl], b01r = Are[pk * ld + ql], b01i = Aim[pk * ld + ql];
-        float b10r = Are[qk * ld + pl], b10i = Aim[qk * ld + pl], b11r = Are[qk * ld + ql], b11i = Aim[qk * ld + ql];
-        // rows q_k times u_k
-        float xr = rk.z * b10r - rk.w * b10i, xi = rk.z * b10i + rk.w * b10r;
-        b10r = xr;
-        b10i = xi;
-        xr = rk.z * b11r - rk.w * b11i;
-        xi = rk.z * b11i + rk.w * b11r;
-        b11r = xr;
-        b11i = xi;
-        // the real rotation of pair k on the rows
-        const float r00r = rk.x * b00r - rk.y * b10r, r00i = rk.x * b00i - rk.y * b10i;
-        const float r10r = rk.y * b00r + rk.x * b10r, r10i = rk.y * b00i + rk.x * b10i;
-        float r01r = rk.x * b01r - rk.y * b11r, r01i = rk.x * b01i - rk.y * b11i;
-        float r11r = rk.y * b01r + rk.x * b11r, r11i = rk.y * b01i + rk.x * b11i;
-        // columns q_l times conj(u_l)
-        xr = rl.z * r01r + rl.w * r01i;
-        xi = rl.z * r01i - rl.w * r01r;
-        r01r = xr;
-        r01i = xi;
-        xr = rl.z * r11r + rl.w * r11i;
-        xi = rl.z * r11i - rl.w * r11r;
-        r11r = xr;
-        r11i = xi;
-        // the real rotation of pair l on the columns
-        const float n00r = rl.x * r00r - rl.y * r01r, n00i = rl.x * r00i - rl.y * r01i;
-        const float n01r = rl.y * r00r + rl.x * r01r, n01i = rl.y * r00i + rl.x * r01i;
-        const float n10r = rl.x * r10r - rl.y * r11r, n10i = rl.x * r10i - rl.y * r11i;
-        const float n11r = rl.y * r10r + rl.x * r11r, n11i = rl.y * r10i + rl.x * r11i;
-        Are[pk * ld + pl] = n00r;
-        Aim[pk * ld + pl] = n00i;
-        Are[pl * ld + pk] = n00r;
-        Aim[pl * ld + pk] = -n00i;
-        Are[pk * ld + ql] = n01r;
-        Aim[pk * ld + ql] = n01i;
-        Are[ql * ld + pk] = n01r;
-        Aim[ql * ld + pk] = -n01i;
-        Are[qk * ld + pl] = n10r;
-        Aim[qk * ld + pl] = n10i;
-        Are[pl * ld + qk] = n10r;
-        Aim[pl * ld + qk] = -n10i;
-        Are[qk * ld + ql] = n11r;
-        Aim[qk * ld + ql] = n11i;
-        Are[ql * ld + qk] = n11r;
-        Aim[ql * ld + qk] = -n11i;
-      }
-      if (want_v) {
-        for (int e = t; e < P * Mp; e += T) {
-          const int k = e / Mp, j = e - k * Mp;
-          int pk, qk;
-          rr_pair(k, s, Mp, pk, qk);
-          const float4 rk = cst[k];
-          const float vpr = Wre[pk * ld + j], vpi = Wim[pk * ld + j];
-          const float wr = Wre[qk * ld + j], wi = Wim[qk * ld + j];
-          const float vqr = rk.z * wr + rk.w * wi, vqi = rk.z * wi - rk.w * wr;   // row q_k times conj(u_k)
-          Wre[pk * ld + j] = rk.x * vpr - rk.y * vqr;
-          Wim[pk * ld + j] = rk.x * vpi - rk.y * vqi;
-          Wre[qk * ld + j] = rk.y * vpr + rk.x * vqr;
-          Wim[qk * ld + j] = rk.y * vpi + rk.x * vqi;
-        }
-      }
-      ph_sync<ONE_WAVE>();
-    }
-    ++n_sweeps;
-  }
+  bool converged;
+  const int n_sweeps = ph_jacobi<ONE_WAVE>(Are, Aim, Wre, Wim, Mp, ld, rowo, rowd, cst, dlt, tab, want_v, EIG_EPS2, EIG_MAX_SWEEPS, t,
+                                           converged);
   if (t == 0) {
     g.sweeps[prob] = n_sweeps;
     g.status[prob] = converged ? 0 : NNHIP_EIG_STATUS_SWEEPS;
@@ -364,18 +201,7 @@ __device__ __forceinline__ void ph_problem(const PhArgs& g, int b, int qi, char*
     rank[i] = r;
     evals[r] = di;
     if (want_v) {
-      float best = -1.f, fr = 1.f, fi = 0.f;
-      for (int j = 0; j < M; ++j) {
-        const float vr = Wre[i * ld + j], vi = Wim[i * ld + j];
-        const float a2 = vr * vr + vi * vi;
-        if (a2 > best) {
-          best = a2;
-          fr = vr;
-          fi = vi;
-        }
-      }
-      const float ab = hypotf(fr, fi);
-      phs[i] = ab > 0.f ? make_float2(fr / ab, -fi / ab) : make_float2(1.f, 0.f);
+      phs[i] = ph_phase(Wre + i * ld, Wim + i * ld, M);
     }
   }
   if (want_v) {

@@ -20,8 +20,12 @@ Supercells.  The model's neighbour list takes a single minimum image, so -- exac
 supercell whose perpendicular widths are at least twice the cutoff, a cell that is not orthogonal must be a symmetric matrix, and
 the sums are divided by the supercell's volume.  Lambda is read at the home atoms.
 
-Left out: finite-strain and third-order constants, Birch coefficients, the relaxed term above max_dim() coordinates per primitive
-cell, piezoelectric terms, symmetry reduction of the six strains.
+Size.  The relaxed term serves primitive cells of up to max_dim() = 96 coordinates by default (solver='lds': the bound of the
+one-workgroup phonon kernel) and, with solver='auto' / 'blocked', of up to max_dim_large() = 768 (256 atoms): the keyword is
+handed to vibrations.eig_blocks and to the Phonons the call computes; nnhip_elastic_fold and nnhip_elastic_relax have no limit.
+
+Left out: finite-strain and third-order constants, Birch coefficients, piezoelectric terms, symmetry reduction of the six
+strains.
 """
 from __future__ import annotations
 
@@ -47,6 +51,12 @@ def max_dim() -> int:
     return _ph.max_dim()
 
 
+def max_dim_large() -> int:
+    """Largest 3 n_b the relaxed-ion term serves with solver='auto' / 'blocked': the smaller of the bounds of the two blocked
+    solvers (phonons.max_dim_large(), vibrations.max_dim_large())."""
+    return min(_ph.max_dim_large(), _v.max_dim_large())
+
+
 def voigt_matrices(e) -> np.ndarray:
     """fp64 [..., 3, 3]: eps of Voigt components e [..., 6] (engineering shears)."""
     e = np.asarray(e, dtype=np.float64)
@@ -56,7 +66,14 @@ def voigt_matrices(e) -> np.ndarray:
     return out
 
 
-def _check_bound(counts):
+def _check_bound(counts, solver: str = 'lds'):
+    if solver != 'lds':
+        bound = max_dim_large()
+        for b, n in enumerate(counts):
+            if 3 * n > bound:
+                raise NotImplementedError(f'crystal {b} has 3 x {n} = {3 * n} coordinates per primitive cell, above the {bound} of '
+                                          f'elastic.max_dim_large() that the relaxed-ion term serves: relaxed=False has no size limit')
+        return
     bound = max_dim()
     for b, n in enumerate(counts):
         if 3 * n > bound:
@@ -169,21 +186,25 @@ def fold_force_constants(ph) -> torch.Tensor:
     return phi0
 
 
-def relaxation_term(phi0: torch.Tensor, blk_ptr: torch.Tensor, counts, lam: torch.Tensor, tol_zero: Optional[float] = None):
+def relaxation_term(phi0: torch.Tensor, blk_ptr: torch.Tensor, counts, lam: torch.Tensor, tol_zero: Optional[float] = None,
+                    solver: str = 'lds'):
     """(R fp32 [B,6,6], n_zero, n_negative, status int32 [B]) with R = Lambda^T pinv(Phi0) Lambda: phi0 packed [n_b,3,n_b,3] blocks at
     blk_ptr (int64 [B]), counts the atoms per crystal (list), lam fp32 [3 n, 6].  The eigenpairs come from vibrations.eig_blocks
     (unit masses, no projection); a mode counts as zero when |lambda| <= vibrations.zero_threshold (tol_zero overrides its
-    relative tolerance)."""
+    relative tolerance).  solver: 'lds' (default: up to max_dim() coordinates), 'auto' or 'blocked' (up to max_dim_large()), handed
+    to vibrations.eig_blocks."""
+    _ph._check_solver(solver)
     dev, B, n = phi0.device, len(counts), sum(counts)
     if tuple(lam.shape) != (3 * n, 6) or lam.dtype != torch.float32:
         raise ValueError(f'Lambda: float32 [{3 * n}, 6] expected (got {tuple(lam.shape)})')
-    bound = max_dim()
+    bound = max_dim() if solver == 'lds' else max_dim_large()
     for b, k in enumerate(counts):
         if 3 * k > bound:
-            raise NotImplementedError(f'crystal {b} has 3 x {k} = {3 * k} coordinates, above the {bound} of elastic.max_dim()')
+            raise NotImplementedError(f'crystal {b} has 3 x {k} = {3 * k} coordinates, above the {bound} of elastic.'
+                                      f'{"max_dim()" if solver == "lds" else "max_dim_large()"}')
     batch = torch.repeat_interleave(torch.arange(B), torch.tensor(counts, dtype=torch.long)).to(dev)
     nm = _v.eig_blocks(phi0, blk_ptr, batch, torch.zeros(n, 3, device=dev), torch.zeros(B, 3, 3, device=dev), None, project=False,
-                       modes=True, tol_zero=tol_zero, counts=torch.tensor(counts, dtype=torch.long))
+                       modes=True, tol_zero=tol_zero, counts=torch.tensor(counts, dtype=torch.long), solver=solver)
     cry = torch.zeros(B + 1, dtype=torch.int32)
     cry[1:] = torch.cumsum(torch.tensor(counts, dtype=torch.int32), 0)
     cry = cry.to(dev)
@@ -199,15 +220,18 @@ def relaxation_term(phi0: torch.Tensor, blk_ptr: torch.Tensor, counts, lam: torc
 
 
 def elastic_constants(model, z, pos, cell, batch, supercell=(1, 1, 1), relaxed: bool = True, phonons=None,
-                      tol_zero: Optional[float] = None, replicas: Optional[int] = None) -> ElasticConstants:
+                      tol_zero: Optional[float] = None, replicas: Optional[int] = None, solver: str = 'lds') -> ElasticConstants:
     """Elastic constants of every crystal of the batch (z, pos, cell, batch: the primitive cells) at the current parameters; see
     the module text.  supercell: three integers or an integer [B,3], checked as phonons.phonons checks it.  relaxed=True adds
     the relaxed-ion term from `phonons` (a Phonons of the same crystals on the same supercell) or, when None, from
     model.phonons(..., asr=True); it needs zero forces to mean anything and serves primitive cells of up to max_dim()
     coordinates (NotImplementedError above).  relaxed=False: the clamped-ion constants, no size limit.  tol_zero: relative zero
     threshold of the modes of Phi0 (None: vibrations.zero_threshold's).  replicas: strains per pass (None: as many of the six as
-    REPLICA_ATOM_BUDGET allows)."""
-    cells, S, counts = _ph._checked_crystals(model, z, pos, cell, batch, supercell, _check_bound if relaxed else None)
+    REPLICA_ATOM_BUDGET allows).  solver: 'lds' (default), 'auto' or 'blocked': with the latter two the relaxed term serves
+    primitive cells of up to max_dim_large() coordinates (see the module text)."""
+    _ph._check_solver(solver)
+    cells, S, counts = _ph._checked_crystals(model, z, pos, cell, batch, supercell,
+                                             (lambda c: _check_bound(c, solver)) if relaxed else None)
     B = len(counts)
     if phonons is not None and relaxed:
         if list(phonons.counts) != list(counts) or not np.array_equal(np.asarray(phonons.supercell), S):
@@ -230,8 +254,8 @@ def elastic_constants(model, z, pos, cell, batch, supercell=(1, 1, 1), relaxed: 
     relaxation = torch.zeros_like(born)
     n_zero, n_neg, status = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(3))
     if relaxed:
-        ph = phonons if phonons is not None else model.phonons(z, pos, cell, batch, supercell, asr=True)
-        r, n_zero, n_neg, status = relaxation_term(fold_force_constants(ph), ph.out_ptr, counts, lam, tol_zero)
+        ph = phonons if phonons is not None else model.phonons(z, pos, cell, batch, supercell, asr=True, solver=solver)
+        r, n_zero, n_neg, status = relaxation_term(fold_force_constants(ph), ph.out_ptr, counts, lam, tol_zero, solver)
         relaxation = (r.double() / torch.tensor(vol, dtype=torch.float64, device=dev)[:, None, None]).float()
     return ElasticConstants(born=born, relaxation=relaxation, C=born - relaxation, asymmetry=asym, internal_strain=lam,
                             volume=torch.tensor(vol, dtype=torch.float64), status=status, n_zero=n_zero, n_negative=n_neg,

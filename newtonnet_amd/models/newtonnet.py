@@ -744,16 +744,17 @@ class NewtonNet(nn.Module):
             return _h.strain_vector_product(self, z, pos, cell, batch, strain)
 
     def elastic_constants(self, z, pos, cell, batch, supercell=(1, 1, 1), relaxed: bool = True, phonons=None, tol_zero=None,
-                          replicas=None):
+                          replicas=None, solver: str = 'lds'):
         """Analytic elastic constants C_IJ = (1 / V) d^2E / de_I de_J (eV / A^3) of B crystals as a newtonnet_amd.elastic
         .ElasticConstants: the clamped-ion (Born) tensor from six strain tangent passes on a supercell (checked as phonons()
         checks it), and with relaxed=True the relaxed-ion correction Lambda^T pinv(Phi0) Lambda / V from the force constants at
         Gamma (`phonons`: a Phonons of this call's crystals and supercell; None computes one), which assumes zero forces and
-        serves primitive cells of up to elastic.max_dim() / 3 = 32 atoms.  Its helpers give GPa, compliance, Voigt / Reuss / Hill
+        serves primitive cells of up to elastic.max_dim() / 3 = 32 atoms (solver='auto' / 'blocked': elastic.max_dim_large() / 3 =
+        256 atoms, through the blocked eigensolvers).  Its helpers give GPa, compliance, Voigt / Reuss / Hill
         moduli and the stability eigenvalue.  Eval mode only; needs the 'energy' head; uses the current parameters."""
         from newtonnet_amd import elastic as _e
         return _e.elastic_constants(self, z, pos, cell, batch, supercell=supercell, relaxed=relaxed, phonons=phonons,
-                                    tol_zero=tol_zero, replicas=replicas)
+                                    tol_zero=tol_zero, replicas=replicas, solver=solver)
 
     def normal_modes(self, z, pos, cell, batch, masses=None, project: bool = True, modes: bool = True, tol_zero=None,
                      solver: str = 'lds'):
@@ -774,16 +775,18 @@ class NewtonNet(nn.Module):
             return _v.normal_modes(self, z, pos, cell, batch, masses=masses, project=project, modes=modes, tol_zero=tol_zero,
                                    solver=solver)
 
-    def phonons(self, z, pos, cell, batch, supercell, masses=None, asr: bool = True):
+    def phonons(self, z, pos, cell, batch, supercell, masses=None, asr: bool = True, solver: str = 'lds'):
         """Phonons of B crystals (z, pos, cell, batch are their primitive cells, every cell non-zero): the analytic force
         constants of the home atoms on a supercell (`supercell`: three integers, or an integer [B, 3]; every perpendicular
         width of it at least twice the cutoff), as a newtonnet_amd.phonons.Phonons.  Its frequencies(q) / band_structure(points,
         n) / mesh(n1, n2, n3) assemble and diagonalise the dynamical matrix of every (crystal, wave vector) pair in one launch
         (csrc/phonon.hip); the mesh gives dos(n_bins, width) and thermochemistry(T) per primitive cell.  masses: fp32 [N] amu
         (None: standard atomic weights of z); asr: impose the acoustic sum rule.  Primitive cells of up to phonons.max_dim() / 3
-        = 32 atoms.  Eval mode only; needs the 'energy' head; uses the current parameters."""
+        = 32 atoms with solver='lds' (default); solver='auto' sends larger cells, up to phonons.max_dim_large() / 3 = 256 atoms,
+        through the blocked solver (csrc/phonon_large.hip), the others exactly as before; solver='blocked': all of them.  Eval mode
+        only; needs the 'energy' head; uses the current parameters."""
         from newtonnet_amd import phonons as _p
-        return _p.phonons(self, z, pos, cell, batch, supercell, masses=masses, asr=asr)
+        return _p.phonons(self, z, pos, cell, batch, supercell, masses=masses, asr=asr, solver=solver)
 
     def sample_displacements(self, z, pos, cell, batch, n_samples: int, temperature: float, quantum: bool = False, masses=None,
                              generator=None, solver: str = 'lds'):

@@ -4,6 +4,9 @@ normal_modes treats a periodic system as a molecule at Gamma.  Here B primitive 
 supercell method: the analytic Hessian columns of the home atoms on a supercell (nnhip_hessian_blocks with n_dirs = 3 n_b) are
 the force constants Phi(i, J); ONE launch of nnhip_phonon_bands (csrc/phonon.hip) then assembles the dynamical matrix D(q) and
 diagonalises the complex Hermitian d x d problem (d = 3 n_b) for every crystal and every wave vector of a path or a mesh.
+That form keeps a problem in the LDS of one workgroup and serves primitive cells up to max_dim() = 96 coordinates (32 atoms);
+solver='auto' sends larger ones, up to max_dim_large() = 768 coordinates (256 atoms), through the blocked solver
+nnhip_phonon_bands_large (csrc/phonon_large.hip), which keeps D(q) in a torch-owned workspace in HBM.
 
 Convention.  Supercell atom J = R n_b + j is the copy of home atom j at lattice offset R (the home cell R = 0 first, then the
 offsets in lexicographic order, last index fastest).  For each (i, J) the image table holds the supercell-lattice translations
@@ -16,7 +19,7 @@ primitive reciprocal vectors (q_frac . x_frac = q . r / 2 pi).
 Units as in vibrations.py: eigenvalues in eV / (A^2 amu), frequencies in cm^-1 (x 521.4709, negative = imaginary).
 
 Left out: the non-analytic LO-TO correction (it needs Born charges, which the model has not got), symmetry reduction of meshes
-and paths, group velocities, primitive cells above max_dim() coordinates.
+and paths, group velocities, primitive cells above max_dim_large() coordinates.
 """
 from __future__ import annotations
 
@@ -32,12 +35,34 @@ from newtonnet_amd import vibrations as _v
 
 TIE_TOL = 1e-8          # relative tolerance at which two images count as equally near
 EPS32 = _v.EPS32
+SOLVERS = _v.SOLVERS
+LARGE_WORKSPACE_BYTES = 1 << 30   # the wave vectors of a blocked call are chunked so that a chunk's workspace stays within this
+IMAGE_TABLE_BYTES = 1 << 28       # image_table walks the home atoms in chunks whose candidate array stays within this
 
 
 def max_dim() -> int:
     """Largest d = 3 n_b of a primitive cell nnhip_phonon_bands serves (nnhip_phonon_max_dim): the dynamical matrix and its
     eigenvectors of one (crystal, q) problem live in the LDS of one workgroup."""
     return int(hip.lib().nnhip_phonon_max_dim())
+
+
+def max_dim_large() -> int:
+    """Largest d = 3 n_b the blocked solver serves (nnhip_phonon_large_max_dim; solver='auto' / 'blocked'): the size its accuracy
+    bound has been verified at; the workspace takes about 16 Mp^2 bytes per (crystal, q) problem with modes."""
+    return int(hip.lib().nnhip_phonon_large_max_dim())
+
+
+def _check_solver(solver) -> str:
+    if solver not in SOLVERS:
+        raise ValueError(f"solver: one of 'lds', 'auto', 'blocked' expected (got {solver!r})")
+    return solver
+
+
+def plan_q_chunks(n_q: int, bytes_per_q: int, budget: int):
+    """[(start, stop)]: the wave vectors 0 .. n_q - 1 in order, in chunks of as many as fit `budget` bytes of workspace at
+    bytes_per_q each, one at least."""
+    step = max(1, int(budget) // max(1, int(bytes_per_q)))
+    return [(a, min(a + step, n_q)) for a in range(0, n_q, step)]
 
 
 # ---- host helpers (numpy, fp64) ----------------------------------------------------------------------------------------------
@@ -77,14 +102,22 @@ def image_table(pos, cell, supercell, tol: float = TIE_TOL):
     frac = pos @ np.linalg.inv(cell)
     n = len(pos)
     fJ = (lattice_offsets(supercell).astype(np.float64)[:, None, :] + frac[None, :, :]).reshape(-1, 3)
-    x = fJ[None, :, None, :] - frac[:, None, None, :] + (_T27 * S)[None, None, :, :]          # [n, N, 27, 3]
-    dist = np.linalg.norm(x @ cell, axis=-1)
-    keep = dist <= dist.min(axis=-1, keepdims=True) * (1.0 + tol)
+    # the home atoms in chunks (every row is independent, so the output does not depend on the chunk): x and x @ cell take
+    # 2 x 27 x 3 x 8 bytes per pair
+    rows = max(1, IMAGE_TABLE_BYTES // (1296 * max(1, len(fJ))))
+    counts, kept = [], []
+    for i0 in range(0, n, rows):
+        x = fJ[None, :, None, :] - frac[i0:i0 + rows, None, None, :] + (_T27 * S)[None, None, :, :]      # [rows, N, 27, 3]
+        dist = np.linalg.norm(x @ cell, axis=-1)
+        keep = dist <= dist.min(axis=-1, keepdims=True) * (1.0 + tol)
+        counts.append(keep.sum(axis=-1).reshape(-1))
+        kept.append(x[keep])
     start = np.zeros(n * len(fJ) + 1, dtype=np.int64)
-    np.cumsum(keep.sum(axis=-1).reshape(-1), out=start[1:])
+    if counts:
+        np.cumsum(np.concatenate(counts), out=start[1:])
     if start[-1] >= 2 ** 31:
         raise NotImplementedError('image table above 2^31 entries')
-    return start.astype(np.int32), np.ascontiguousarray(x[keep])
+    return start.astype(np.int32), np.ascontiguousarray(np.concatenate(kept) if kept else np.zeros((0, 3)))
 
 
 def monkhorst_pack(n1: int, n2: int, n3: int, shift: bool = False) -> np.ndarray:
@@ -162,10 +195,13 @@ def _counts(batch, n_cry: int, n_atoms: int):
     return counts
 
 
-def _check_bound(counts):
-    bound = max_dim()
+def _check_bound(counts, solver: str = 'lds'):
+    bound, large = max_dim(), max_dim_large()
     for b, n in enumerate(counts):
-        if 3 * n > bound:
+        if 3 * n > large:
+            raise NotImplementedError(f'crystal {b} has 3 x {n} = {3 * n} coordinates per primitive cell, above the {large} of '
+                                      f'phonons.max_dim_large() (nnhip_phonon_large_max_dim), the bound of every solver')
+        if solver == 'lds' and 3 * n > bound:
             raise NotImplementedError(f'crystal {b} has 3 x {n} = {3 * n} coordinates per primitive cell, above the {bound} of '
                                       f'phonons.max_dim() (nnhip_phonon_max_dim)')
 
@@ -320,6 +356,7 @@ class Phonons:
     counts, sc_counts   atoms per primitive cell n_b / per supercell N_b (lists)
     supercell    int numpy [B, 3]
     masses       fp32 [n] amu;  z, pos, cell: the primitive cells
+    solver       'lds' | 'auto' | 'blocked': the default of frequencies / band_structure / mesh (see frequencies)
     """
 
     def __init__(self, **kw):
@@ -330,13 +367,16 @@ class Phonons:
         return self.fc[o:o + 9 * n * N].view(n, 3, N, 3)
 
     @classmethod
-    def from_force_constants(cls, fc, z, pos, cell, supercell, masses=None, batch=None, device=None) -> 'Phonons':
+    def from_force_constants(cls, fc, z, pos, cell, supercell, masses=None, batch=None, device=None,
+                             solver: str = 'lds') -> 'Phonons':
         """A Phonons from force constants the caller has: fc is one [n, 3, N, 3] array / tensor, a list of them (one per
         crystal), or the packed 1-d tensor; z [n_total], pos [n_total, 3], cell [B, 3, 3] (or [3, 3]) are the primitive cells,
         batch [n_total] their crystal index (None: one crystal).  N_b must be n_b x prod(supercell_b), the supercell atoms in the
         order of build_supercell.  masses: amu per home atom (None: standard atomic weights of z).  No width check and no
         acoustic sum rule: the force constants are taken as they are.  device: where the tables go (default: that of fc when
-        it is a tensor, else of pos when it is one, else 'cuda')."""
+        it is a tensor, else of pos when it is one, else 'cuda').  solver: see frequencies; 'lds' refuses a primitive cell above
+        max_dim() coordinates here, every solver one above max_dim_large()."""
+        _check_solver(solver)
         if device is None:
             src = fc if isinstance(fc, torch.Tensor) else fc[0] if isinstance(fc, (list, tuple)) and fc and \
                 isinstance(fc[0], torch.Tensor) else pos if isinstance(pos, torch.Tensor) else None
@@ -377,17 +417,17 @@ class Phonons:
             if fc_t.dim() != 1 or fc_t.numel() != sum(sizes):
                 raise ValueError(f'fc: packed 1-d with {sum(sizes)} values expected (got {tuple(fc_t.shape)})')
             fc_t = hip._f32c(fc_t, 'fc').to(device)
-        _check_bound(counts)
+        _check_bound(counts, solver)
         if masses is None:
             m_t = _v.table_masses(z_t)
         else:
             m_t = torch.as_tensor(np.asarray(masses) if not isinstance(masses, torch.Tensor) else masses).detach().reshape(-1)
             if m_t.numel() != n_total:
                 raise ValueError(f'masses: {m_t.numel()} values for {n_total} atoms')
-        return cls._assemble(fc_t.contiguous(), z_t, pos_t, cell_t, cells, S, counts, sc_counts, m_t, device)
+        return cls._assemble(fc_t.contiguous(), z_t, pos_t, cell_t, cells, S, counts, sc_counts, m_t, device, solver)
 
     @classmethod
-    def _assemble(cls, fc_t, z_t, pos_t, cell_t, cells, S, counts, sc_counts, m_t, device) -> 'Phonons':
+    def _assemble(cls, fc_t, z_t, pos_t, cell_t, cells, S, counts, sc_counts, m_t, device, solver: str = 'lds') -> 'Phonons':
         """the image tables (host, fp64, once per crystal) and the offset arrays of nnhip_phonon_bands"""
         B = len(counts)
         pos_h = pos_t.detach().double().cpu().numpy()
@@ -416,17 +456,26 @@ class Phonons:
                    img_start=dev(np.concatenate(starts) if starts else np.zeros(0), torch.int32),
                    img_off=dev(np.concatenate(offs) if offs else np.zeros((0, 3)), torch.float64).contiguous(),
                    out_ptr=dev(np.cumsum(sq) - sq, torch.int64), _sq_offsets=(np.cumsum(sq) - sq).tolist(),
-                   _offsets=(3 * cry[:-1]).tolist(), _dims=[3 * n for n in counts])
+                   _offsets=(3 * cry[:-1]).tolist(), _dims=[3 * n for n in counts], solver=solver)
 
     # ---- wave vectors ---------------------------------------------------------------------------------------------------------
-    def frequencies(self, q, modes: bool = False, dynamical_matrix: bool = False) -> PhononBands:
-        """The spectra at the wave vectors q ([Q, 3], units of the primitive reciprocal vectors, shared by all crystals) in one
-        launch of nnhip_phonon_bands.  modes=True also returns the eigenvectors; the eigenvalues are bitwise the same either
-        way, and those of a q do not depend on the other q of the call.  dynamical_matrix=True also returns D(q)."""
+    def frequencies(self, q, modes: bool = False, dynamical_matrix: bool = False, solver: Optional[str] = None,
+                    workspace_bytes: Optional[int] = None) -> PhononBands:
+        """The spectra at the wave vectors q ([Q, 3], units of the primitive reciprocal vectors, shared by all crystals).
+        modes=True also returns the eigenvectors; the eigenvalues are bitwise the same either way, and those of a q do not
+        depend on the other q of the call.  dynamical_matrix=True also returns D(q).
+        solver (None: the object's): 'lds' -- one launch of nnhip_phonon_bands, NotImplementedError above max_dim() = 96
+        coordinates; 'auto' -- crystals up to max_dim() through nnhip_phonon_bands, bitwise as under 'lds', the others through the
+        blocked solver nnhip_phonon_bands_large (up to max_dim_large() = 768 coordinates; sweeps counts its OUTER sweeps);
+        'blocked' -- every crystal through the blocked solver.  All land in one packed PhononBands.  The blocked solver works in
+        a torch-owned workspace; the wave vectors are served in chunks whose workspace stays within workspace_bytes (None:
+        LARGE_WORKSPACE_BYTES; a chunk holds one q at least) -- the result does not depend on the chunking."""
+        solver = _check_solver(self.solver if solver is None else solver)
         qh = q.detach().double().cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q, dtype=np.float64)
         qh = np.ascontiguousarray(qh.reshape(-1, 3) if qh.size else qh.reshape(0, 3))
         if not np.isfinite(qh).all():
             raise ValueError('q: finite wave vectors expected')
+        _check_bound(self.counts, solver)
         dev = self.fc.device
         if dev.type != 'cuda':
             raise RuntimeError('newtonnet_amd phonons run on an MI355X (ROCm) device only: build the Phonons on "cuda"')
@@ -438,31 +487,93 @@ class Phonons:
         sweeps, status = (torch.zeros(B, Q, dtype=torch.int32, device=dev) for _ in range(2))
         q_dev = torch.tensor(qh, dtype=torch.float64).to(dev)
         if B and Q and n_val:
-            rc = hip.lib().nnhip_phonon_bands(hip._ptr(self.fc), hip._ptr(self.fc_ptr), hip._ptr(self.cry_ptr), self._cry_host.data_ptr(),
-                                              hip._ptr(self.sc_atoms), hip._ptr(self.img_ptr), hip._ptr(self.img_start),
-                                              hip._ptr(self.img_off), hip._ptr(self.masses), hip._ptr(self.out_ptr), B, hip._ptr(q_dev), Q,
-                                              hip._ptr(evals), hip._ptr(vec), hip._ptr(dm), hip._ptr(sweeps), hip._ptr(status),
-                                              hip._stream(dev))
-            if rc == 2:
-                raise NotImplementedError(hip.lib().nnhip_last_error().decode())
-            hip._check(rc, 'nnhip_phonon_bands')
+            bound = max_dim()
+            large = [False] * B if solver == 'lds' else [n > 0 and (solver == 'blocked' or 3 * n > bound) for n in self.counts]
+            b = 0
+            while b < B:   # nnhip_phonon_bands on every run of consecutive crystals it serves: the same call, the per-crystal pointers moved up
+                if large[b]:
+                    b += 1
+                    continue
+                e = b
+                while e < B and not large[e]:
+                    e += 1
+                if sum(self.counts[b:e]):
+                    rc = hip.lib().nnhip_phonon_bands(hip._ptr(self.fc), self.fc_ptr.data_ptr() + 8 * b, self.cry_ptr.data_ptr() + 4 * b,
+                                                      self._cry_host.data_ptr() + 4 * b, self.sc_atoms.data_ptr() + 4 * b,
+                                                      self.img_ptr.data_ptr() + 8 * b, hip._ptr(self.img_start), hip._ptr(self.img_off),
+                                                      hip._ptr(self.masses), self.out_ptr.data_ptr() + 8 * b, e - b, hip._ptr(q_dev), Q,
+                                                      hip._ptr(evals), hip._ptr(vec), hip._ptr(dm), sweeps.data_ptr() + 4 * Q * b,
+                                                      status.data_ptr() + 4 * Q * b, hip._stream(dev))
+                    if rc == 2:
+                        raise NotImplementedError(hip.lib().nnhip_last_error().decode())
+                    hip._check(rc, 'nnhip_phonon_bands')
+                b = e
+            if any(large):
+                self._bands_large(large, q_dev, evals, vec, dm, sweeps, status,
+                                  LARGE_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes))
         freq = torch.sign(evals) * evals.abs().sqrt() * _v.WAVENUMBER_PER_SQRT_EIGENVALUE
         return PhononBands(eigenvalues=evals, frequencies=freq, modes=None if vec is None else torch.view_as_complex(vec),
                            dynamical_matrix=None if dm is None else torch.view_as_complex(dm), sweeps=sweeps, status=status, q=qh,
                            _dims=self._dims, _offsets=self._offsets, _sq_offsets=self._sq_offsets)
 
-    def band_structure(self, points, n_per_segment: int = 20, modes: bool = False) -> PhononBands:
+    def _bands_large(self, large, q_dev, evals, vec, dm, sweeps, status, budget: int):
+        """nnhip_phonon_bands_large on the crystals `large` selects, the wave vectors in chunks (plan_q_chunks).  A chunk that is not
+        the whole call writes outputs of its own, which are copied into place: the kernels lay a crystal's values out by the
+        number of wave vectors of their call."""
+        L, dev, B, Q = hip.lib(), self.fc.device, len(self.counts), q_dev.shape[0]
+        select = torch.tensor(large, dtype=torch.uint8)
+        want = 0 if vec is None else 1
+
+        def ws_bytes(n_q):
+            return int(L.nnhip_phonon_large_ws_bytes(self._cry_host.data_ptr(), B, n_q, want, select.data_ptr()))
+
+        def run(q_c, n_q, ev_c, vec_c, dm_c, sw_c, st_c):
+            nbytes = ws_bytes(n_q)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            rc = L.nnhip_phonon_bands_large(hip._ptr(self.fc), hip._ptr(self.fc_ptr), hip._ptr(self.cry_ptr), self._cry_host.data_ptr(),
+                                            hip._ptr(self.sc_atoms), hip._ptr(self.img_ptr), hip._ptr(self.img_start),
+                                            hip._ptr(self.img_off), hip._ptr(self.masses), hip._ptr(self.out_ptr), B, hip._ptr(q_c), n_q,
+                                            hip._ptr(ev_c), hip._ptr(vec_c), hip._ptr(dm_c), hip._ptr(sw_c), hip._ptr(st_c),
+                                            select.data_ptr(), hip._ptr(ws), nbytes, hip._stream(dev))
+            if rc == 2:
+                raise NotImplementedError(L.nnhip_last_error().decode())
+            hip._check(rc, 'nnhip_phonon_bands_large')
+
+        chunks = plan_q_chunks(Q, ws_bytes(1), budget)
+        if len(chunks) == 1:
+            run(q_dev, Q, evals, vec, dm, sweeps, status)
+            return
+        n_val, n_sq = 3 * sum(self.counts), sum(9 * n * n for n in self.counts)
+        for q0, q1 in chunks:
+            C = q1 - q0
+            ev_c = torch.zeros(C * n_val, dtype=torch.float32, device=dev)
+            vec_c = None if vec is None else torch.zeros(C * n_sq, 2, dtype=torch.float32, device=dev)
+            dm_c = None if dm is None else torch.zeros(C * n_sq, 2, dtype=torch.float32, device=dev)
+            sw_c, st_c = (torch.zeros(B, C, dtype=torch.int32, device=dev) for _ in range(2))
+            run(q_dev[q0:q1].contiguous(), C, ev_c, vec_c, dm_c, sw_c, st_c)
+            for b in range(B):
+                if not large[b]:
+                    continue
+                d, o, so = self._dims[b], self._offsets[b], self._sq_offsets[b]
+                evals[Q * o:Q * (o + d)].view(Q, d)[q0:q1] = ev_c[C * o:C * (o + d)].view(C, d)
+                for full, part in ((vec, vec_c), (dm, dm_c)):
+                    if full is not None:
+                        full[Q * so:Q * (so + d * d)].view(Q, d * d, 2)[q0:q1] = part[C * so:C * (so + d * d)].view(C, d * d, 2)
+                sweeps[b, q0:q1] = sw_c[b]
+                status[b, q0:q1] = st_c[b]
+
+    def band_structure(self, points, n_per_segment: int = 20, modes: bool = False, solver: Optional[str] = None) -> PhononBands:
         """frequencies() along the piecewise-linear path through `points` (band_path); the result also holds `path`, the
         cumulative length in 1 / Angstrom per crystal [B, Q], and `ticks`, the indices of the given points."""
         q, ticks = band_path(points, n_per_segment)
-        bands = self.frequencies(q, modes=modes)
+        bands = self.frequencies(q, modes=modes, solver=solver)
         bands.path = np.stack([path_length(q, c) for c in self._cells]) if len(self._cells) else np.zeros((0, len(q)))
         bands.ticks = ticks
         return bands
 
-    def mesh(self, n1: int, n2: int, n3: int, shift: bool = False) -> PhononMesh:
+    def mesh(self, n1: int, n2: int, n3: int, shift: bool = False, solver: Optional[str] = None) -> PhononMesh:
         """The spectra on the full n1 x n2 x n3 grid of monkhorst_pack (no symmetry reduction), eigenvalues only."""
-        return PhononMesh(self.frequencies(monkhorst_pack(n1, n2, n3, shift)), self)
+        return PhononMesh(self.frequencies(monkhorst_pack(n1, n2, n3, shift), solver=solver), self)
 
 
 # ---- from a model ----------------------------------------------------------------------------------------------------------------
@@ -486,14 +597,18 @@ def acoustic_sum_rule(phi: torch.Tensor) -> torch.Tensor:
     return phi
 
 
-def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor] = None, asr: bool = True) -> Phonons:
+def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor] = None, asr: bool = True,
+            solver: str = 'lds') -> Phonons:
     """Force constants of every primitive cell of the batch on its supercell at the current parameters (see the module text).
     supercell: three integers, or an integer [B, 3].  Every perpendicular width of a supercell must be at least twice the
     model's cutoff (its neighbour list takes one minimum image): ValueError otherwise, before any kernel.  A cell that is not
     orthogonal must be given as a symmetric matrix (symmetric_cell rotates any crystal into that form): the model's minimum-image
     shift is a lattice vector for such cells only.  masses: fp32 [N] amu
-    (None: standard atomic weights of z).  asr: impose the acoustic sum rule on the fp32 force constants."""
-    cells, S, counts = _checked_crystals(model, z, pos, cell, batch, supercell, _check_bound)
+    (None: standard atomic weights of z).  asr: impose the acoustic sum rule on the fp32 force constants.  solver: 'lds' (default:
+    primitive cells up to max_dim() = 96 coordinates), 'auto' or 'blocked' (up to max_dim_large() = 768): kept on the result as
+    the default of its frequencies / band_structure / mesh (see Phonons.frequencies)."""
+    _check_solver(solver)
+    cells, S, counts = _checked_crystals(model, z, pos, cell, batch, supercell, lambda c: _check_bound(c, solver))
     n_atoms = pos.shape[0]
     if masses is not None and masses.numel() != n_atoms:
         raise ValueError(f'masses: {masses.numel()} values for {n_atoms} atoms')
@@ -511,7 +626,8 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
         phi = blocks[ptr[b]:ptr[b] + 9 * N * N].view(N, 3, N, 3)[:, :, :n, :].permute(2, 3, 0, 1).contiguous()
         parts.append((acoustic_sum_rule(phi) if asr else phi).reshape(-1))
     fc_t = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
-    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev)
+    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev,
+                             solver)
 
 
 def _checked_crystals(model, z, pos, cell, batch, supercell, check_bound):

@@ -147,27 +147,29 @@ class MLAseCalculator(_Base):
         modes = nm.modes.cpu().numpy().reshape(n_frames, 3 * n_atoms, n_atoms, 3)
         return (freq[0], modes[0]) if n_frames == 1 else (freq, modes)
 
-    def phonons(self, atoms_or_list, supercell, asr: bool = True):
+    def phonons(self, atoms_or_list, supercell, asr: bool = True, solver: str = 'lds'):
         """Phonons of one crystal or a list of crystals (NewtonNet.phonons): a newtonnet_amd.phonons.Phonons over the
         primitive cells given, ready for frequencies(q), band_structure(points, n) and mesh(n1, n2, n3).  supercell: three
         integers, or one triple per structure.  Masses from atoms.get_masses() when the objects have it, else standard atomic
-        weights.  The structures may differ in size.  A method of its own: not a property of calculate()."""
+        weights.  The structures may differ in size.  solver: 'lds' (up to 32 atoms per primitive cell), 'auto' or 'blocked' (up
+        to 256), as NewtonNet.phonons takes it.  A method of its own: not a property of calculate()."""
         atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
         z, pos, cell, batch = self.format_data(atoms)
         masses = None
         if all(hasattr(a, 'get_masses') for a in atoms):
             masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
                                   dtype=torch.float32, device=pos.device)
-        return self.model.phonons(z, pos.float(), cell.float(), batch, supercell, masses=masses, asr=asr)
+        return self.model.phonons(z, pos.float(), cell.float(), batch, supercell, masses=masses, asr=asr, solver=solver)
 
-    def elastic_constants(self, atoms_or_list, supercell, relaxed: bool = True):
+    def elastic_constants(self, atoms_or_list, supercell, relaxed: bool = True, solver: str = 'lds'):
         """Elastic constants of one crystal or a list of crystals (NewtonNet.elastic_constants): a
         newtonnet_amd.elastic.ElasticConstants over the primitive cells given (C in eV / A^3; .gpa() converts).  supercell:
         three integers, or one triple per structure.  relaxed=True adds the relaxed-ion term (it assumes relaxed atoms).  The
-        structures may differ in size.  A method of its own: not a property of calculate()."""
+        structures may differ in size.  solver: as NewtonNet.elastic_constants takes it.  A method of its own: not a property of
+        calculate()."""
         atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
         z, pos, cell, batch = self.format_data(atoms)
-        return self.model.elastic_constants(z, pos.float(), cell.float(), batch, supercell, relaxed=relaxed)
+        return self.model.elastic_constants(z, pos.float(), cell.float(), batch, supercell, relaxed=relaxed, solver=solver)
 
     def sample(self, atoms, n_samples: int, temperature: float, quantum: bool = False, seed=None, solver: str = 'lds'):
         """n_samples geometries of one structure drawn from its harmonic distribution at `temperature` (K), as an
