@@ -1770,6 +1770,38 @@ int nnhip_phonon_bands_large(const float* fc, const int64_t* fc_ptr, const int32
                              size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
+ * Phonon group velocities (csrc/phonon_velocity.hip): d lambda / d q_cart and the velocity of every mode of every (crystal, q) problem
+ * in ONE launch, from the eigenpairs nnhip_phonon_bands / nnhip_phonon_bands_large wrote (either: the layouts are the same).
+ *   fc .. out_ptr, n_cry, q, n_q: as nnhip_phonon_bands takes them.  cells [n_cry][3][3] fp64 (device): the primitive lattice vectors
+ *     as rows, A.  direction [n_q][3] fp64 (device, may be null): the unit Cartesian direction n of each q, shared by all crystals;
+ *     null: q_cart / |q_cart| of each crystal, q_cart = 2 pi q @ inv(cell)^T, and (1, 0, 0) at q = 0.
+ *   evals, modes: inputs, as nnhip_phonon_bands writes them.  deg_tol, zero_tol [n_cry]: absolute, eV/(A^2 amu).
+ *   G_a,ij = dD_ij/dq_cart,a = (m_i m_j)^-1/2 sum_J Phi(i, J) (1 / m_iJ) sum_T (i r_a) exp(2 pi i q . x_T), r = x_T @ cell, then
+ *     (G_a + G_a^H) / 2: D's own sums (fp64 phase, copies ascending, fmaf) with one more factor per image.
+ *   Consecutive eigenvalues no more than deg_tol[b] apart form a group.  A group of one: dlam_a = Re e^H G_a e.  A group of g <= 16:
+ *     M_a = V^H G_a V, M_n = sum_a n_a M_a diagonalised (the Jacobi of nnhip_phonon_bands, eigenvalues ascending), and the group's
+ *     modes, in that order, take dlam_a = Re diag(U^H M_a U).  Inside a subgroup M_n leaves degenerate only the trace is invariant.
+ *   vel [.][3], laid out like evals x 3: dlam_a / (2 sqrt|lambda|), the derivative of sign(lambda) sqrt|lambda|, in sqrt(eV/amu)
+ *     (x 98.227 = A/ps); zero where |lambda| <= zero_tol[b] (defined = 0: the limit depends on the direction).  dlam (may be null):
+ *     d lambda / d q_cart, eV/(A amu).  group (may be null): per mode, the index of the first mode of its group.  defined: per mode.
+ *   status [n_cry][n_q]: bits 1 and 2 of nnhip_phonon_bands (nothing else of the problem is written); bit 3
+ *     (NNHIP_PHONON_STATUS_GROUP): a group above 16 modes -- its modes get zero, defined = 0; bit 4 (NNHIP_PHONON_STATUS_NONFINITE): a
+ *     non-finite eigenvalue or mode -- nothing of the problem is written beyond defined = 0.
+ * One workgroup per (crystal, q, tile of modes: all of them up to d = 96, 64 above); no workspace; every d up to
+ * nnhip_phonon_large_max_dim, checked from cry_ptr_host BEFORE any launch (NNHIP_E_UNSUPPORTED).  Every sum has a fixed order, no float
+ * atomics, one writer per output: a problem's result is bitwise repeatable and does not depend on the rest of the launch.
+ * Measured against fp64 (tests/test_hip_phonon_velocities.py): see DESIGN.md section 23b.
+ * ------------------------------------------------------------------------ */
+#define NNHIP_PHONON_STATUS_GROUP 8
+#define NNHIP_PHONON_STATUS_NONFINITE 16
+int nnhip_phonon_velocities(const float* fc, const int64_t* fc_ptr, const int32_t* cry_ptr, const int32_t* cry_ptr_host,
+                            const int32_t* sc_atoms, const int64_t* img_ptr, const int32_t* img_start, const double* img_off,
+                            const float* masses, const int64_t* out_ptr, int32_t n_cry, const double* cells, const double* q,
+                            int32_t n_q, const double* direction, const float* evals, const float* modes, const float* deg_tol,
+                            const float* zero_tol, float* vel, float* dlam, int32_t* group, uint8_t* defined, int32_t* status,
+                            void* stream);
+
+/* --------------------------------------------------------------------------
  * Analytic elastic constants of crystals.  The kernels, nnhip_elastic_fold and nnhip_elastic_relax are in csrc/elastic.hip;
  * nnhip_strain_vp is implemented in csrc/train_step.hip, next to the static tangent sweeps it drives.
  *   nnhip_strain_vp: the tangent-over-reverse pass of nnhip_hessian_vp seeded with a homogeneous strain instead of a position

@@ -40,6 +40,31 @@ __device__ __forceinline__ float2 ph_weight(const int* ist, const double* img_of
   return make_float2((float)(sr * inv), (float)(si * inv));
 }
 
+// dw_a(i, J) = (1 / m_iJ) sum_T (i r_a) exp(2 pi i q_frac . x), a = x, y, z: the weights of d D / d q_cart (csrc/phonon_velocity.hip).
+// The phase is that of ph_weight (the same fp64 product, the same reduction, the same sincospi); r = x @ cell (cell [3][3], the
+// primitive lattice vectors as rows, A) in fp64; the mean in fp64, every component rounded once.
+__device__ __forceinline__ void ph_dweight(const int* ist, const double* img_off, size_t ij, double q0, double q1, double q2,
+                                           const double* cell, float2* dw) {
+  const int k0 = ist[ij], k1 = ist[ij + 1];
+  double sr[3] = {0.0, 0.0, 0.0}, si[3] = {0.0, 0.0, 0.0};
+  for (int k = k0; k < k1; ++k) {
+    const double x0 = img_off[3 * (size_t)k], x1 = img_off[3 * (size_t)k + 1], x2 = img_off[3 * (size_t)k + 2];
+    double ph = q0 * x0 + q1 * x1 + q2 * x2;
+    ph -= rint(ph);   // [-1/2, 1/2]
+    double s, c;
+    sincospi(2.0 * ph, &s, &c);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double r = x0 * cell[a] + x1 * cell[3 + a] + x2 * cell[6 + a];
+      sr[a] -= r * s;   // i r (c + i s) = -r s + i r c
+      si[a] += r * c;
+    }
+  }
+  const double inv = k1 > k0 ? 1.0 / (double)(k1 - k0) : 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) dw[a] = make_float2((float)(sr[a] * inv), (float)(si[a] * inv));
+}
+
 // the sum over the copies R0 .. R0 + rc - 1 of one element: f points at Phi(i a, (R0, j) b), consecutive copies n atoms apart;
 // w(r) at wch[r * w_stride]
 __device__ __forceinline__ void ph_accumulate(const float* f, int n, const float2* wch, int w_stride, int rc, float& are, float& aim) {

@@ -18,8 +18,14 @@ primitive reciprocal vectors (q_frac . x_frac = q . r / 2 pi).
 
 Units as in vibrations.py: eigenvalues in eV / (A^2 amu), frequencies in cm^-1 (x 521.4709, negative = imaginary).
 
+Group velocities (frequencies / band_structure / mesh with velocities=True): one more launch, nnhip_phonon_velocities
+(csrc/phonon_velocity.hip; one per crystal from band_structure, whose segment directions depend on the cell), takes d lambda / d q_cart = e^H (dD/dq) e of every mode from the force constants, the image table and
+the modes the solver left on the device, with degenerate perturbation theory along a direction inside groups of (nearly) equal
+eigenvalues; v = d lambda / (2 sqrt|lambda|) in A/ps.  PhononMesh.transport_tensor sums C_v v v over such a mesh.
+
 Left out: the non-analytic LO-TO correction (it needs Born charges, which the model has not got), symmetry reduction of meshes
-and paths, group velocities, primitive cells above max_dim_large() coordinates.
+and paths, primitive cells above max_dim_large() coordinates; of the velocities: the Gamma limit of the acoustic branches,
+degenerate groups above MAX_DEGENERATE modes, and the split inside a subgroup the direction leaves degenerate.
 """
 from __future__ import annotations
 
@@ -38,6 +44,13 @@ EPS32 = _v.EPS32
 SOLVERS = _v.SOLVERS
 LARGE_WORKSPACE_BYTES = 1 << 30   # the wave vectors of a blocked call are chunked so that a chunk's workspace stays within this
 IMAGE_TABLE_BYTES = 1 << 28       # image_table walks the home atoms in chunks whose candidate array stays within this
+MAX_DEGENERATE = 16               # largest group of (nearly) equal eigenvalues nnhip_phonon_velocities rotates (status bit 3 above)
+STATUS_GROUP = hip.abi.CONSTANTS['NNHIP_PHONON_STATUS_GROUP']
+STATUS_NONFINITE = hip.abi.CONSTANTS['NNHIP_PHONON_STATUS_NONFINITE']
+# sqrt(eV / amu) in A / ps: omega (rad / s) of a unit eigenvalue is 2 pi c x its wavenumber; 98.227
+ANGSTROM_PER_PS_PER_SQRT_EV_AMU = _v.WAVENUMBER_PER_SQRT_EIGENVALUE * 2.0 * math.pi * _v._C_LIGHT * 1e-12
+# eV / (K A ps) in W / (m K): kappa / tau of transport_tensor per ps of relaxation time; 1602.18
+WATT_PER_M_K_PER_PS = _v._E_CHARGE * 1e10 * 1e12
 
 
 def max_dim() -> int:
@@ -158,6 +171,46 @@ def path_length(q, cell) -> np.ndarray:
     return np.concatenate([[0.0], np.cumsum(step)])
 
 
+def _check_direction(direction, n_q: int):
+    """None, or the unit fp64 [n_q, 3] of an explicit Cartesian direction ([3] or [n_q, 3], finite, non-zero)."""
+    if direction is None:
+        return None
+    n = direction.detach().double().cpu().numpy() if isinstance(direction, torch.Tensor) else np.asarray(direction, dtype=np.float64)
+    if n.shape not in ((3,), (n_q, 3)):
+        raise ValueError(f'direction: [3] or [{n_q}, 3] Cartesian components expected (got shape {tuple(n.shape)})')
+    n = np.broadcast_to(n, (n_q, 3))
+    if not np.isfinite(n).all():
+        raise ValueError('direction: finite components expected')
+    norm = np.linalg.norm(n, axis=1, keepdims=True)
+    if not (norm > 0.0).all():
+        raise ValueError('direction: a non-zero vector expected')
+    return np.ascontiguousarray(n / norm)
+
+
+class _PerCrystal(list):
+    """unit directions [Q, 3] per crystal: what band_structure hands frequencies in place of one direction for all crystals"""
+
+
+def _check_degeneracy_tol(tol):
+    if tol is not None and not (float(tol) >= 0.0 and math.isfinite(float(tol))):
+        raise ValueError(f'degeneracy_tol: a finite value >= 0 (relative to max |lambda|) expected (got {tol!r})')
+    return None if tol is None else float(tol)
+
+
+def segment_directions(points, n_per_segment: int, cell) -> np.ndarray:
+    """fp64 [Q, 3]: for every point of band_path(points, n_per_segment) the unit Cartesian direction of the segment it lies on in
+    the reciprocal lattice of `cell`; a tick belongs to the segment it starts, the last point to the last segment."""
+    p = np.asarray(points, dtype=np.float64)
+    recip = 2.0 * np.pi * np.linalg.inv(np.asarray(cell, dtype=np.float64).reshape(3, 3)).T
+    seg = (p[1:] - p[:-1]) @ recip
+    norm = np.linalg.norm(seg, axis=1, keepdims=True)
+    if not (norm > 0.0).all():
+        raise ValueError('points: a segment of zero length has no direction (velocities=True)')
+    seg = seg / norm
+    m = int(n_per_segment)
+    return np.ascontiguousarray(np.concatenate([np.repeat(seg, m, axis=0), seg[-1:]]))
+
+
 def symmetric_cell(pos, cell):
     """(pos', cell') of one crystal (pos [n,3], cell [3,3], numpy fp64) rotated rigidly so that cell' is a symmetric matrix: the
     polar decomposition cell = P Q (P symmetric positive definite, Q a rotation for a right-handed cell), cell' = P and
@@ -221,11 +274,27 @@ class PhononBands:
                  from (a C caller's mismatch; a Phonons keeps the two equal), bit 2 = a mass that is not positive and finite.
                  With bit 1 or 2 nothing else of the problem is written
     q            fp64 numpy [Q, 3]; path (band_structure only): fp64 numpy [B, Q] cumulative length in 1 / Angstrom, ticks
+    With velocities=True (None otherwise):
+    group_velocities  fp32 [Q sum d_b, 3]  A / ps (= 100 m / s), Cartesian: the gradient of the signed frequency the library reports,
+                 d lambda / d q_cart / (2 sqrt|lambda|).  Modes whose eigenvalues lie within the degeneracy tolerance of each other
+                 are rotated so that the perturbation along the problem's direction n is diagonal (eigenvalues of n . dD/dq
+                 ascending), which is what follows a band through a crossing along n.  Inside a subgroup that n . dD/dq leaves
+                 degenerate the individual values depend on the basis; their sum over the subgroup does not.
+    velocity_defined  bool [Q sum d_b]  False (and v = 0) for |lambda| <= the zero tolerance -- the acoustic modes at Gamma, whose limit
+                 depends on the direction -- and for the modes of a group above MAX_DEGENERATE (status bit 3 = STATUS_GROUP).
+                 status bit 4 = STATUS_NONFINITE: a non-finite eigenvalue or mode, nothing of the problem is defined
+    degenerate_group  int32 [Q sum d_b]  per mode, the index (within its [d_b]) of the first mode of its group
+    eigenvalue_gradients  fp32 [Q sum d_b, 3]  d lambda / d q_cart in eV / (A amu), what the velocities are made of (also where
+                 velocity_defined is False for a zero mode; zero for a group above the cap)
     """
 
     def __init__(self, **kw):
         self.path = None
         self.ticks = None
+        self.group_velocities = None
+        self.velocity_defined = None
+        self.degenerate_group = None
+        self.eigenvalue_gradients = None
         self.__dict__.update(kw)
 
     def crystal(self, b: int):
@@ -240,6 +309,13 @@ class PhononBands:
             return None
         Q, d, o = len(self.q), self._dims[b], self._sq_offsets[b]
         return x[Q * o:Q * (o + d * d)].view(Q, d, d)
+
+    def velocities(self, b: int):
+        """(group velocities [Q, d, 3] in A / ps, velocity_defined [Q, d]) of crystal b: views (velocities=True only)."""
+        if self.group_velocities is None:
+            raise ValueError('no group velocities: ask for them with velocities=True')
+        Q, d, o = len(self.q), self._dims[b], self._offsets[b]
+        return self.group_velocities[Q * o:Q * (o + d)].view(Q, d, 3), self.velocity_defined[Q * o:Q * (o + d)].view(Q, d)
 
     def dynamical(self, b: int):
         """D(q) of crystal b as complex64 [Q, d, d] (frequencies(..., dynamical_matrix=True) only)."""
@@ -347,6 +423,35 @@ class PhononMesh:
                                      Cv=s[:, 4].float(), temperature=T, threshold=thr,
                                      n_skipped_zero=torch.stack(n_zero) if n_zero else torch.zeros(0, dtype=torch.long, device=dev),
                                      n_skipped_imaginary=torch.stack(n_imag) if n_imag else torch.zeros(0, dtype=torch.long, device=dev))
+
+
+    def transport_tensor(self, temperature: float, tol_zero: Optional[float] = None) -> torch.Tensor:
+        """fp32 [B, 3, 3]: (1 / (Q V)) sum_{q, s} C_v(omega_qs, T) v_a v_b over the live modes (lambda > threshold(tol_zero), as
+        thermochemistry selects and counts them) whose velocity is defined, V the volume of the primitive cell: kappa / tau of
+        the constant-relaxation-time approximation, in W / (m K) per ps of relaxation time.  fp64 torch ops on the device.
+        Needs a mesh made with velocities=True (ValueError otherwise)."""
+        bands, ph = self.bands, self._ph
+        if bands.group_velocities is None:
+            raise ValueError('transport_tensor needs group velocities: make the mesh with velocities=True')
+        T = _v._temperature(temperature)
+        Q, dev = len(bands.q), bands.eigenvalues.device
+        thr = self.threshold(tol_zero)
+        out = []
+        for b in range(len(ph.counts)):
+            ev = bands.crystal(b)[0].reshape(-1).double()
+            v, ok = bands.velocities(b)
+            v, live = v.reshape(-1, 3).double(), (ev > thr[b]) & ok.reshape(-1)
+            if T == 0.0:
+                cv = torch.zeros_like(ev)
+            else:
+                eps = _v.EV_PER_SQRT_EIGENVALUE * torch.where(live, ev, torch.ones_like(ev)).sqrt()
+                x = (eps / (_v.K_BOLTZMANN * T)).clamp(max=100.0)
+                em, om = torch.exp(-x), -torch.expm1(-x)
+                cv = _v.K_BOLTZMANN * x * x * em / (om * om)
+            w = torch.where(live, cv, torch.zeros_like(cv))
+            vol = abs(float(np.linalg.det(ph._cells[b])))
+            out.append((w[:, None, None] * v[:, :, None] * v[:, None, :]).sum(dim=0) * (WATT_PER_M_K_PER_PS / (max(Q, 1) * vol)))
+        return (torch.stack(out) if out else torch.zeros(0, 3, 3, dtype=torch.float64, device=dev)).float()
 
 
 class Phonons:
@@ -460,7 +565,8 @@ class Phonons:
 
     # ---- wave vectors ---------------------------------------------------------------------------------------------------------
     def frequencies(self, q, modes: bool = False, dynamical_matrix: bool = False, solver: Optional[str] = None,
-                    workspace_bytes: Optional[int] = None) -> PhononBands:
+                    workspace_bytes: Optional[int] = None, velocities: bool = False, direction=None,
+                    degeneracy_tol: Optional[float] = None) -> PhononBands:
         """The spectra at the wave vectors q ([Q, 3], units of the primitive reciprocal vectors, shared by all crystals).
         modes=True also returns the eigenvectors; the eigenvalues are bitwise the same either way, and those of a q do not
         depend on the other q of the call.  dynamical_matrix=True also returns D(q).
@@ -469,12 +575,24 @@ class Phonons:
         blocked solver nnhip_phonon_bands_large (up to max_dim_large() = 768 coordinates; sweeps counts its OUTER sweeps);
         'blocked' -- every crystal through the blocked solver.  All land in one packed PhononBands.  The blocked solver works in
         a torch-owned workspace; the wave vectors are served in chunks whose workspace stays within workspace_bytes (None:
-        LARGE_WORKSPACE_BYTES; a chunk holds one q at least) -- the result does not depend on the chunking."""
+        LARGE_WORKSPACE_BYTES; a chunk holds one q at least) -- the result does not depend on the chunking.
+        velocities=True also returns the group velocities (PhononBands.group_velocities, velocity_defined, degenerate_group): the
+        modes are computed (and dropped again unless modes=True) and ONE launch of nnhip_phonon_velocities follows, whatever the
+        solver (band_structure's per-crystal directions: one launch per crystal); everything else of the result is bitwise what it is without the option.  direction: the Cartesian direction n
+        along which degenerate groups are split, [3] or [Q, 3], normalised here (None: that of q itself, q_cart / |q_cart|, and
+        (1, 0, 0) at q = 0).  degeneracy_tol: consecutive eigenvalues no more than degeneracy_tol max |lambda| apart (the maximum
+        over the crystal's spectra of the call) form a group; None: 8 x 2 d x 2^-24, the formula of PhononMesh.threshold, which is
+        also the tolerance below which |lambda| counts as zero.  Both tolerances are one number per crystal and call (the ABI
+        takes them per crystal), so they depend on which q share the call: the arithmetic of a (crystal, q) does not, but a gap or
+        an eigenvalue that lies between the tolerances of two calls is grouped, or flagged as zero, in one and not in the other."""
         solver = _check_solver(self.solver if solver is None else solver)
         qh = q.detach().double().cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q, dtype=np.float64)
         qh = np.ascontiguousarray(qh.reshape(-1, 3) if qh.size else qh.reshape(0, 3))
         if not np.isfinite(qh).all():
             raise ValueError('q: finite wave vectors expected')
+        dirs = direction if isinstance(direction, _PerCrystal) else _check_direction(direction, len(qh))
+        degeneracy_tol = _check_degeneracy_tol(degeneracy_tol)
+        want_modes, modes = modes, bool(modes or velocities)
         _check_bound(self.counts, solver)
         dev = self.fc.device
         if dev.type != 'cuda':
@@ -512,9 +630,45 @@ class Phonons:
                 self._bands_large(large, q_dev, evals, vec, dm, sweeps, status,
                                   LARGE_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes))
         freq = torch.sign(evals) * evals.abs().sqrt() * _v.WAVENUMBER_PER_SQRT_EIGENVALUE
-        return PhononBands(eigenvalues=evals, frequencies=freq, modes=None if vec is None else torch.view_as_complex(vec),
+        extra = self._velocities(q_dev, evals, vec, status, dirs, degeneracy_tol) if velocities else {}
+        return PhononBands(eigenvalues=evals, frequencies=freq,
+                           modes=None if vec is None or not want_modes else torch.view_as_complex(vec),
                            dynamical_matrix=None if dm is None else torch.view_as_complex(dm), sweeps=sweeps, status=status, q=qh,
-                           _dims=self._dims, _offsets=self._offsets, _sq_offsets=self._sq_offsets)
+                           _dims=self._dims, _offsets=self._offsets, _sq_offsets=self._sq_offsets, **extra)
+
+    def _velocities(self, q_dev, evals, vec, status, dirs, degeneracy_tol):
+        """nnhip_phonon_velocities on the assembled spectra of a call: ONE launch (dirs None or one [Q, 3] for all crystals), or one
+        per crystal (dirs a _PerCrystal of [Q, 3]: band_structure's segment directions depend on the crystal's cell).  status takes the
+        new bits."""
+        dev, B, Q = self.fc.device, len(self.counts), q_dev.shape[0]
+        n_val = 3 * sum(self.counts)
+        vel, dlam = (torch.zeros(Q * n_val, 3, dtype=torch.float32, device=dev) for _ in range(2))
+        group = torch.zeros(Q * n_val, dtype=torch.int32, device=dev)
+        defined = torch.zeros(Q * n_val, dtype=torch.uint8, device=dev)
+        vstatus = torch.zeros(B, Q, dtype=torch.int32, device=dev)
+        if B and Q and n_val:
+            # max |lambda| per crystal over the call: one segmented reduction (a crystal without atoms gives 0)
+            lengths = torch.tensor([Q * d for d in self._dims], dtype=torch.int64).to(dev)
+            scale = torch.segment_reduce(evals.abs(), 'max', lengths=lengths, unsafe=True).clamp_min(0.0)
+            default = torch.tensor([8.0 * EPS32 * 2 * d for d in self._dims], dtype=torch.float32, device=dev)
+            zero_tol = (default * scale).contiguous()
+            deg_tol = zero_tol if degeneracy_tol is None else (degeneracy_tol * scale).contiguous()
+            cells = torch.tensor(np.asarray(self._cells, dtype=np.float64).reshape(B, 3, 3), dtype=torch.float64).to(dev).contiguous()
+            runs = [(0, B, dirs)] if not isinstance(dirs, _PerCrystal) else [(b, b + 1, dirs[b]) for b in range(B) if self.counts[b]]
+            for b, e, n in runs:
+                n_dev = None if n is None else torch.tensor(n, dtype=torch.float64).to(dev).contiguous()
+                rc = hip.lib().nnhip_phonon_velocities(
+                    hip._ptr(self.fc), self.fc_ptr.data_ptr() + 8 * b, self.cry_ptr.data_ptr() + 4 * b, self._cry_host.data_ptr() + 4 * b,
+                    self.sc_atoms.data_ptr() + 4 * b, self.img_ptr.data_ptr() + 8 * b, hip._ptr(self.img_start), hip._ptr(self.img_off),
+                    hip._ptr(self.masses), self.out_ptr.data_ptr() + 8 * b, e - b, cells.data_ptr() + 72 * b, hip._ptr(q_dev), Q,
+                    hip._ptr(n_dev), hip._ptr(evals), hip._ptr(vec), deg_tol.data_ptr() + 4 * b, zero_tol.data_ptr() + 4 * b,
+                    hip._ptr(vel), hip._ptr(dlam), hip._ptr(group), hip._ptr(defined), vstatus.data_ptr() + 4 * Q * b, hip._stream(dev))
+                if rc == 2:
+                    raise NotImplementedError(hip.lib().nnhip_last_error().decode())
+                hip._check(rc, 'nnhip_phonon_velocities')
+            status |= vstatus
+        return dict(group_velocities=vel * ANGSTROM_PER_PS_PER_SQRT_EV_AMU, velocity_defined=defined.bool(), degenerate_group=group,
+                    eigenvalue_gradients=dlam)
 
     def _bands_large(self, large, q_dev, evals, vec, dm, sweeps, status, budget: int):
         """nnhip_phonon_bands_large on the crystals `large` selects, the wave vectors in chunks (plan_q_chunks).  A chunk that is not
@@ -562,18 +716,28 @@ class Phonons:
                 sweeps[b, q0:q1] = sw_c[b]
                 status[b, q0:q1] = st_c[b]
 
-    def band_structure(self, points, n_per_segment: int = 20, modes: bool = False, solver: Optional[str] = None) -> PhononBands:
+    def band_structure(self, points, n_per_segment: int = 20, modes: bool = False, solver: Optional[str] = None,
+                       velocities: bool = False) -> PhononBands:
         """frequencies() along the piecewise-linear path through `points` (band_path); the result also holds `path`, the
-        cumulative length in 1 / Angstrom per crystal [B, Q], and `ticks`, the indices of the given points."""
+        cumulative length in 1 / Angstrom per crystal [B, Q], and `ticks`, the indices of the given points.  velocities=True:
+        the group velocities, degenerate groups split along the Cartesian direction of the segment a point lies on (a tick belongs
+        to the segment it starts, the last point to the last segment)."""
         q, ticks = band_path(points, n_per_segment)
-        bands = self.frequencies(q, modes=modes, solver=solver)
+        if velocities:
+            dirs = _PerCrystal(segment_directions(points, n_per_segment, c) for c in self._cells)
+            bands = self.frequencies(q, modes=modes, solver=solver, velocities=True, direction=dirs)
+        else:
+            bands = self.frequencies(q, modes=modes, solver=solver)
         bands.path = np.stack([path_length(q, c) for c in self._cells]) if len(self._cells) else np.zeros((0, len(q)))
         bands.ticks = ticks
         return bands
 
-    def mesh(self, n1: int, n2: int, n3: int, shift: bool = False, solver: Optional[str] = None) -> PhononMesh:
-        """The spectra on the full n1 x n2 x n3 grid of monkhorst_pack (no symmetry reduction), eigenvalues only."""
-        return PhononMesh(self.frequencies(monkhorst_pack(n1, n2, n3, shift), solver=solver), self)
+    def mesh(self, n1: int, n2: int, n3: int, shift: bool = False, solver: Optional[str] = None, velocities: bool = False) -> PhononMesh:
+        """The spectra on the full n1 x n2 x n3 grid of monkhorst_pack (no symmetry reduction), eigenvalues only; velocities=True:
+        with the group velocities (direction=None: groups split along q itself), which PhononMesh.transport_tensor needs."""
+        if not velocities:
+            return PhononMesh(self.frequencies(monkhorst_pack(n1, n2, n3, shift), solver=solver), self)
+        return PhononMesh(self.frequencies(monkhorst_pack(n1, n2, n3, shift), solver=solver, velocities=True), self)
 
 
 # ---- from a model ----------------------------------------------------------------------------------------------------------------
