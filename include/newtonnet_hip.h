@@ -1802,6 +1802,37 @@ int nnhip_phonon_velocities(const float* fc, const int64_t* fc_ptr, const int32_
                             void* stream);
 
 /* --------------------------------------------------------------------------
+ * Strain slopes of phonon eigenvalues and mode Grueneisen parameters (csrc/phonon_gruneisen.hip): d lambda / d eta_k = e^H (dD/d eta_k) e
+ * of every mode of every (crystal, q) problem and every strain plane k in ONE launch, from the eigenpairs nnhip_phonon_bands /
+ * nnhip_phonon_bands_large wrote.
+ *   fc_ptr .. out_ptr, n_cry, q, n_q, evals, modes, deg_tol, zero_tol: as nnhip_phonon_velocities takes them (cells and direction are
+ *     not taken).  In place of fc: dfc, fp32, n_planes planes (1 .. 6) of d Phi / d eta_k; plane k starts at dfc + k plane_stride
+ *     (elements) and is laid out exactly as fc under fc_ptr.  dfc_split: one such plane, the perturbation along which degenerate groups
+ *     are split; it may be the same pointer as a plane of dfc (that plane is then streamed once).
+ *   dD_k,ij = (m_i m_j)^-1/2 sum_J dPhi_k(i, J) (1 / m_iJ) sum_T exp(2 pi i q . x_T), then (dD_k + dD_k^H) / 2: D's own sums (fp64
+ *     phase, copies ascending, fmaf) applied to plane k, so fc itself handed in as a plane assembles D(q) as the solvers do.
+ *   Groups as in nnhip_phonon_velocities.  A group of one: dlam_k = Re e^H dD_k e.  A group of g <= 16: M_s = V^H dD_split V is
+ *     diagonalised (eigenvalues ascending, ties by index) and the group's modes, in that order, take dlam_k = Re diag(U^H M_k U).
+ *   dlam [.][n_planes], laid out like evals x n_planes: d lambda / d eta_k, eV/(A^2 amu) per unit of the strain parameter.
+ *     gamma [.][n_planes] = -dlam / (2 lambda) where |lambda| > zero_tol[b], else 0.  group (may be null): per mode, the first mode of
+ *     its group.  defined: per mode, 0 for |lambda| <= zero_tol[b] and for the modes of a group above 16.
+ *   status [n_cry][n_q]: the bits of nnhip_phonon_velocities with the same meaning -- 1 and 2 (size, mass: nothing else of the problem
+ *     is written), NNHIP_PHONON_STATUS_GROUP (dlam = gamma = 0, defined = 0 for the group's modes), NNHIP_PHONON_STATUS_NONFINITE
+ *     (nothing of the problem is written beyond defined = 0).
+ * One workgroup per (crystal, q, tile of modes, plane): grid (n_q, tiles x n_planes, n_cry); a workgroup streams the split plane and its
+ * own, so plane k's result does not depend on n_planes.  No workspace, no float atomics, one writer per output: bitwise repeatable and
+ * independent of the rest of the launch.  Checked BEFORE any launch: null pointers, n_planes outside 1 .. 6, cry_ptr_host decreasing
+ * (NNHIP_E_INVALID); a crystal above nnhip_phonon_large_max_dim, more than 65535 crystals (NNHIP_E_UNSUPPORTED).
+ * Measured against fp64 (tests/test_hip_gruneisen.py): see DESIGN.md section 23c.
+ * ------------------------------------------------------------------------ */
+int nnhip_phonon_strain_slopes(const float* dfc, int32_t n_planes, int64_t plane_stride, const float* dfc_split, const int64_t* fc_ptr,
+                               const int32_t* cry_ptr, const int32_t* cry_ptr_host, const int32_t* sc_atoms, const int64_t* img_ptr,
+                               const int32_t* img_start, const double* img_off, const float* masses, const int64_t* out_ptr,
+                               int32_t n_cry, const double* q, int32_t n_q, const float* evals, const float* modes,
+                               const float* deg_tol, const float* zero_tol, float* dlam, float* gamma, int32_t* group,
+                               uint8_t* defined, int32_t* status, void* stream);
+
+/* --------------------------------------------------------------------------
  * Analytic elastic constants of crystals.  The kernels, nnhip_elastic_fold and nnhip_elastic_relax are in csrc/elastic.hip;
  * nnhip_strain_vp is implemented in csrc/train_step.hip, next to the static tangent sweeps it drives.
  *   nnhip_strain_vp: the tangent-over-reverse pass of nnhip_hessian_vp seeded with a homogeneous strain instead of a position

@@ -788,6 +788,18 @@ class NewtonNet(nn.Module):
         from newtonnet_amd import phonons as _p
         return _p.phonons(self, z, pos, cell, batch, supercell, masses=masses, asr=asr, solver=solver)
 
+    def gruneisen(self, z, pos, cell, batch, supercell, strain='volume', delta: float = 0.01, masses=None, asr: bool = True,
+                  solver: str = 'lds', phonons=None):
+        """Mode Grueneisen parameters of B crystals as a newtonnet_amd.gruneisen.Gruneisen: the derivative of the force constants
+        along `strain` ('volume', 'voigt' or symmetric matrices [K, 3, 3]) as a central difference, step `delta`, of the analytic
+        force constants at strained cells (ions follow the strain affinely).  Its frequencies(q) / band_structure(points, n) /
+        mesh(n1, n2, n3) give gamma = -(d lambda / d eta) / (2 lambda) of every mode in one launch (csrc/phonon_gruneisen.hip);
+        the mesh gives mean(T) and thermal_expansion(T, elastic).  The other arguments as phonons() takes them; phonons: the
+        central Phonons (None computes one).  Eval mode only; needs the 'energy' head; uses the current parameters."""
+        from newtonnet_amd import gruneisen as _g
+        return _g.gruneisen(self, z, pos, cell, batch, supercell, strain=strain, delta=delta, masses=masses, asr=asr, solver=solver,
+                            phonons=phonons)
+
     def sample_displacements(self, z, pos, cell, batch, n_samples: int, temperature: float, quantum: bool = False, masses=None,
                              generator=None, solver: str = 'lds'):
         """n_samples displaced geometries per molecule drawn from the harmonic distribution around `pos` at `temperature` (K):

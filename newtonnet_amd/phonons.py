@@ -23,6 +23,9 @@ Group velocities (frequencies / band_structure / mesh with velocities=True): one
 the modes the solver left on the device, with degenerate perturbation theory along a direction inside groups of (nearly) equal
 eigenvalues; v = d lambda / (2 sqrt|lambda|) in A/ps.  PhononMesh.transport_tensor sums C_v v v over such a mesh.
 
+Mode Grueneisen parameters and thermal expansion are newtonnet_amd/gruneisen.py: the same launch shape with the derivative of D taken
+along strain (csrc/phonon_gruneisen.hip), on planes of force-constant derivatives made with _force_constants below.
+
 Left out: the non-analytic LO-TO correction (it needs Born charges, which the model has not got), symmetry reduction of meshes
 and paths, primitive cells above max_dim_large() coordinates; of the velocities: the Gamma limit of the acoustic branches,
 degenerate groups above MAX_DEGENERATE modes, and the split inside a subgroup the direction leaves degenerate.
@@ -780,6 +783,14 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
     if not pos.is_cuda:
         raise RuntimeError('newtonnet_amd phonons run on an MI355X (ROCm) device only: move the model and the inputs to "cuda"')
     dev = pos.device
+    fc_t, sc_counts = _force_constants(model, z, pos, cells, S, counts, asr, dev)
+    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev,
+                             solver)
+
+
+def _force_constants(model, z, pos, cells, S, counts, asr: bool, dev):
+    """(fc fp32 packed [n_b, 3, N_b, 3] per crystal, atoms per supercell): the force-constant body of phonons(), shared with
+    newtonnet_amd/gruneisen.py, which runs it at strained cells.  cells, S, counts: what _checked_crystals returned."""
     z_sc, pos_sc, cell_sc, batch_sc, sc_counts = _supercell_batch(z, pos, cells, S, counts, dev)
     with torch.no_grad():
         blocks, blk_ptr, _ = _hessian.hessian_blocks_counts(model, z_sc, pos_sc, cell_sc, batch_sc, n_dirs=3 * max(counts))
@@ -790,8 +801,7 @@ def phonons(model, z, pos, cell, batch, supercell, masses: Optional[torch.Tensor
         phi = blocks[ptr[b]:ptr[b] + 9 * N * N].view(N, 3, N, 3)[:, :, :n, :].permute(2, 3, 0, 1).contiguous()
         parts.append((acoustic_sum_rule(phi) if asr else phi).reshape(-1))
     fc_t = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
-    return Phonons._assemble(fc_t, z.detach().reshape(-1).long(), pos.detach(), cell.detach(), cells, S, counts, sc_counts, m, dev,
-                             solver)
+    return fc_t, sc_counts
 
 
 def _checked_crystals(model, z, pos, cell, batch, supercell, check_bound):

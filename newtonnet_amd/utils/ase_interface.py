@@ -161,6 +161,20 @@ class MLAseCalculator(_Base):
                                   dtype=torch.float32, device=pos.device)
         return self.model.phonons(z, pos.float(), cell.float(), batch, supercell, masses=masses, asr=asr, solver=solver)
 
+    def gruneisen(self, atoms_or_list, supercell, strain='volume', delta: float = 0.01, asr: bool = True, solver: str = 'lds'):
+        """Mode Grueneisen parameters of one crystal or a list of crystals (NewtonNet.gruneisen): a newtonnet_amd.gruneisen.Gruneisen
+        over the primitive cells given, ready for frequencies(q), band_structure(points, n) and mesh(n1, n2, n3).  strain: 'volume',
+        'voigt' or symmetric matrices [K, 3, 3]; delta: the strain step of the central difference.  supercell, masses, solver: as
+        phonons() takes them.  A method of its own: not a property of calculate()."""
+        atoms = [atoms_or_list] if _is_single(atoms_or_list) else list(atoms_or_list)
+        z, pos, cell, batch = self.format_data(atoms)
+        masses = None
+        if all(hasattr(a, 'get_masses') for a in atoms):
+            masses = torch.tensor(np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in atoms]),
+                                  dtype=torch.float32, device=pos.device)
+        return self.model.gruneisen(z, pos.float(), cell.float(), batch, supercell, strain=strain, delta=delta, masses=masses, asr=asr,
+                                    solver=solver)
+
     def elastic_constants(self, atoms_or_list, supercell, relaxed: bool = True, solver: str = 'lds'):
         """Elastic constants of one crystal or a list of crystals (NewtonNet.elastic_constants): a
         newtonnet_amd.elastic.ElasticConstants over the primitive cells given (C in eV / A^3; .gpa() converts).  supercell:
