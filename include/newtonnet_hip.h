@@ -1866,6 +1866,55 @@ int nnhip_elastic_relax(const float* evals, const float* modes, const int64_t* b
                         void* stream);
 
 /* --------------------------------------------------------------------------
+ * Observables of recorded trajectories (csrc/observables.hip): the pair-distance histogram behind the radial distribution function and
+ * lagged time correlations (mean squared displacement, velocity autocorrelation).  Frames are [n_frames][n_atoms][3] fp32 with a frame
+ * stride in floats (>= 3 n_atoms); mol_ptr int32 [n_mol + 1] as everywhere; kind int32 [n_atoms]: the species index 0 .. n_kinds - 1
+ * of an atom, any other value (-1) = the atom is ignored.  tests/observables_ref.py restates both.
+ *
+ *   nnhip_rdf_accumulate: counts [n_mol][P][n_bins] int64, P = n_kinds (n_kinds + 1) / 2, is ADDED TO.  Of every frame and system,
+ *     every unordered pair i < j of counted atoms adds 1 to counts[b][p][k] where
+ *       r2 = pair_disp(pos_i, pos_j) of the neighbour list (csrc/pair_disp.h; bit for bit: fp32, no contraction, d = pos_i - pos_j,
+ *            for a periodic system f = d / L (diagonal cell, exact division) or the product with the fp32 image of the fp64 inverse,
+ *            n = rintf(f), d -= (c0 n0 + c1 n1) + c2 n2, r2 = fma(dz, dz, fma(dy, dy, dx dx)): a single image; positions may be
+ *            unwrapped),
+ *       k:   edge2[k] <= r2 < edge2[k+1]   (edge2 fp32 [n_bins + 1], non-decreasing, edge2[0] = 0; r2 >= edge2[n_bins] is not counted),
+ *       p:   the pair kind (a, c) = (min, max) of the two kinds, p = a n_kinds - a (a - 1) / 2 + (c - a): (0,0), (0,1), .., (1,1), ...
+ *     The bin edges are thresholds on r2: the caller forms edge2[k] = the smallest float T with sqrt_rn(T) >= r_k on the host (the
+ *     cut2_of construction of the neighbour list), so that bin k holds exactly the pairs with r_k <= sqrt_rn(r2) < r_{k+1}; the kernel
+ *     takes a square root only to propose a bin, the table decides.
+ *     cell: [n_frames][n_mol][3][3] with cell_frame_stride (floats) >= 9 n_mol, or [n_mol][3][3] with cell_frame_stride = 0 (the same
+ *     cells for every frame); an all-zero cell = that system is not periodic.  max_atoms: the size of the largest system (it sizes
+ *     the grid; a larger value costs idle workgroups, max_atoms < 2 = no pair: nothing is launched).
+ *     One workgroup = (system, tile of 64 atoms i, chunk of frames): uint32 counters in LDS, flushed with 64-bit integer atomics before
+ *     any of them can wrap.  Integer counts: the result does not depend on scheduling, on the grid or on how frames are split into calls.
+ *     Checked BEFORE any launch: n_kinds > NNHIP_RDF_MAX_KINDS, n_bins > NNHIP_RDF_MAX_BINS or P n_bins > NNHIP_RDF_MAX_COUNTERS (the LDS histogram; NNHIP_E_INVALID with a message);
+ *     more than 2^26 atoms or 65535 systems (NNHIP_E_UNSUPPORTED).
+ *
+ *   nnhip_time_correlation: sums [n_mol][n_kinds][max_lag + 1] fp64 is ADDED TO (one writer per element).  For lag l,
+ *       sums[b][s][l] += sum over origins t0 = 0, origin_every, 2 origin_every, ... with t0 + l < n_frames, and over the atoms i of
+ *                        system b with kind s, of term(i, t0, l), with a = x_i(t0), c = x_i(t0 + l), all fp32, no contraction:
+ *         mode 0:  v = fma(a_z, c_z, fma(a_y, c_y, a_x c_x))                                          (x(t0) . x(t0 + l))
+ *         mode 1:  d = c - a (three roundings);  v = fma(d_z, d_z, fma(d_y, d_y, d_x d_x))            (|x(t0 + l) - x(t0)|^2)
+ *         term = v, or weight_i v (one more rounding) when weight [n_atoms] is given.
+ *     Every term is converted to fp64 and every sum is in fp64, in this order: atoms in tiles of 16 (from the system's first atom),
+ *     origins in blocks of 64 frames; wave p of 4 takes the atoms p, p + 4, .. of a tile; per (atom, block) the terms are added
+ *     ascending in t0 to a subtotal, the subtotal to the accumulator of the atom's kind; at the end (p0 + p1) + (p2 + p3).  No float
+ *     atomics, no workspace: two identical calls give identical bits and the result does not depend on the grid.  Direct evaluation,
+ *     O(n_frames max_lag n_atoms): a workgroup = (system, 64 lags) stages the frames of an origin block and of the lags it meets in LDS.
+ *     Checked BEFORE any launch: max_lag outside 0 .. n_frames - 1, origin_every < 1, mode other than 0 / 1, n_kinds outside 1 .. 8
+ *     (NNHIP_E_INVALID); more than 65535 systems (NNHIP_E_UNSUPPORTED).
+ * ------------------------------------------------------------------------ */
+#define NNHIP_RDF_MAX_KINDS 8
+#define NNHIP_RDF_MAX_BINS 4096
+#define NNHIP_RDF_MAX_COUNTERS 16384
+int nnhip_rdf_accumulate(const float* pos, int64_t pos_frame_stride, int32_t n_frames, const float* cell, int64_t cell_frame_stride,
+                         const int32_t* mol_ptr, int32_t n_mol, int32_t n_atoms, int32_t max_atoms, const int32_t* kind,
+                         int32_t n_kinds, const float* edge2, int32_t n_bins, int64_t* counts, void* stream);
+int nnhip_time_correlation(const float* x, int64_t frame_stride, int32_t n_frames, const int32_t* mol_ptr, int32_t n_mol,
+                           int32_t n_atoms, const int32_t* kind, int32_t n_kinds, const float* weight, int32_t mode, int32_t max_lag,
+                           int32_t origin_every, double* sums, void* stream);
+
+/* --------------------------------------------------------------------------
  * Timing hook for bench.py: wraps the kernels of one nnhip_energy_forces call
  * in HIP events on `stream` and accumulates per-kernel-class milliseconds.
  * classes: 0 = edge kernels (message/force fwd+adjoint), 1 = all dense MFMA kernels, 2 = everything else,

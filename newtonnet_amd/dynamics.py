@@ -114,6 +114,48 @@ class Trajectory:
             return 2.0 * self.kinetic_energy / (K_BOLTZMANN * self._dof.clamp(min=1).float())
         return 2.0 * self.kinetic_energy / (3.0 * K_BOLTZMANN * self._counts.clamp(min=1).float())
 
+    # ---- observables (newtonnet_amd/observables.py): the frames stay on the device
+    _system = None       # (z, batch, cell, masses, timestep) of the run: Dynamics attaches it
+
+    def _observed(self):
+        if self._system is None:
+            raise AttributeError('this trajectory does not know its system: use newtonnet_amd.observables with z and batch')
+        return self._system
+
+    def _frame_cells(self):
+        """the cells of the frames: [B,3,3] here (they do not change); NPTTrajectory holds one set per frame"""
+        return self._observed()[2]
+
+    def _frame_spacing(self) -> float:
+        """fs between two recorded frames; ValueError unless the records are evenly spaced (one host read of `step`)"""
+        step = self.step.cpu()
+        d = step[1:] - step[:-1]
+        if d.numel() and not bool((d == d[0]).all()):
+            raise ValueError(f'the recorded steps {step.tolist()[:4]} ... {step.tolist()[-2:]} are not evenly spaced (the last record '
+                             f'is the final step): choose n_steps a multiple of record_every')
+        return self._observed()[4] * (int(d[0]) if d.numel() else 1)
+
+    def radial_distribution(self, r_max, n_bins, species=None):
+        """observables.RadialDistribution of every recorded frame (under the cell of its own frame), counted on the device"""
+        from newtonnet_amd import observables
+        z, batch = self._observed()[:2]
+        return observables.RadialDistribution(z, batch, r_max, n_bins, species=species).add(self.pos, self._frame_cells())
+
+    def mean_squared_displacement(self, max_lag, origin_every=1, species=None):
+        """observables.MSD of the recorded (unwrapped) positions; the records must be evenly spaced"""
+        from newtonnet_amd import observables
+        z, batch, cell = self._observed()[:3]
+        return observables.mean_squared_displacement(self.pos, z, batch, self._frame_spacing(), max_lag, origin_every=origin_every,
+                                                     species=species, n_mol=cell.shape[0])
+
+    def velocity_autocorrelation(self, max_lag, mass_weighted=False, origin_every=1, species=None):
+        """observables.VACF of the recorded velocities (mass_weighted: with the run's masses); the records must be evenly spaced"""
+        from newtonnet_amd import observables
+        z, batch, cell, masses = self._observed()[:4]
+        return observables.velocity_autocorrelation(self.vel, z, batch, self._frame_spacing(), max_lag,
+                                                    masses=masses if mass_weighted else None, origin_every=origin_every,
+                                                    species=species, n_mol=cell.shape[0])
+
 
 def _check_system(model, z, pos, cell, batch, masses, velocities, fixed, timestep, friction):
     """the model, the batch and the integrator's numbers, refused without touching the device; returns (N, B, timestep, friction)"""
@@ -412,6 +454,7 @@ class Dynamics:
                    self._counts)
         if self._dof is not None:
             traj._dof = self._dof
+        traj._system = (self.z, self.batch, self.cell, self.masses, self.timestep)
         return traj
 
     def _advance(self, pending: bool):

@@ -1132,6 +1132,94 @@ def bias_eval(hills: torch.Tensor, hill_par: torch.Tensor, group: int, n_hills: 
     return out
 
 
+RDF_MAX_KINDS, RDF_MAX_BINS, RDF_MAX_COUNTERS = _K['NNHIP_RDF_MAX_KINDS'], _K['NNHIP_RDF_MAX_BINS'], _K['NNHIP_RDF_MAX_COUNTERS']
+
+
+def check_histogram_size(n_kinds: int, n_bins: int):
+    """the LDS histogram of nnhip_rdf_accumulate: refused here as the library refuses it, without touching the device"""
+    n_kinds, n_bins = int(n_kinds), int(n_bins)
+    if not (1 <= n_kinds <= RDF_MAX_KINDS and 1 <= n_bins <= RDF_MAX_BINS and n_kinds * (n_kinds + 1) // 2 * n_bins <= RDF_MAX_COUNTERS):
+        raise ValueError(f'{n_kinds} kinds and {n_bins} bins are outside the histogram kernel: at most {RDF_MAX_KINDS} kinds, '
+                         f'{RDF_MAX_BINS} bins and n_kinds (n_kinds + 1) / 2 * n_bins <= {RDF_MAX_COUNTERS}')
+
+
+def _frames(name, t, dev=None):
+    """a block of frames [F,N,3]: float32, on `dev` when given, each frame contiguous (the frame stride is free); returns (F, N, stride)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f'{name}: a float32 tensor [F,N,3] expected')
+    F, N = t.shape[0], t.shape[1]
+    if N and (t.stride(2) != 1 or t.stride(1) != 3 or (F > 1 and t.stride(0) < 3 * N)):
+        raise ValueError(f'{name}: contiguous frames expected (strides {tuple(t.stride())})')
+    if dev is not None and t.device != dev:
+        raise ValueError(f'{name}: on {dev} expected (it is on {t.device})')
+    return F, N, (t.stride(0) if F > 1 else 3 * N)
+
+
+def _kinds(kind, N, dev):
+    if not isinstance(kind, torch.Tensor) or kind.dtype != torch.int32 or not kind.is_contiguous() or kind.numel() != N or kind.device != dev:
+        raise ValueError(f'kind: a contiguous int32 tensor [{N}] on {dev} expected')
+
+
+def rdf_accumulate(pos: torch.Tensor, cell: torch.Tensor, mol_ptr: torch.Tensor, kind: torch.Tensor, n_kinds: int,
+                   edge2: torch.Tensor, counts: torch.Tensor, max_atoms: int):
+    """Add the pair-distance histogram of the frames pos [F,N,3] to counts, int64 [B, n_kinds (n_kinds + 1) / 2, n_bins]
+    (nnhip_rdf_accumulate, csrc/observables.hip; include/newtonnet_hip.h states which pair lands where).  cell: [B,3,3] (every frame)
+    or [F,B,3,3]; mol_ptr int32 [B+1]; kind int32 [N] (0 .. n_kinds - 1, -1 = ignored); edge2 fp32 [n_bins + 1]: the bin edges as
+    thresholds on r2; max_atoms: the size of the largest system."""
+    dev = pos.device if isinstance(pos, torch.Tensor) else None
+    F, N, stride = _frames('pos', pos)
+    B = _offsets('mol_ptr', mol_ptr, dev)
+    _kinds(kind, N, dev)
+    if not isinstance(edge2, torch.Tensor) or edge2.dtype != torch.float32 or not edge2.is_contiguous() or edge2.dim() != 1 \
+            or edge2.numel() < 2 or edge2.device != dev:
+        raise ValueError(f'edge2: a contiguous float32 tensor [n_bins + 1] on {dev} expected')
+    n_bins, n_kinds = edge2.numel() - 1, int(n_kinds)
+    check_histogram_size(n_kinds, n_bins)
+    _written(dev, counts=(counts, B * (n_kinds * (n_kinds + 1) // 2) * n_bins, torch.int64))
+    if not isinstance(cell, torch.Tensor) or cell.dtype != torch.float32 or not cell.is_contiguous() or cell.device != dev \
+            or tuple(cell.shape) not in ((B, 3, 3), (F, B, 3, 3)):
+        raise ValueError(f'cell: a contiguous float32 tensor [{B},3,3] or [{F},{B},3,3] on {dev} expected')
+    cell_stride = 9 * B if cell.dim() == 4 else 0
+    if not 0 <= int(max_atoms) <= N:
+        raise ValueError(f'max_atoms: 0 .. {N} expected (got {max_atoms})')
+    _check(lib().nnhip_rdf_accumulate(_ptr(pos), stride, F, _ptr(cell), cell_stride, _ptr(mol_ptr), B, N, int(max_atoms), _ptr(kind),
+                                      n_kinds, _ptr(edge2), n_bins, _ptr(counts), _stream(dev)), 'nnhip_rdf_accumulate')
+
+
+TC_PRODUCT, TC_DISPLACEMENT = 0, 1          # modes of nnhip_time_correlation
+
+
+def check_correlation(n_frames: int, max_lag, origin_every, mode=TC_PRODUCT):
+    """the arguments nnhip_time_correlation refuses, refused here without touching the device; returns (max_lag, origin_every)"""
+    if int(max_lag) != max_lag or not 0 <= max_lag < n_frames:
+        raise ValueError(f'max_lag: an integer in 0 .. n_frames - 1 = {n_frames - 1} expected (got {max_lag!r}): a lag needs two '
+                         f'frames that far apart')
+    if int(origin_every) != origin_every or origin_every < 1:
+        raise ValueError(f'origin_every: an integer >= 1 expected (got {origin_every!r})')
+    if mode not in (TC_PRODUCT, TC_DISPLACEMENT):
+        raise ValueError(f'mode: {TC_PRODUCT} (product) or {TC_DISPLACEMENT} (squared displacement) expected (got {mode!r})')
+    return int(max_lag), int(origin_every)
+
+
+def time_correlation(x: torch.Tensor, mol_ptr: torch.Tensor, kind: torch.Tensor, n_kinds: int, mode: int, max_lag: int,
+                     sums: torch.Tensor, origin_every: int = 1, weight: Optional[torch.Tensor] = None):
+    """Add the lagged correlation of the frames x [F,N,3] to sums, fp64 [B, n_kinds, max_lag + 1] (nnhip_time_correlation,
+    csrc/observables.hip): per system, kind and lag the sum over origins 0, origin_every, ... and atoms of x(t0) . x(t0 + l)
+    (TC_PRODUCT) or |x(t0 + l) - x(t0)|^2 (TC_DISPLACEMENT), times weight [N] when given.  fp32 terms, fp64 sums in a fixed order."""
+    dev = x.device if isinstance(x, torch.Tensor) else None
+    F, N, stride = _frames('x', x)
+    max_lag, origin_every = check_correlation(F, max_lag, origin_every, mode)
+    B = _offsets('mol_ptr', mol_ptr, dev)
+    _kinds(kind, N, dev)
+    n_kinds = int(n_kinds)
+    if not 1 <= n_kinds <= RDF_MAX_KINDS:
+        raise ValueError(f'n_kinds: 1 .. {RDF_MAX_KINDS} expected (got {n_kinds})')
+    _written(dev, sums=(sums, B * n_kinds * (max_lag + 1), torch.float64))
+    weight, = _read(dev, weight=(weight, N))
+    _check(lib().nnhip_time_correlation(_ptr(x), stride, F, _ptr(mol_ptr), B, N, _ptr(kind), n_kinds, _ptr(weight), int(mode),
+                                        max_lag, origin_every, _ptr(sums), _stream(dev)), 'nnhip_time_correlation')
+
+
 def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """out[e] = x[idx[e]] (idx int32)."""
     x = _f32c(x, 'x')

@@ -77,6 +77,9 @@ class NPTTrajectory(Trajectory):
     def density(self):
         return self._mass[None, :] / self.volume * AMU_PER_A3_IN_G_PER_CM3
 
+    def _frame_cells(self):
+        return self.cell
+
 
 class ConstantPressure(Dynamics):
     """B periodic systems advanced together on the device at constant pressure and temperature.
